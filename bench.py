@@ -16,12 +16,17 @@ the one real exchange of the path, the total-log-likelihood all-reduce (RCCL).
 
 Prints ONE JSON line on rank 0 (see the task contract), including
   "roofline":     algorithmic bytes per launch / measured kernel time vs 8 TB/s HBM
+  "per_rank":     (N > 1) every rank's kernel time per call and the time of its log Z all-reduce
+and, with --full only (a plain run sets up, warms up, times the steps and prints the line):
   "cpu_baseline": the C oracle (a port of the reference's CPU operation order;
                   the Julia reference cannot run here) timed on the host cores
                   on a bounded sample of the same workload.
   "sharp":        the same workload on the inputs of a trained acoustic model (log-softmax of 10 x N(0,1)), measured in the
                   same process after the timed region: ms_per_step, frac, redo_utterances, which kernels ran
-  "per_rank":     (N > 1) every rank's kernel time per call and the time of its log Z all-reduce
+
+    python bench.py --gpus 1 --steps 50 --warmup 10 --dump-outputs DIR
+writes what the last timed step returned as DIR/<name>.npy (float32 / float64, 64 MB at most: beyond that a fixed, seeded
+sample of the posterior frames), on inputs that are the same from run to run: two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -39,6 +44,8 @@ sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md: 8.0 TB/s spec, ~6.3 achievable)
+DUMP_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_SAMPLE_BYTES = 48 << 20  # ... of which the one large array (posteriors, paths, gradient) or its sample
 
 
 def make_workload(wl, name):
@@ -83,6 +90,40 @@ def measured_traffic(workload, B, N):
         if t.get("source_hash") == sha and (B, N) == (t.get("B"), t.get("N")):
             return t["hbm_bytes_per_launch"], os.path.relpath(f, ROOT)
     return None, None
+
+
+def sample_rows(x, seed=0):
+    """A [rows, cols] device tensor as float32 / float64 NumPy: whole if it fits in DUMP_SAMPLE_BYTES, else a fixed, seeded sample
+    of its rows (sorted), returned with the row indices (float64, exact) -- the same rows for the same shape in every run."""
+    import torch
+
+    x = x if x.dtype in (torch.float32, torch.float64) else x.double()
+    rows, row_bytes = x.shape[0], x.shape[1] * x.element_size()
+    if rows * row_bytes <= DUMP_SAMPLE_BYTES:
+        return x.cpu().numpy(), None
+    k = max(1, DUMP_SAMPLE_BYTES // row_bytes)
+    idx = np.sort(np.random.default_rng(seed).choice(rows, size=k, replace=False))
+    return x[torch.from_numpy(idx).to(x.device)].cpu().numpy(), idx.astype(np.float64)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs DIR: what the last timed step computed, as DIR/<name>.npy.  `arrays`: name -> device tensor; a 2-D or
+    larger one is dumped by sample_rows over its last axis (<name>.npy, and <name>_rows.npy with the flat row indices when
+    sampled), a smaller one whole."""
+    os.makedirs(d, exist_ok=True)
+    out = {}
+    for name, x in arrays.items():
+        if x.dim() >= 2:
+            out[name], idx = sample_rows(x.reshape(-1, x.shape[-1]))
+            if idx is not None:
+                out[name + "_rows"] = idx
+        else:
+            out[name] = x.cpu().numpy() if x.is_floating_point() else x.double().cpu().numpy()
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_BYTES, f"--dump-outputs: {total} bytes"
+    for name, a in out.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def algorithmic_bytes(g, B, N, lens_sum, semiring="log"):
@@ -362,16 +403,22 @@ def lfmmi_step_main(args):
         return wall, float(np.mean([a.elapsed_time(b) for a, b in ev]))
 
     Vg = V.clone().requires_grad_(True)
+    last = {}
 
     def full_step():
         Vg.grad = None
-        loss, _, _ = mm.lfmmi_loss(Vg, bnum, bden, lens)
+        loss, last["ttl_num"], last["ttl_den"] = mm.lfmmi_loss(Vg, bnum, bden, lens)
         loss.backward()
+        last["loss"] = loss
 
     den_ms = timed(lambda: bden.pdfposteriors(V, lens, out=buf))
     num_ms = timed(lambda: bnum.pdfposteriors(V, lens, out=buf))
     parts = {m: timed(lambda m=m: lf.posteriors_difference(V, bnum, bden, lens, m, out=buf)) for m in ("fused", "serial", "concurrent")}
     step_ms = timed(full_step)
+    if args.dump_outputs:  # (the headline's last step: loss, the two ttl and the gradient)
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, {"loss": last["loss"].detach(), "ttl_num": last["ttl_num"], "ttl_den": last["ttl_den"],
+                                         "grad": Vg.grad})
     # the fused step from one hipGraph
     bden.set_exact_policy("f32_first")
     side = torch.cuda.Stream()
@@ -435,7 +482,13 @@ def main():
     ap.add_argument("--sigma", type=float, default=10.0, help="sharpness of the peaky / consistent emissions")
     ap.add_argument("--posterior-floor", type=float, default=0.0,
                     help="mm_batch_set_posterior_floor (default: the library's 1e-30); 1e-12 keeps sharp emissions on the fast kernels")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline does not need: the `sharp` sub-records and the CPU baselines (each runs on its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.workload == "lfmmi_step":
         return lfmmi_step_main(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -489,13 +542,13 @@ def main():
     gamma = torch.empty(B, N, g.P, device="cuda") if semiring == "log" else None
 
     def call():
-        """one pass of the hot path over the batch: pdfposteriors (log semiring) or bestpath (tropical)"""
+        """one pass of the hot path over the batch: pdfposteriors (log semiring: gamma, ttl) or bestpath (tropical: path, score)"""
         if semiring == "log":
-            return bf.pdfposteriors(V, lens, out=gamma)[1]
-        return bf.viterbi(V, lens)[1]
+            return bf.pdfposteriors(V, lens, out=gamma)
+        return bf.viterbi(V, lens)
 
     def step():
-        ttl = call()
+        ttl = call()[1]
         return mm.dist.allreduce_logz(ttl) if use_dist else ttl
 
     if semiring == "log":
@@ -509,8 +562,9 @@ def main():
     t0 = time.perf_counter()
     for i in range(args.steps):
         ev[i][0].record()
-        ttl = call()
+        res = call()
         ev[i][1].record()
+        ttl = res[1]
         if use_dist:
             mm.dist.allreduce_logz(ttl)
             ev[i][2].record()
@@ -527,13 +581,16 @@ def main():
         per_rank = reduce_over_ranks(dist, torch, "cpu" if backend == "gloo" else "cuda", elapsed, frames_local, kernel_ms, allreduce_ms)
         elapsed, frames_total = per_rank["elapsed"], per_rank["frames_total"]
     assert os.environ.get("MM_BENCH_NOCHECK") or torch.isfinite(ttl).all(), "non-finite log-likelihoods"
+    if args.dump_outputs:  # (before anything else reuses the output buffer; one directory per rank beyond the first)
+        d = args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"rank{rank}")
+        dump_outputs(d, {"posteriors": res[0], "total_loglik": res[1]} if semiring == "log" else {"path": res[0], "score": res[1]})
     # utterances of the last call that the fast kernels handed to the exact ones (flag and redo): they were computed twice
     redo = bf.last_redo_count() if semiring == "log" else 0
     # team kernels: how many of the launches' workgroups found their whole team on one XCD (warm-up + timed steps)
     teams_xcd = bf.team_xcd_stats() if semiring == "log" else (0, 0)
 
     sharp = sharp_consistent = None
-    if semiring == "log" and args.emissions == "randn" and not args.no_sharp and args.posterior_floor <= 0:
+    if args.full and semiring == "log" and args.emissions == "randn" and not args.no_sharp and args.posterior_floor <= 0:
         ab = algorithmic_bytes(g, B, N, frames_local, semiring)
         wname = None if (args.varlen or args.batch or args.frames) else args.workload
         sharp = sharp_record(torch, bf, g, B, N, gamma, lens, ab, rank, workload=wname)
@@ -622,7 +679,7 @@ def main():
             "frac": lds_bytes / (kernel_ms * 1e-3) / 1e9 / (256 * 128 * 2.4),
             "note": "gathered LDS bytes only (arcs x 4 B x 2 passes); informative, the graded roofline is the HBM one",
         }
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # (1) one thread: faithful to the reference, whose CPU path is serial (src/inference.jl:62-110);
             # (2) all host hardware threads, OpenMP over utterances: the "whole node" denominator.
             cores = host_cores()

@@ -10,7 +10,7 @@ export TMPDIR=/tmp; R=$PWD; TAG=$1; WL=$2; shift 2
 NAME=${NAME:-$WL}
 PW=${PMC_WARMUP:-0}   # (calls before the one the counters are read for: LAST_CALL=1 makes tools/measure_summary.py take the last call alone)
 O=$R/gpurun_out/measure/${TAG}_${NAME}; rm -rf $O; mkdir -p $O
-timeout 600 python3 $R/bench.py --workload $WL --steps 20 --warmup 5 "$@" > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/bench.json
+timeout 600 python3 $R/bench.py --workload $WL --full --steps 20 --warmup 5 "$@" > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/bench.json
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --workload $WL --steps 5 --warmup 2 --no-cpu-baseline --no-sharp "$@" > $O/trace.log 2>&1
 timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -- python3 $R/bench.py --workload $WL --steps 1 --warmup $PW --no-cpu-baseline --no-sharp "$@" > $O/fetch.log 2>&1

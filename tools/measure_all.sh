@@ -11,14 +11,14 @@ P=gpurun_out/measure/profiles
 PMC_WARMUP=2 LAST_CALL=1 NAME=lfmmi_den_peaky bash tools/measure.sh "$1" lfmmi_den --emissions peaky --no-cpu-baseline > gpurun_out/measure_lfmmi_den_peaky.log 2>&1
 PMC_WARMUP=2 LAST_CALL=1 NAME=wsj_den_peaky bash tools/measure.sh "$1" wsj_den --emissions peaky --no-cpu-baseline > gpurun_out/measure_wsj_den_peaky.log 2>&1
 PMC_WARMUP=2 LAST_CALL=1 NAME=lfmmi_den_consistent bash tools/measure.sh "$1" lfmmi_den --emissions consistent --no-cpu-baseline > gpurun_out/measure_lfmmi_den_consistent.log 2>&1
-timeout 300 python3 bench.py --emissions peaky_offset --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | tail -1 > $P/$1_bench_lfmmi_den_peaky_offset.json
-timeout 300 python3 bench.py --workload lfmmi_den4000 --emissions peaky --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | tail -1 > $P/$1_bench_lfmmi_den4000_peaky.json
+timeout 300 python3 bench.py --full --emissions peaky_offset --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | tail -1 > $P/$1_bench_lfmmi_den_peaky_offset.json
+timeout 300 python3 bench.py --full --workload lfmmi_den4000 --emissions peaky --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | tail -1 > $P/$1_bench_lfmmi_den4000_peaky.json
 timeout 900 python3 tools/sharpness.py > $P/$1_sharpness.txt 2>/dev/null
 # SURVEY 8(d)'s second run of config 3: lengths U[750, 1500] (frames/s counts the frames inside the lengths)
-timeout 300 python3 bench.py --varlen --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | tail -1 > $P/$1_bench_lfmmi_den_varlen.json
-timeout 300 python3 bench.py --workload wsj_den --varlen --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | tail -1 > $P/$1_bench_wsj_den_varlen.json
+timeout 300 python3 bench.py --full --varlen --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | tail -1 > $P/$1_bench_lfmmi_den_varlen.json
+timeout 300 python3 bench.py --full --workload wsj_den --varlen --no-cpu-baseline --steps 20 --warmup 5 2>/dev/null | tail -1 > $P/$1_bench_wsj_den_varlen.json
 # config 4's global batch (B = 2048) on this one GPU: what eight GPUs would have to beat
-timeout 600 python3 bench.py --batch 2048 --no-cpu-baseline --steps 5 --warmup 2 2>/dev/null | tail -1 > $P/$1_bench_lfmmi_den_B2048_one_gpu.json
+timeout 600 python3 bench.py --full --batch 2048 --no-cpu-baseline --steps 5 --warmup 2 2>/dev/null | tail -1 > $P/$1_bench_lfmmi_den_B2048_one_gpu.json
 timeout 600 python3 bench.py --batch 2048 --varlen --no-cpu-baseline --no-sharp --steps 5 --warmup 2 2>/dev/null | tail -1 > $P/$1_bench_lfmmi_den_B2048_varlen_one_gpu.json
 # the caller's step (examples/test_cuda.jl:128-152): numerator + denominator + gradient, T = 700 and 150
 timeout 300 python3 bench.py --workload lfmmi_step --frames 700 --steps 20 --warmup 5 2>/dev/null | tail -1 > $P/$1_bench_lfmmi_step.json
@@ -28,7 +28,7 @@ timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/gpur
 cd $OLDPWD
 python3 tools/measure_summary.py "$1" lfmmi_step > /dev/null 2>&1
 # the N > 1 path of bench.py on this box's one GPU (two ranks over gloo)
-MM_BENCH_BACKEND=gloo timeout 300 python3 bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $P/$1_bench_lfmmi_den_2ranks_one_gpu_gloo.json
+MM_BENCH_BACKEND=gloo timeout 300 python3 bench.py --full --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $P/$1_bench_lfmmi_den_2ranks_one_gpu_gloo.json
 # graphs beyond config 3's size: more pdfs, more states (teams of 4 / 8), beyond every fast path; the stream kernels under the profiler
 timeout 600 python3 tools/bench_big.py $P/$1_bench_big.json > /dev/null 2>&1
 bash tools/measure_cmd.sh "$1" big10000 python3 $PWD/tools/bench_big.py 10000 1000 64 700 > gpurun_out/measure_big10000.log 2>&1
