@@ -113,7 +113,8 @@ int64_t mm_batch_total_states(mm_batch_t batch);
 /* Names of the kernels a run entry launches for this batch (the engine picks them from the graphs' sizes and
  * shapes): entry 0 = mm_pdfposteriors_f32, 1 = mm_viterbi_f32, 2 = what the last mm_pdfposteriors_ex call on the batch launched
  * (the recursion kernel; for ProbSemiring FSMs in float32 with general state maps, the emission GEMM C_hat * V_hat on the matrix
- * cores before it), 3 = mm_alpharecursion_f32 / mm_betarecursion_f32.  Informational (bench.py quotes it). */
+ * cores before it), 3 = mm_alpharecursion_f32 / mm_betarecursion_f32, 4 = mm_arcposteriors_f32 (log batches only).
+ * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
 int mm_batch_reserve(mm_batch_t batch, int64_t N);
@@ -147,6 +148,32 @@ size_t mm_batch_workspace_bytes(mm_batch_t batch, int64_t N);
 int mm_pdfposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n,
                          const int32_t *lens, int64_t N, float *gamma, int64_t g_stride_b, int64_t g_stride_n,
                          int64_t g_stride_p, float *ttl, void *stream);
+
+/* Arc posteriors: the expected number of times each arc is taken (Baum-Welch's xi summed over the frames), and the expected
+ * initial-state occupancy.  For utterance b, with the expanded emissions lhs = C_hat V_hat (expand() semantics, frames
+ * 1..N+1, length len_b) and Z_b the value mm_pdfposteriors_f32 normalises by, for each stored entry k = (i -> j) of the
+ * caller's T_hat, the phony-final column and the phony self-loop included:
+ *
+ *   c_b[k]    = sum_{n=1..N} alpha_n(i) * T_hat_ij * lhs_{n+1}(j) * beta_{n+1}(j) / Z_b        (linear, float32 out)
+ *   init_b[m] = alpha_hat_i * lhs_1(i) * beta_1(i) / Z_b    for the m-th stored entry i of alpha_hat
+ *
+ * So the real arcs sum to len_b - 1, the final (omega) arcs to 1, the phony self-loop gets N - len_b, sum_k c_b[k] = N and
+ * sum_m init_b[m] = 1 for every utterance that has a path; an utterance with no accepting path (len_b = 0 included) gets all
+ * counts 0 and ttl = -inf.  c_b[k] = d log Z_b / d log T_hat_ij: the gradient of log Z with respect to the arc log-weights.
+ *   V, lens, N   as mm_pdfposteriors_f32
+ *   counts       device, out: c_b[k] at counts[b*c_stride_b + k], k < nnz_b, in the order the caller gave T_hat's entries to
+ *                mm_fsm_create (CSC or CSR, as its layout said); slots nnz_b <= k < c_stride_b are left untouched.
+ *                c_stride_b < max_b nnz_b: MM_ERR_DIM.  NULL: MM_ERR_INVALID
+ *   init_counts  device, out (NULL: not computed): init_b[m] at init_counts[b*i_stride_b + m], m < n_init_b, in init_idx order;
+ *                i_stride_b < max_b n_init_b: MM_ERR_DIM
+ *   ttl          device float[B], out (NULL: not written): log Z_b, the value mm_pdfposteriors_f32 returns
+ * MM_LOG batches only: Tropical and ProbSemiring batches return MM_ERR_UNSUPPORTED.  Runs on the item form of every FSM (any
+ * size): the forward half of the item kernel, then a backward kernel that adds each arc's term to the sum of the one lane that
+ * holds the arc -- no atomics, so the result is bit-identical from call to call.  The exact, mark and gamma policies and the
+ * posterior floor do not apply to it.  Same stream contract as mm_pdfposteriors_f32: launches on `stream` only, no host
+ * synchronisation; it can be captured in a hipGraph once a first call has made the batch's arc forms and sized the workspace. */
+int mm_arcposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                         float *counts, int64_t c_stride_b, float *init_counts, int64_t i_stride_b, float *ttl, void *stream);
 
 /* alpha-recursion(alpha_hat, T_hat', C_hat*V_hat) (src/inference.jl:62-74) as
  * called from pdfposteriors (:150-152): out is the reference's state_A, a

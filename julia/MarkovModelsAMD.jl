@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -206,6 +206,38 @@ function pdfposteriors(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing; out:
         b.handle, pointer(V), P * N, P, lp, N, pointer(γ), 1, B * P, B, pointer(ttl),
         AMDGPU.stream().stream))
     γ, ttl
+end
+
+"""
+    arcposteriors(b::ROCBatch, V::ROCArray{Float32,3}, fsms, lens = nothing) -> (counts, init, ttl)
+
+Expected arc counts (mm_arcposteriors_f32 in the header: Baum-Welch's ξ summed over the frames) of a log-semiring batch.  `V`
+and `lens` as for `pdfposteriors`; `fsms` the FSMs the batch was compiled from, in its order (their patterns).  Returns, per
+utterance, a `SparseMatrixCSC` with the pattern of its `T̂` holding the counts (phony final column and self-loop included:
+the counts of an utterance with a path sum to N), the expected initial-state occupancy as a `SparseVector` with the
+pattern of its `α̂`, and ttl = log Z (a `Vector{Float32}`).  `counts[i, j]` is also ∂ log Z / ∂ log T̂[i, j].
+"""
+function arcposteriors(b::ROCBatch, V::ROCArray{Float32,3}, fsms::AbstractVector, lens = nothing)
+    P, N, B = size(V)
+    P == b.P || throw(DimensionMismatch("V has $P pdfs, the FSMs $(b.P)"))
+    length(fsms) == B || throw(DimensionMismatch("$(length(fsms)) FSMs for a batch of $B utterances"))
+    Ts = [SparseMatrixCSC(f.T̂) for f in fsms]      # (the entry order _create handed to mm_fsm_create: CSC)
+    αs = [SparseVector(f.α̂) for f in fsms]
+    K = maximum(nnz, Ts)
+    I = max(1, maximum(nnz, αs))
+    counts = ROCArray{Float32}(undef, K, B)          # utterance b's counts at column b: c_stride_b = K
+    init = ROCArray{Float32}(undef, I, B)
+    ttl = ROCArray{Float32}(undef, B)
+    lp = lens === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(lens))
+    check(ccall((:mm_arcposteriors_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Float32}, Int64, Ptr{Float32}, Int64,
+         Ptr{Float32}, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, lp, N, pointer(counts), K, pointer(init), I, pointer(ttl),
+        AMDGPU.stream().stream))
+    c, iv = Array(counts), Array(init)
+    mats = [SparseMatrixCSC(size(T, 1), size(T, 2), copy(T.colptr), copy(T.rowval), c[1:nnz(T), u]) for (u, T) in enumerate(Ts)]
+    inits = [SparseVector(length(a), copy(SparseArrays.nonzeroinds(a)), iv[1:nnz(a), u]) for (u, a) in enumerate(αs)]
+    mats, inits, Array(ttl)
 end
 
 """

@@ -182,6 +182,13 @@ struct mm_fsm_s {
     const float *d_init = nullptr;
     const int *d_s2p = nullptr;
     const int *d_pdf_ptr = nullptr, *d_pdf_rows = nullptr;  // pdf -> states (CSR)
+    // arc posteriors (MM_LOG): the caller's entry index of every entry of mat[1] (T_hat by source state, columns ascending, ties in
+    // the caller's order), the caller's entry of the phony self-loop (-1: none), the states of alpha_hat in init_idx order; the
+    // device form (ArcDev::k2slot, ::init_states) is made on the first mm_arcposteriors_f32 call that needs it
+    std::vector<int64_t> bwd_caller;
+    int64_t kphony = -1;
+    std::vector<int32_t> init_order;
+    void *arc_blob = nullptr;
 };
 
 // Test/diagnostic switches.  Read from the environment at mm_batch_create (and once per process for the entries that have no
@@ -308,6 +315,10 @@ struct mm_batch_s {
     mm_batch_s *log_twin = nullptr;
     float *prob_logv = nullptr;
     size_t prob_logv_bytes = 0;
+    // arc posteriors (mm_arcposteriors_f32): the utterances' ArcDev descriptors on the device (made on the first call), the float64
+    // sums of all their backward slots, the most caller entries / initial states of one FSM
+    ArcDev *d_arcs = nullptr;
+    int64_t arc_slots = 0, arc_max_nnz = 0, arc_max_init = 0;
 };
 
 // Launch geometry of the item kernels: NW waves per workgroup, NI register-resident items per wave
@@ -617,6 +628,9 @@ static int fsm_create_impl(int semiring, int64_t S1, int64_t nnz, int layout, in
         given.col[k] = int32_t(c);
         given.val[k] = rd_val(val, val_bytes, k) * scale;
     }
+    // (the caller's arrays as given, 0-based: the arc posteriors report in their entry order)
+    const std::vector<int64_t> given_ptr = semiring == MM_LOG ? given.rowptr : std::vector<int64_t>();
+    const std::vector<int32_t> given_idx = semiring == MM_LOG ? given.col : std::vector<int32_t>();
     sort_rows(given, S1);
     // MM_CSC(T_hat) is CSR(T_hat') = the forward matrix; MM_CSR(T_hat) the backward one
     Csr other = transpose(given, S1);
@@ -700,6 +714,25 @@ static int fsm_create_impl(int semiring, int64_t S1, int64_t nnz, int layout, in
     f->mat[0] = fwd;
     f->mat[1] = bwd;
     if (semiring == MM_LOG) {
+        // the caller's entry behind every entry of bwd (sort_rows and transpose are stable: a row of bwd lists its arcs by
+        // destination, the arcs of one (source, destination) in the caller's order)
+        f->bwd_caller.resize(size_t(nnz));
+        if (layout == MM_CSR) {
+            std::vector<int64_t> ks;
+            for (int64_t r = 0; r < S1; ++r) {
+                ks.clear();
+                for (int64_t k = given_ptr[size_t(r)]; k < given_ptr[size_t(r) + 1]; ++k) ks.push_back(k);
+                std::stable_sort(ks.begin(), ks.end(), [&](int64_t x, int64_t y) { return given_idx[size_t(x)] < given_idx[size_t(y)]; });
+                std::copy(ks.begin(), ks.end(), f->bwd_caller.begin() + given_ptr[size_t(r)]);
+            }
+        } else {  // CSC(T_hat): the caller's entries come by destination; bucket them by source
+            std::vector<int64_t> cur(bwd.rowptr.begin(), bwd.rowptr.end() - 1);
+            for (int64_t k = 0; k < nnz; ++k) f->bwd_caller[size_t(cur[size_t(given_idx[size_t(k)])]++)] = k;
+        }
+        for (int64_t k = given_ptr[size_t(S1 - 1)]; k < given_ptr[size_t(S1)] && f->kphony < 0; ++k)
+            if (given_idx[size_t(k)] == S1 - 1) f->kphony = k;
+        f->init_order.resize(size_t(n_init));
+        for (int64_t k = 0; k < n_init; ++k) f->init_order[size_t(k)] = int32_t(rd_index(init_idx, index_bytes, k) - index_base);
         // useful states: forward reachable (over out-arcs = rows of T_hat) and co-reachable (over in-arcs)
         std::vector<char> reach(S1, 0), coreach(S1, 0);
         std::vector<int32_t> stack;
@@ -1418,6 +1451,7 @@ int mm_fsm_destroy(mm_fsm_t f) {
         }
     if (f->dev_blob) (void)hipFree(f->dev_blob);
     if (f->lane_blob) (void)hipFree(f->lane_blob);
+    if (f->arc_blob) (void)hipFree(f->arc_blob);
     for (StreamForm *sf : f->stream_h) mm_stream_free(sf);
     for (auto &kv : f->variants) {
         if (kv.second->blob) (void)hipFree(kv.second->blob);
@@ -2255,6 +2289,7 @@ int mm_batch_destroy(mm_batch_t h) {
     if (h->stat_host) (void)hipHostFree(const_cast<int *>(h->stat_host));
     if (h->gen.ws) (void)hipFree(h->gen.ws);
     if (h->gen.d_utts) (void)hipFree(h->gen.d_utts);
+    if (h->d_arcs) (void)hipFree(h->d_arcs);
     delete h;
     return MM_OK;
 }
@@ -2458,6 +2493,11 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
                                  "mm_pair_export_kernel, then for marked utterances only the item kernel";
         s = h->semiring == MM_TROPICAL ? std::string("mm_tropical_kernel / mm_log_kernel<MODE_BETA, TROP>")
             : "alpha: " + (xa ? fast : std::string("mm_log_kernel<MODE_ALPHA>")) + "; beta: " + (xb ? fast : std::string("mm_log_kernel<MODE_BETA>"));
+    } else if (entry == 4) {  // mm_arcposteriors_f32
+        if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_arcposteriors_f32 runs on log-semiring batches only");
+        const Geometry g = pick_geometry(h);
+        s = "mm_log_kernel<MODE_FB," + std::to_string(g.NI) + ",1> (forward) + mm_arc_kernel<" + std::to_string(g.NI) +
+            "> (backward, the arcs' sums by their owning lanes) + mm_arc_scatter_kernel";
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -2862,6 +2902,132 @@ int mm_pdfposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
         }
     }
     return launch_log<MODE_FB>(h, p, stream);
+}
+
+// The arc forms of a batch (mm_kernel_arcs.hip): per FSM, the slot of the backward item form that holds each caller entry and the
+// initial states in init_idx order (uploaded once per FSM); per utterance, an ArcDev with its first slot in the float64 sums.
+// Made on the first mm_arcposteriors_f32 call, like the item forms: never during a stream capture.
+static int ensure_arc_forms(mm_batch_t h, void *stream) {
+    if (h->d_arcs) return MM_OK;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return fail(MM_ERR_INVALID, "the arc forms of this batch are not on the device yet: run mm_arcposteriors_f32 once outside a stream capture");
+    std::vector<ArcDev> arcs(size_t(h->B));
+    int64_t slots = 0;
+    for (int64_t b = 0; b < h->B; ++b) {
+        mm_fsm_t f = h->fsms[size_t(b)];
+        if (f->nnz > INT32_MAX) return fail(MM_ERR_UNSUPPORTED, "mm_arcposteriors_f32: more than 2^31 - 1 arcs in one FSM");
+        const Packed &pk = f->packed[1];  // (ensure_item_forms packed it)
+        if (!f->arc_blob) {
+            std::vector<int32_t> k2slot(size_t(f->nnz), -1);
+            const std::vector<int64_t> &rowptr = f->mat[1].rowptr;
+            for (size_t it = 0; it < pk.items.size(); ++it) {
+                const ItemMeta &im = pk.items[it];
+                const int g = 1 << im.log2g;
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int32_t row = pk.rowinfo[it * 64 + size_t(lane)].row;
+                    if (row < 0) continue;
+                    // (pack_rows: lane `sub` of the row's group holds arcs sub, sub + g, ... in slots k = 0, 1, ...)
+                    int64_t k = 0;
+                    for (int64_t a = rowptr[size_t(row)] + (lane & (g - 1)); a < rowptr[size_t(row) + 1]; a += g, ++k)
+                        k2slot[size_t(f->bwd_caller[size_t(a)])] = int32_t((int64_t(im.slot_row) + k) * 64 + lane);
+                }
+            }
+            Blob bl;
+            (void)bl.add(k2slot);  // (at 0)
+            (void)bl.add(f->init_order);
+            void *blob = nullptr;
+            const int rc = upload(bl, &blob);
+            if (rc) return rc;
+            f->arc_blob = blob;
+        }
+        ArcDev &a = arcs[size_t(b)];
+        const size_t o_i = align_up(size_t(f->nnz) * 4, 256);  // (where Blob::add put init_order, behind k2slot)
+        a.k2slot = static_cast<const int *>(f->arc_blob);
+        a.init_states = reinterpret_cast<const int *>(static_cast<const char *>(f->arc_blob) + o_i);
+        a.slot_off = slots;
+        a.nnz = int(f->nnz);
+        a.n_init = int(f->init_order.size());
+        a.kphony = int(f->kphony);
+        a.pad = 0;
+        slots += pk.n_slot_rows * 64;
+        h->arc_max_nnz = std::max<int64_t>(h->arc_max_nnz, f->nnz);
+        h->arc_max_init = std::max<int64_t>(h->arc_max_init, int64_t(f->init_order.size()));
+    }
+    void *d = nullptr;
+    HIP_TRY(hipMalloc(&d, sizeof(ArcDev) * size_t(h->B)));
+    if (hipMemcpy(d, arcs.data(), sizeof(ArcDev) * size_t(h->B), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return fail(MM_ERR_HIP, "mm_arcposteriors_f32: upload of the arc descriptors failed");
+    }
+    h->d_arcs = static_cast<ArcDev *>(d);
+    h->arc_slots = slots;
+    return MM_OK;
+}
+// workspace of mm_arcposteriors_f32: the item kernel's alpha~ store and offsets, the float64 slot sums, the frame-1 posteriors
+static size_t arc_ws_bytes(mm_batch_t h, int64_t N, size_t off[3]) {
+    off[0] = align_up(size_t(h->total_s1p) * size_t(N + 1) * 4, 256);
+    off[1] = off[0] + ws_c_bytes(h, N);
+    off[2] = off[1] + align_up(size_t(h->arc_slots) * 8, 256);
+    return off[2] + align_up(size_t(h->total_s1p) * 4, 256);
+}
+
+int mm_arcposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, float *counts,
+                         int64_t csb, float *init_counts, int64_t isb, float *ttl, void *stream) {
+    if (h && h->semiring != MM_LOG)
+        return fail(MM_ERR_UNSUPPORTED, "mm_arcposteriors_f32: log-semiring batches only (this batch is " +
+                                            std::string(h->semiring == MM_TROPICAL ? "tropical" : "ProbSemiring") + ")");
+    int rc = check_run(h, "mm_arcposteriors_f32", V, N, MM_LOG);
+    if (rc) return rc;
+    if (!counts) return fail(MM_ERR_INVALID, "mm_arcposteriors_f32: counts is NULL");
+    // (the item forms first: a batch created without them has max_items = 0 until they are up, and pick_geometry would size the
+    // workgroups for no items)
+    rc = ensure_item_forms(h, stream);
+    if (rc) return rc;
+    rc = ensure_arc_forms(h, stream);
+    if (rc) return rc;
+    if (csb < h->arc_max_nnz)
+        return fail(MM_ERR_DIM, "mm_arcposteriors_f32: c_stride_b " + std::to_string(csb) + " < " + std::to_string(h->arc_max_nnz) + " entries of the largest FSM");
+    if (init_counts && isb < h->arc_max_init)
+        return fail(MM_ERR_DIM, "mm_arcposteriors_f32: i_stride_b " + std::to_string(isb) + " < " + std::to_string(h->arc_max_init) + " initial states of the largest FSM");
+    const Geometry g = pick_geometry(h);
+    const int NW = std::min(g.NW, 8);  // (mm_arc_kernel holds 8 items' arcs and their sums per wave: 8 waves per CU)
+    const int P1p = (h->max_P1 + 3) & ~3;
+    LdsPlan L = lds_plan(h->max_S1p, P1p, true);
+    const bool bigv = size_t(L.total) * 4 + 2 * MM_MAX_WAVES * 4 > 160 * 1024 || h->dbg.bigv || g.NI == 0;  // (mm_launch_arcs: + the posterior sums)
+    if (bigv) {
+        if (!h->ws_big) return fail(MM_ERR_UNSUPPORTED, "FSM too large for the LDS and no global-memory vectors were allocated");
+        L = lds_plan(0, P1p, true);
+        if (size_t(L.total) * 4 > 160 * 1024) return fail(MM_ERR_UNSUPPORTED, "too many pdfs for the LDS: " + std::to_string(h->max_P1));
+    }
+    size_t off[3];
+    rc = ensure_ws(h, std::max(mm_batch_workspace_bytes(h, N), arc_ws_bytes(h, N, off)), stream);
+    if (rc) return rc;
+    char *ws = static_cast<char *>(h->ws);
+    RunParams p{};
+    p.utts = h->d_utts;
+    p.V = V;
+    p.vsb = vsb;
+    p.vsn = vsn;
+    p.lens = lens;
+    p.N = int(N);
+    p.B = int(h->B);
+    p.ws_alpha = reinterpret_cast<float *>(ws);
+    p.ws_c = reinterpret_cast<double *>(ws + off[0]);
+    if (bigv) {
+        p.ws_big = h->ws_big;
+        p.big_stride = 4ll * h->max_S1p;
+    }
+    ArcParams ap{};
+    ap.arcs = h->d_arcs;
+    ap.acc = reinterpret_cast<double *>(ws + off[1]);
+    ap.post1 = reinterpret_cast<float *>(ws + off[2]);
+    ap.counts = counts;
+    ap.csb = csb;
+    ap.init_counts = init_counts;
+    ap.isb = isb;
+    ap.ttl = ttl;
+    return mm_launch_arcs(h->B, NW, g.NI, bigv, size_t(L.total) * 4, p, ap, static_cast<hipStream_t>(stream));
 }
 
 // alpha / beta export on the pair kernels (mm_pairs_tu.hip: mm_fbx_kernel + mm_pair_export_kernel): one shared graph in the pair

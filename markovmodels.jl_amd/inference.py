@@ -385,6 +385,28 @@ class BatchedFSM:
         out = out.t()  # (sum S1) x (N+1) like the reference's state_A / state_B
         return out.cpu().numpy() if as_numpy else out
 
+    def arcposteriors(self, V, lens=None, want_init=False):
+        """Expected arc counts (mm_arcposteriors_f32): ``(counts[B, max nnz], ttl[B])``, plus ``init[B, max n_init]`` when
+        ``want_init``.  ``counts[b, k]`` is the expected number of times utterance b takes the k-th stored entry of its FSM's
+        ``T_hat`` (the CSC data order of ``FSM.nzval``, phony final column and self-loop included), ``init[b, m]`` the posterior
+        of the m-th initial state (``FSM.alpha_idx`` order); entries beyond an FSM's own are 0.  ``ttl`` = log Z, as
+        ``pdfposteriors`` returns it.  Log batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        K = max(c.fsm.nnz for c in self.cfsms)
+        counts = torch.zeros((B, K), dtype=torch.float32, device=Vt.device)
+        ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        init = None
+        if want_init:
+            I = max(1, max(len(c.fsm.alpha_idx) for c in self.cfsms))
+            init = torch.zeros((B, I), dtype=torch.float32, device=Vt.device)
+        check(lib.mm_arcposteriors_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
+                                       lt.data_ptr() if lt is not None else None, N, counts.data_ptr(), counts.stride(0),
+                                       init.data_ptr() if init is not None else None, init.stride(0) if init is not None else 0,
+                                       ttl.data_ptr(), self._stream(torch)))
+        out = (counts, ttl) + ((init,) if want_init else ())
+        return tuple(t.cpu().numpy() for t in out) if as_numpy else out
+
     def maxstateposteriors(self, V, lens=None):
         """Max-marginals of the tropical semiring, (sum S1) x (N+1), computed on the device."""
         return self._export(lib.mm_maxstateposteriors_f32, V, lens)
@@ -467,11 +489,11 @@ class BatchedFSM:
 
     def kernels(self, semiring: str = "log") -> str:
         """The kernels the engine launches for this batch (informational): "log" = pdfposteriors, "tropical" = bestpath, "export" =
-        alpharecursion / betarecursion."""
+        alpharecursion / betarecursion, "arcs" = arcposteriors."""
         import ctypes
 
         buf = ctypes.create_string_buffer(512)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3}[semiring], buf, 512))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4}[semiring], buf, 512))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -765,6 +787,16 @@ def pdfposteriors(fsm, Vhats, Chats=None, seqlengths=None):
     V, lens = un
     g, ttl = bf.pdfposteriors(V, lens)
     return np.ascontiguousarray(g.transpose(0, 2, 1)), ttl
+
+
+def arcposteriors(fsm, Vhats, Chats=None, want_init=False):
+    """Expected arc counts of every utterance (Baum-Welch's xi summed over the frames): ``(counts[B, max nnz], ttl[B])``, plus
+    ``init[B, max n_init]`` with ``want_init`` -- see ``BatchedFSM.arcposteriors``.  ``fsm`` and the arguments as for
+    ``pdfposteriors``: the rawunion of the batch with its state maps, or a BatchedFSM / CompiledFSM; ``counts[b, k]`` belongs to
+    the k-th stored ``T_hat`` entry of utterance b's own FSM.  V_hats must be what ``expand`` makes.  NumPy arrays out."""
+    bf = _as_batch(fsm, Chats)
+    V, lens = _need_expanded(Vhats, bf.semiring)
+    return bf.arcposteriors(V, lens, want_init=want_init)
 
 
 def alpharecursion(fsm, Vhats, Chats=None):
