@@ -95,11 +95,6 @@ size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 }  // namespace
 
-#ifdef MM_STAMPS
-static unsigned long long *g_dbg = nullptr;
-static size_t g_dbg_n = 0;
-#endif
-
 // The quad form of one FSM laid out for KQ quads per lane (mm_pack.h), resident on the device.
 struct QuadVariant {  // the quad form of ONE direction of an FSM for one KQ (quads per lane)
     int KQ = 0, dir = 0;
@@ -251,6 +246,10 @@ static const DebugOpts &process_debug_opts() {
     return d;
 }
 
+// The kernels mm_pdfposteriors_f32 launches first on a log batch (pick_family).  Quad and Item: none of the linear-domain families
+// takes the batch; the quad kernels where they are usable (mm_batch_s::quad_ok), else the item kernel.
+enum class Fb { Item, Quad, Rows, Pairs, Split, Lane, Wave, Stream };
+
 struct mm_batch_s {
     DebugOpts dbg;
     std::vector<mm_fsm_t> fsms;
@@ -265,18 +264,16 @@ struct mm_batch_s {
     int xcsr = 0;          // floats of LDS reserved for it (0: it stays in global memory)
     bool fast_ok = true;
     int geo_kq[2] = {0, 0}, geo_nw[2] = {1, 1};  // quad kernel geometry of the forward and the backward kernel
-    bool rows_ok = false;                        // every FSM has its row-lane forms: the row kernels can run
+    Fb fb = Fb::Item;
+    bool quad_ok = false;  // the quad kernels run where the item kernel would: first (Quad), and after the rows, pair and float64 kernels
     int row_ka[2] = {0, 0}, row_nwc[2] = {1, 1}, row_slotrows[2] = {0, 0};
-    bool pairs_ok = false;                       // one FSM shared by all utterances, in pair form: the pair kernels can run
     int pair_ka = 0, pair_nwc = 1, pair_slotrows = 0;
     bool vit_ok = false;   // every FSM has its Viterbi form: mm_vit_kernel + mm_vit_backtrace_kernel can run
     int vit_n4 = 0, vit_n2 = 0, vit_arcs = 0;
-    bool lane_ok = false;  // every FSM has at most 64 states and 64 pdfs: the lane kernel runs (one wave per utterance and direction)
-    int lane_S = 0;        // ... the most states of one
-    bool lane_redo_wave = false;  // ... and every FSM has its wave forms too: what the lane kernel marks goes to the wave kernel (else: the item kernel)
-    bool wave_ok = false;  // every FSM has its wave forms: the wave kernel can run (small graphs that are off the linear paths)
+    int lane_S = 0;        // (lane kernel) the most states of one FSM
+    bool lane_redo_wave = false;  // ... every FSM has its wave forms too: what the lane kernel marks goes to the wave kernel (else: the item kernel)
     int wave_nseg = 0;
-    int pair_H = 1;        // workgroups per team: 1 = the pair kernels proper, > 1 = the split pair kernels
+    int pair_H = 1;        // workgroups per team: 1 = the pair kernels proper (Pairs), > 1 = the split pair kernels (Split)
     int split_s1p = 0;     // floats / 2 of a stored vector of the split kernels (positions of the team's vector, padded)
     bool deterministic = false;  // mm_batch_set_deterministic(): no float atomics in the item kernel
     float lt_floor = -20.f;      // mm_batch_set_posterior_floor(): smallest accepted log2 overlap of a frame (mm_pair_finish_kernel)
@@ -298,8 +295,7 @@ struct mm_batch_s {
     std::vector<UttDesc> utts_host;     // what d_utts holds
     bool items_resident = true;         // the FSMs' item forms are on the device (a batch of the wave kernel uploads them on first need)
     bool dpair_ok = false;
-    int stream_S1 = 0, stream_H = 1;    // ... the most states of one; workgroups of a team (mm_stream_pick_h)
-    bool stream_ok = false;             // every FSM has a stream form and nothing faster takes the batch (mm_stream.hip)
+    int stream_S1 = 0, stream_H = 1;    // (stream kernels) the most states of one FSM; workgroups of a team (mm_stream_pick_h)
     bool wpair_ok = false;              // a whole batch on the exact kernels fits the wide pair kernels (mm_kernel_wpair.hip: two utterances per workgroup)
     bool quad_built = false;            // the FSMs' quad forms exist (not built for batches whose exact path is the float64 kernels)
     int *stat_dev = nullptr;            // {count, ticket, team workgroups whose team sits on ONE XCD, team workgroups} (the last two: mm_batch_team_xcd_stats)
@@ -320,6 +316,67 @@ struct mm_batch_s {
     ArcDev *d_arcs = nullptr;
     int64_t arc_slots = 0, arc_max_nnz = 0, arc_max_init = 0;
 };
+
+static bool on_pairs(mm_batch_t h) { return h->fb == Fb::Pairs || h->fb == Fb::Split; }
+
+static bool capturing(void *stream) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return stream && hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
+// what every run entry hands its kernels: the utterances, their log-likelihoods V[b][n][p] and lengths, the frames
+static RunParams run_params(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N) {
+    RunParams p{};
+    p.utts = h->d_utts;
+    p.V = V;
+    p.vsb = vsb;
+    p.vsn = vsn;
+    p.lens = lens;
+    p.N = int(N);
+    p.B = int(h->B);
+    return p;
+}
+
+// (team kernels) ticks of s_memrealtime a poll waits before it gives the team up
+static unsigned long long x_timeout(int64_t N) {
+    return std::min<unsigned long long>(10000000ull, std::max<unsigned long long>(200000ull, 1000ull * (unsigned long long)N));
+}
+
+#ifdef MM_STAMPS
+static unsigned long long *g_dbg = nullptr;
+static size_t g_dbg_n = 0;
+#endif
+// (diagnostic build) where the kernels add their per-wave phase cycle sums
+static void bind_stamps(mm_batch_t h, RunParams &p) {
+#ifdef MM_STAMPS
+    if (!g_dbg) {
+        g_dbg_n = size_t(16) * MM_MAX_WAVES * size_t(h->B);
+        (void)hipMalloc(&g_dbg, sizeof(unsigned long long) * g_dbg_n);
+    }
+    p.dbg = g_dbg;
+#endif
+}
+
+static PairLaunch pair_launch_of(mm_batch_t h) {
+    PairLaunch pl;
+    pl.B = h->B;
+    pl.nwc = h->pair_nwc;
+    pl.slotrows = h->pair_slotrows;
+    pl.max_P1 = h->max_P1;
+    pl.pair_ka = h->pair_ka;
+    pl.H = h->pair_H;
+    pl.small = h->pair_H == 1 && h->max_S1p <= 128;
+    return pl;
+}
+
+static WaveLaunch wave_launch_of(mm_batch_t h) {
+    WaveLaunch wl;
+    wl.B = h->B;
+    wl.nseg = h->wave_nseg;
+    wl.max_P1 = h->max_P1;
+    wl.n_cus = h->n_cus;
+    return wl;
+}
 
 // Launch geometry of the item kernels: NW waves per workgroup, NI register-resident items per wave
 // (mm_kernels.hip, "Register-resident graph"; 8 items keep 16 waves per CU inside the 128-VGPR
@@ -346,8 +403,7 @@ static int fsm_to_device(mm_fsm_t f);
 // utterance descriptors, once, when an entry that runs the item / tropical kernels is first called on the batch.
 static int ensure_item_forms(mm_batch_t h, void *stream) {
     if (h->items_resident) return MM_OK;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    if (capturing(stream))
         return fail(MM_ERR_INVALID, "the item forms of this batch are not on the device yet: run the entry once outside a stream capture");
     for (int64_t b = 0; b < h->B; ++b) {
         mm_fsm_t f = h->fsms[size_t(b)];
@@ -417,9 +473,9 @@ static size_t quad_lds_bytes(mm_batch_t h, int dir) {
     return (size_t(lds_plan_q(h->max_S1p, P1p, std::max(vl, 64 * NW) * KQ).total) + size_t(h->xcsr)) * 4;
 }
 
+// (batch creation: h->quad_ok.  No quad forms are built for the lane, wave and stream kernels, nor without fast_ok)
 static bool quad_kernel_usable(mm_batch_t h) {
-    if (h->dbg.kernel == DebugOpts::K_ITEM || h->wave_ok || h->lane_ok || !h->quad_built) return false;
-    if (!h->fast_ok || h->geo_kq[0] < 1 || h->geo_kq[1] < 1) return false;
+    if (h->dbg.kernel == DebugOpts::K_ITEM || !h->quad_built || h->geo_kq[0] < 1 || h->geo_kq[1] < 1) return false;
     // small deep graphs (numerators): measured on the reference's WSJ numerator graph (depth 165),
     // item kernel 2.3 ms against 2.7 ms; shallow graphs of the same size are 1.6x faster on the quad kernels
     if (h->max_depth >= 64 && h->geo_kq[0] <= 3 && h->geo_kq[1] <= 3 && h->dbg.kernel == DebugOpts::K_AUTO) return false;
@@ -487,14 +543,7 @@ static int launch_rows(mm_batch_t h, const RunParams &p, void *stream) {
 
 // The pair kernels live in a translation unit of their own (mm_pairs_tu.hip)
 static int launch_pairs(mm_batch_t h, const RunParams &p, void *stream) {
-    PairLaunch pl;
-    pl.B = h->B;
-    pl.nwc = h->pair_nwc;
-    pl.slotrows = h->pair_slotrows;
-    pl.max_P1 = h->max_P1;
-    pl.pair_ka = h->pair_ka;
-    pl.H = h->pair_H;
-    pl.small = h->pair_H == 1 && h->max_S1p <= 128;
+    const PairLaunch pl = pair_launch_of(h);
     return h->pair_H > 1 ? mm_launch_split(pl, p, static_cast<hipStream_t>(stream)) : mm_launch_pairs(pl, p, static_cast<hipStream_t>(stream));
 }
 
@@ -1880,6 +1929,199 @@ int mm_fsm_create_many(int64_t n, int semiring, int layout, int index_bytes, int
 // a batch of ProbSemiring FSMs answers for its settings and counters through the batch of its log twins (what runs its fast calls)
 static mm_batch_t twin_of(mm_batch_t h) { return h && h->log_twin ? h->log_twin : h; }
 
+// The wave forms of every FSM of the batch (packed on the host's cores for the FSMs that are new): *ok, h->wave_nseg.
+static int try_wave(mm_batch_t h, const mm_fsm_t *fsms, bool *ok) {
+    const int64_t B = h->B;
+    *ok = true;
+    {   // pack the forms of the FSMs that are new, on the host's cores
+        std::vector<mm_fsm_t> todo;
+        for (int64_t b = 0; b < B; ++b)
+            if (!fsms[b]->wrows[0] && !fsms[b]->wave_tried && !fsms[b]->wave_packed &&
+                std::find(todo.begin(), todo.end(), fsms[b]) == todo.end())
+                todo.push_back(fsms[b]);
+        const size_t nthr = std::min<size_t>({todo.size() / 4, size_t(std::max(1u, std::thread::hardware_concurrency())), size_t(16)});
+        if (nthr > 1) {
+            std::atomic<size_t> next{0};
+            std::vector<std::thread> pool;
+            for (size_t t = 0; t < nthr; ++t)
+                pool.emplace_back([&]() {
+                    // (an exception must not leave a thread: an FSM whose packing failed is packed again, and fails
+                    // again, on the calling thread -- wave_variants below)
+                    for (size_t i = next.fetch_add(1); i < todo.size(); i = next.fetch_add(1)) {
+                        try {
+                            wave_pack(todo[i]);
+                        } catch (...) {
+                            todo[i]->wave_packed = false;
+                        }
+                    }
+                });
+            for (std::thread &t : pool) t.join();
+        }
+    }
+    for (int64_t b = 0; b < B && *ok; ++b) {
+        bool fit = false;
+        int rc = wave_variants(fsms[b], h->dbg, &fit);
+        if (rc) return rc;
+        *ok = fit;
+        // (segments of a wave's registers: the state segments, and twice the pdf segments -- the kernel has NSEG / 2 of those)
+        if (fit)
+            h->wave_nseg = std::max({h->wave_nseg, std::max(fsms[b]->wrows[0]->g.KA, fsms[b]->wrows[1]->g.KA) / 4,
+                                     2 * std::max(fsms[b]->wrows[0]->pdf_nps, fsms[b]->wrows[1]->pdf_nps)});
+    }
+    return MM_OK;
+}
+
+// The kernel family of a log batch (h->fb), with the forms it needs packed, and what goes with it: h->lane_redo_wave, the wave,
+// pair and stream geometries, h->quad_built, h->quad_ok.  *rows: every FSM has its row-lane forms (a batch of the pair kernels
+// keeps them too).  Reads the quad geometry, h->xcsr and h->n_cus; nq_max, s1_max: the most quads per direction, states of one FSM.
+static int pick_family(mm_batch_t h, const mm_fsm_t *fsms, const int64_t nq_max[2], int64_t s1_max, bool *rows_out) {
+    const int64_t B = h->B;
+    const int kernel = h->dbg.kernel;
+    bool lane = false, wave = false, rows = false, pairs = false, stream = false, same = true;  // (same: one FSM shared by all utterances)
+    for (int64_t b = 1; b < B && same; ++b) same = fsms[b] == fsms[0];
+    // The wave kernel FIRST wherever every graph of the batch fits it (up to 1023 states, 16 segments of 64 lanes x 4 arcs
+    // per direction, 250 pdfs): one workgroup per utterance runs both directions at once in the log domain, without the
+    // marks and the exact second pass of the linear-domain kernels -- measured against the row kernels on batches of
+    // different graphs (1.18 -> 0.72 ms: 128 lexicon graphs of 150..400 states, T = 700) and against the pair kernels on one
+    // shared small graph (0.80 -> 0.47 ms: 300 states, B = 256, T = 500; 3-state HMM, B = 1, T = 100: 0.18 -> 0.06 ms).  The
+    // exception: one shared DENSE graph (more than 16 arcs per state, more than 2 segments per wave) on a batch of more than
+    // two utterances per compute unit, where the pair kernels' two utterances per workgroup win (32-state ergodic HMM,
+    // B = 1024: 1.90 against 2.33 ms).
+    // The lane kernel FIRST for batches of tiny graphs (every FSM: up to 64 states and 64 pdfs): one wave per utterance and
+    // direction with the graph in its registers, float64, exact -- BASELINE config 2 (dense 64-state HMM, B = 32, T = 500):
+    // 0.60 ms on the pair kernels; config 1 (3-state HMM, one utterance).
+    if (h->semiring == MM_LOG && (kernel == DebugOpts::K_AUTO || kernel == DebugOpts::K_LANE)) {
+        lane = true;
+        for (int64_t b = 0; b < B && lane; ++b) {
+            bool ok = false;
+            int rc = lane_variant(fsms[b], &ok);
+            if (rc) return rc;
+            lane = ok;
+            h->lane_S = std::max(h->lane_S, int(fsms[b]->S1 - 1));
+        }
+    }
+    // What the lane kernel marks (mass beyond the double's range: the one path of a sharp left-to-right graph) is computed again in the
+    // log domain: by the WAVE kernel when every graph has its wave forms (up to 4096 arc slots per direction; packed with the graph by
+    // mm_fsm_create_many, nothing to upload at the first call, capturable from the first call on), else -- a dense 64-state HMM has
+    // 4161 arcs -- by the item kernel, whose forms then go to the device here.
+    if (lane) {
+        int rc = try_wave(h, fsms, &h->lane_redo_wave);
+        if (rc) return rc;
+        if (!h->lane_redo_wave) h->wave_nseg = 0;
+    }
+    bool wave_first_tried = false;
+    if (h->semiring == MM_LOG && kernel == DebugOpts::K_AUTO && !lane) {
+        bool small = h->max_P1 <= 250;
+        for (int64_t b = 0; b < B && small; ++b)
+            small = fsms[b]->S1 <= 1023 && fsms[b]->qmat[0].rowptr[fsms[b]->S1] <= 16 * 64 * 4;
+        const bool dense_many = same && B > 2 * int64_t(h->n_cus) && fsms[0]->qmat[0].rowptr[fsms[0]->S1] > 16 * fsms[0]->S1;
+        if (small) {
+            wave_first_tried = true;
+            int rc = try_wave(h, fsms, &wave);
+            if (rc) return rc;
+            // (the exception; the forms stay with the FSM.  Graphs of up to 2 segments per wave run the kernel instance of
+            // which two workgroups fit a compute unit and win at every batch size: 16-state ergodic HMM, B = 1024: 1.18
+            // against 1.88 ms)
+            if (wave && dense_many && h->wave_nseg > 2) wave = false;
+        }
+    }
+    // row kernels: every FSM of the batch needs its row-lane forms.  Small deep (left-to-right) graphs keep states
+    // alive whose values differ by more than the float range within one frame, so most of their rows would take the
+    // exact fallback of the linear-domain kernels: they run on the item kernel (unless a kernel is forced).
+    const bool linear_first = !wave && !lane && h->fast_ok && kernel != DebugOpts::K_ITEM && kernel != DebugOpts::K_QUAD &&
+                              kernel != DebugOpts::K_WAVE && kernel != DebugOpts::K_STREAM &&
+                              !(h->max_depth >= 64 && nq_max[0] <= 3 * 1024 && nq_max[1] <= 3 * 1024 && kernel == DebugOpts::K_AUTO);
+    rows = linear_first;
+    for (int64_t b = 0; b < B && rows; ++b) {
+        bool ok = false;
+        int rc = row_variants(fsms[b], h->dbg.verbose, &ok);
+        if (rc) return rc;
+        rows = ok;
+    }
+    // pair kernels: all utterances on ONE FSM (the graph registers are shared by the two utterances of a workgroup)
+    // (a batch of ONE utterance too: its pair runs the utterance twice, the copy writes nothing outside the workspace -- both
+    // directions at once instead of the row kernels' two passes: 4.1 -> 2.6 ms on config 3's graph)
+    // (the row kernels take up to 250 pdfs, the pair kernels 506: a shared graph of more pdfs has no row forms)
+    pairs = linear_first && same && (rows || h->max_P1 > 250) && kernel != DebugOpts::K_ROW && kernel != DebugOpts::K_SPLIT;
+    if (pairs) {
+        bool ok = false;
+        int rc = pair_variants(fsms[0], h->dbg, &ok);
+        if (rc) return rc;
+        pairs = ok;
+        if (ok) {
+            h->pair_ka = std::max(fsms[0]->prows[0]->g.KA, fsms[0]->prows[1]->g.KA);
+            h->pair_nwc = std::max(fsms[0]->prows[0]->g.NWC, fsms[0]->prows[1]->g.NWC);
+            h->pair_slotrows = std::max(fsms[0]->prows[0]->g.nslotrows, fsms[0]->prows[1]->g.nslotrows);
+            pairs = h->pair_ka <= MM_PAIR_KA && mm_pair_lds_bytes(1, h->pair_slotrows, h->max_P1) <= 160 * 1024;
+        }
+    }
+    // split pair kernels: one shared FSM that is too large for the pair kernels proper (more arcs than the registers of a
+    // compute unit hold, more states than half its LDS) -- teams of 2 workgroups per utterance pair and direction
+    if (linear_first && same && !pairs && kernel != DebugOpts::K_ROW) {
+        bool ok = false;
+        int rc = split_variants(fsms[0], h->dbg, 2, &ok);
+        // (a graph beyond the teams of 2 -- more than 3070 states or 2 x 14 x 64 x 36 arcs: teams of 4; beyond those -- more
+        // than 4094 states: teams of 8, up to 6014 states and 314 pdfs)
+        if (!rc && !ok) rc = split_variants(fsms[0], h->dbg, 4, &ok);
+        if (!rc && !ok) rc = split_variants(fsms[0], h->dbg, 8, &ok);
+        if (rc) return rc;
+        if (ok) {
+            const mm_fsm_t f0 = fsms[0];
+            h->pair_H = f0->split.H;
+            h->pair_ka = 0;
+            h->pair_nwc = 1;
+            h->pair_slotrows = 0;
+            for (int d = 0; d < 2; ++d)
+                for (int s = 0; s < h->pair_H; ++s) {
+                    h->pair_ka = std::max(h->pair_ka, f0->srows[d][s]->g.KA);
+                    h->pair_nwc = std::max(h->pair_nwc, f0->srows[d][s]->g.NWC);
+                    h->pair_slotrows = std::max(h->pair_slotrows, f0->srows[d][s]->g.nslotrows);
+                }
+            h->split_s1p = (f0->split.total + 2 + 3) & ~3;
+            const size_t lds = mm_split_lds_bytes(h->pair_H, 1, h->pair_slotrows, h->max_P1);
+            pairs = h->pair_ka <= mm_split_ka(h->pair_H) && h->pair_nwc <= MM_SPLIT_NWC && lds > 0 && lds <= 160 * 1024;
+            if (h->dbg.verbose) fprintf(stderr, "[mm] teams of %d: LDS %zu bytes in phase B\n", h->pair_H, lds);
+            if (!pairs) h->pair_H = 1;
+        }
+    }
+    // wave kernel, the other case: small graphs that none of the linear-domain kernels takes (deep left-to-right graphs:
+    // numerators), or the kernel is asked for by name
+    if (h->semiring == MM_LOG && !wave && !lane && !wave_first_tried && !rows && !pairs &&
+        (kernel == DebugOpts::K_WAVE ||
+         (kernel == DebugOpts::K_AUTO && (!h->fast_ok || (h->max_depth >= 64 && h->geo_kq[0] <= 3 && h->geo_kq[1] <= 3))))) {
+        // (= where the item kernel would run: quad_kernel_usable() says no for these; see there)
+        int rc = try_wave(h, fsms, &wave);
+        if (rc) return rc;
+    }
+    // stream kernels (mm_stream.hip): graphs beyond every register-resident form and beyond the quad kernels' LDS (more than ~3000
+    // states, more than 250 pdfs on different graphs / 506 on a shared one, weights outside the float range) -- what the item
+    // kernel ran until round 5
+    const bool beyond = s1_max > 3000 || h->max_P1 > 250 || !h->fast_ok;
+    if (h->semiring == MM_LOG && !lane && !wave && !pairs && !rows &&
+        (kernel == DebugOpts::K_STREAM || (kernel == DebugOpts::K_AUTO && beyond))) {
+        stream = true;
+        // teams of 2 or 4 workgroups per utterance and direction when the batch leaves compute units idle (round 6: a direction's
+        // record stream through ONE compute unit's memory path is what bounds a frame)
+        h->stream_H = (h->dbg.stream_h == 1 || h->dbg.stream_h == 2 || h->dbg.stream_h == 4) ? h->dbg.stream_h : mm_stream_pick_h(B, h->n_cus);
+        for (int64_t b = 0; b < B && stream; ++b) {
+            bool ok = false;
+            int rc = stream_variant(fsms[b], h->stream_H, &ok);
+            if (rc) return rc;
+            stream = ok && mm_stream_dev(fsms[b]->stream_h[stream_hidx(h->stream_H)]) != nullptr;
+        }
+        h->stream_S1 = int(s1_max);
+    }
+    // (a batch of the wave kernel never runs the quad kernels, and one whose marked utterances go to the float64 pair kernels
+    // has the item kernel behind those: their quad forms are not built)
+    const bool want_dpair = pairs && !h->dbg.no_dpair;
+    h->quad_built = h->fast_ok && !wave && !lane && !stream && !(want_dpair && kernel != DebugOpts::K_QUAD);
+    h->quad_ok = quad_kernel_usable(h);
+    h->fb = lane ? Fb::Lane : stream ? Fb::Stream : wave ? Fb::Wave : pairs ? (h->pair_H > 1 ? Fb::Split : Fb::Pairs) : rows ? Fb::Rows
+          : h->quad_ok ? Fb::Quad : Fb::Item;
+    *rows_out = rows;
+    return MM_OK;
+}
+
 static int batch_create_impl(const mm_fsm_t *fsms, int64_t B, mm_batch_t *out) {
     if (!out) return fail(MM_ERR_INVALID, "mm_batch_create: out is NULL");
     *out = nullptr;
@@ -1917,23 +2159,27 @@ static int batch_create_impl(const mm_fsm_t *fsms, int64_t B, mm_batch_t *out) {
         *out = hold.release();
         return MM_OK;
     }
-    for (int64_t b = 0; b < B; ++b) h->max_P1 = std::max(h->max_P1, int(fsms[b]->P1));  // (the choice of kernels below reads it)
-    std::vector<UttDesc> utts(B);
-    // quad kernels: one geometry (quads per lane, waves) per direction for the whole batch
-    int64_t nq_max[2] = {0, 0};
+    {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) h->n_cus = cus;
+    }
+    // (the choice of kernels below reads them)
+    int64_t nq_max[2] = {0, 0}, s1_max = 0;
     for (int64_t b = 0; b < B; ++b) {
+        h->max_P1 = std::max(h->max_P1, int(fsms[b]->P1));
+        h->max_S1p = std::max(h->max_S1p, fsms[b]->S1p);
+        s1_max = std::max(s1_max, fsms[b]->S1);
         h->fast_ok = h->fast_ok && fsms[b]->fast_ok;
         for (int d = 0; d < 2; ++d) nq_max[d] = std::max(nq_max[d], fsms[b]->nquads[d]);
         h->max_depth = std::max(h->max_depth, fsms[b]->depth);
     }
+    // quad kernels: one geometry (quads per lane, waves) per direction for the whole batch
     h->fast_ok = h->fast_ok && h->semiring == MM_LOG;
     if (h->fast_ok) {
         for (int d = 0; d < 2; ++d) {
             QuadGeometry geo = pick_quad_geometry(nq_max[d]);
             if (h->dbg.kq >= 1 && h->dbg.kq <= 29) geo.KQ = h->dbg.kq;
             // enough waves for the quads, and for at most two rows per thread where the workgroup can be that large
-            int64_t s1_max = 0;
-            for (int64_t b = 0; b < B; ++b) s1_max = std::max(s1_max, fsms[b]->S1);
             geo.NW = int(std::min<int64_t>(geo.KQ > 13 ? 8 : MM_MAX_WAVES,
                                            std::max<int64_t>({1, (nq_max[d] + 64 * geo.KQ - 1) / (64 * geo.KQ),
                                                               (s1_max + 127) / 128})));
@@ -1947,167 +2193,20 @@ static int batch_create_impl(const mm_fsm_t *fsms, int64_t B, mm_batch_t *out) {
         for (int64_t b = 0; b < B; ++b)
             h->max_xcsr = std::max<int64_t>(h->max_xcsr, fsms[b]->S1 + 1 + 2 * std::max(fsms[b]->qmat[0].rowptr[fsms[b]->S1],
                                                                                   fsms[b]->qmat[1].rowptr[fsms[b]->S1]));
-    }
-    // The wave forms of every FSM of the batch (packed on the host's cores for the FSMs that are new): h->wave_ok, h->wave_nseg.
-    auto try_wave = [&]() -> int {
-        h->wave_ok = true;
-        {   // pack the forms of the FSMs that are new, on the host's cores
-            std::vector<mm_fsm_t> todo;
-            for (int64_t b = 0; b < B; ++b)
-                if (!fsms[b]->wrows[0] && !fsms[b]->wave_tried && !fsms[b]->wave_packed &&
-                    std::find(todo.begin(), todo.end(), fsms[b]) == todo.end())
-                    todo.push_back(fsms[b]);
-            const size_t nthr = std::min<size_t>({todo.size() / 4, size_t(std::max(1u, std::thread::hardware_concurrency())), size_t(16)});
-            if (nthr > 1) {
-                std::atomic<size_t> next{0};
-                std::vector<std::thread> pool;
-                for (size_t t = 0; t < nthr; ++t)
-                    pool.emplace_back([&]() {
-                        // (an exception must not leave a thread: an FSM whose packing failed is packed again, and fails
-                        // again, on the calling thread -- wave_variants below)
-                        for (size_t i = next.fetch_add(1); i < todo.size(); i = next.fetch_add(1)) {
-                            try {
-                                wave_pack(todo[i]);
-                            } catch (...) {
-                                todo[i]->wave_packed = false;
-                            }
-                        }
-                    });
-                for (std::thread &t : pool) t.join();
-            }
-        }
-        for (int64_t b = 0; b < B && h->wave_ok; ++b) {
-            bool ok = false;
-            int rc = wave_variants(fsms[b], h->dbg, &ok);
-            if (rc) return rc;
-            h->wave_ok = ok;
-            // (segments of a wave's registers: the state segments, and twice the pdf segments -- the kernel has NSEG / 2 of those)
-            if (ok)
-                h->wave_nseg = std::max({h->wave_nseg, std::max(fsms[b]->wrows[0]->g.KA, fsms[b]->wrows[1]->g.KA) / 4,
-                                         2 * std::max(fsms[b]->wrows[0]->pdf_nps, fsms[b]->wrows[1]->pdf_nps)});
-        }
-        return MM_OK;
-    };
-    // The wave kernel FIRST wherever every graph of the batch fits it (up to 1023 states, 16 segments of 64 lanes x 4 arcs
-    // per direction, 250 pdfs): one workgroup per utterance runs both directions at once in the log domain, without the
-    // marks and the exact second pass of the linear-domain kernels -- measured against the row kernels on batches of
-    // different graphs (1.18 -> 0.72 ms: 128 lexicon graphs of 150..400 states, T = 700) and against the pair kernels on one
-    // shared small graph (0.80 -> 0.47 ms: 300 states, B = 256, T = 500; 3-state HMM, B = 1, T = 100: 0.18 -> 0.06 ms).  The
-    // exception: one shared DENSE graph (more than 16 arcs per state, more than 2 segments per wave) on a batch of more than
-    // two utterances per compute unit, where the pair kernels' two utterances per workgroup win (32-state ergodic HMM,
-    // B = 1024: 1.90 against 2.33 ms).
-    // The lane kernel FIRST for batches of tiny graphs (every FSM: up to 64 states and 64 pdfs): one wave per utterance and
-    // direction with the graph in its registers, float64, exact -- BASELINE config 2 (dense 64-state HMM, B = 32, T = 500):
-    // 0.60 ms on the pair kernels; config 1 (3-state HMM, one utterance).
-    if (h->semiring == MM_LOG && (h->dbg.kernel == DebugOpts::K_AUTO || h->dbg.kernel == DebugOpts::K_LANE)) {
-        h->lane_ok = true;
-        for (int64_t b = 0; b < B && h->lane_ok; ++b) {
-            bool ok = false;
-            int rc = lane_variant(fsms[b], &ok);
-            if (rc) return rc;
-            h->lane_ok = ok;
-            h->lane_S = std::max(h->lane_S, int(fsms[b]->S1 - 1));
+        if (h->geo_kq[0] <= 3 && h->geo_kq[1] <= 3 && !h->dbg.no_xcsr) {
+            h->xcsr = int((h->max_xcsr + 3) & ~int64_t(3));
+            if (h->max_xcsr > 16 * 1024 || quad_lds_bytes(h, 0) > 128 * 1024 || quad_lds_bytes(h, 1) > 128 * 1024) h->xcsr = 0;
         }
     }
-    // What the lane kernel marks (mass beyond the double's range: the one path of a sharp left-to-right graph) is computed again in the
-    // log domain: by the WAVE kernel when every graph has its wave forms (up to 4096 arc slots per direction; packed with the graph by
-    // mm_fsm_create_many, nothing to upload at the first call, capturable from the first call on), else -- a dense 64-state HMM has
-    // 4161 arcs -- by the item kernel, whose forms then go to the device here.
-    if (h->lane_ok) {
-        int rc = try_wave();
-        if (rc) return rc;
-        h->lane_redo_wave = h->wave_ok;
-        h->wave_ok = false;
-        if (!h->lane_redo_wave) h->wave_nseg = 0;
-    }
-    bool wave_first_tried = false;
-    if (h->semiring == MM_LOG && h->dbg.kernel == DebugOpts::K_AUTO && !h->lane_ok) {
-        bool small = h->max_P1 <= 250, same = true;
-        for (int64_t b = 0; b < B && small; ++b)
-            small = fsms[b]->S1 <= 1023 && fsms[b]->qmat[0].rowptr[fsms[b]->S1] <= 16 * 64 * 4;
-        for (int64_t b = 1; b < B && same; ++b) same = fsms[b] == fsms[0];
-        const bool dense_many = same && B > 2 * int64_t(h->n_cus) && fsms[0]->qmat[0].rowptr[fsms[0]->S1] > 16 * fsms[0]->S1;
-        if (small) {
-            wave_first_tried = true;
-            int rc = try_wave();
-            if (rc) return rc;
-            // (the exception; the forms stay with the FSM.  Graphs of up to 2 segments per wave run the kernel instance of
-            // which two workgroups fit a compute unit and win at every batch size: 16-state ergodic HMM, B = 1024: 1.18
-            // against 1.88 ms)
-            if (h->wave_ok && dense_many && h->wave_nseg > 2) h->wave_ok = false;
-        }
-    }
-    // row kernels: every FSM of the batch needs its row-lane forms.  Small deep (left-to-right) graphs keep states
-    // alive whose values differ by more than the float range within one frame, so most of their rows would take the
-    // exact fallback of the linear-domain kernels: they run on the item kernel (unless a kernel is forced).
-    const bool linear_first = !h->wave_ok && !h->lane_ok && h->fast_ok && h->dbg.kernel != DebugOpts::K_ITEM && h->dbg.kernel != DebugOpts::K_QUAD &&
-                              h->dbg.kernel != DebugOpts::K_WAVE && h->dbg.kernel != DebugOpts::K_STREAM &&
-                              !(h->max_depth >= 64 && nq_max[0] <= 3 * 1024 && nq_max[1] <= 3 * 1024 && h->dbg.kernel == DebugOpts::K_AUTO);
-    h->rows_ok = linear_first;
-    for (int64_t b = 0; b < B && h->rows_ok; ++b) {
-        bool ok = false;
-        int rc = row_variants(fsms[b], h->dbg.verbose, &ok);
-        if (rc) return rc;
-        h->rows_ok = ok;
-    }
-    // pair kernels: all utterances on ONE FSM (the graph registers are shared by the two utterances of a workgroup)
-    // (a batch of ONE utterance too: its pair runs the utterance twice, the copy writes nothing outside the workspace -- both
-    // directions at once instead of the row kernels' two passes: 4.1 -> 2.6 ms on config 3's graph)
-    // (the row kernels take up to 250 pdfs, the pair kernels 506: a shared graph of more pdfs has no row forms)
-    h->pairs_ok = linear_first && (h->rows_ok || h->max_P1 > 250) && h->dbg.kernel != DebugOpts::K_ROW && h->dbg.kernel != DebugOpts::K_SPLIT;
-    for (int64_t b = 1; b < B && h->pairs_ok; ++b) h->pairs_ok = fsms[b] == fsms[0];
-    if (h->pairs_ok) {
-        bool ok = false;
-        int rc = pair_variants(fsms[0], h->dbg, &ok);
-        if (rc) return rc;
-        h->pairs_ok = ok;
-        if (ok) {
-            h->pair_ka = std::max(fsms[0]->prows[0]->g.KA, fsms[0]->prows[1]->g.KA);
-            h->pair_nwc = std::max(fsms[0]->prows[0]->g.NWC, fsms[0]->prows[1]->g.NWC);
-            h->pair_slotrows = std::max(fsms[0]->prows[0]->g.nslotrows, fsms[0]->prows[1]->g.nslotrows);
-            h->pairs_ok = h->pair_ka <= MM_PAIR_KA && mm_pair_lds_bytes(1, h->pair_slotrows, h->max_P1) <= 160 * 1024;
-        }
-    }
-    // split pair kernels: one shared FSM that is too large for the pair kernels proper (more arcs than the registers of a
-    // compute unit hold, more states than half its LDS) -- teams of 2 workgroups per utterance pair and direction
-    if (!h->wave_ok && !h->lane_ok && !h->pairs_ok && h->fast_ok && h->dbg.kernel != DebugOpts::K_ITEM && h->dbg.kernel != DebugOpts::K_QUAD &&
-        h->dbg.kernel != DebugOpts::K_ROW && h->dbg.kernel != DebugOpts::K_WAVE && h->dbg.kernel != DebugOpts::K_STREAM &&
-        !(h->max_depth >= 64 && nq_max[0] <= 3 * 1024 && nq_max[1] <= 3 * 1024 && h->dbg.kernel == DebugOpts::K_AUTO)) {
-        bool same = true;
-        for (int64_t b = 1; b < B && same; ++b) same = fsms[b] == fsms[0];
-        if (same) {
-            bool ok = false;
-            int rc = split_variants(fsms[0], h->dbg, 2, &ok);
-            // (a graph beyond the teams of 2 -- more than 3070 states or 2 x 14 x 64 x 36 arcs: teams of 4; beyond those -- more
-            // than 4094 states: teams of 8, up to 6014 states and 314 pdfs)
-            if (!rc && !ok) rc = split_variants(fsms[0], h->dbg, 4, &ok);
-            if (!rc && !ok) rc = split_variants(fsms[0], h->dbg, 8, &ok);
-            if (rc) return rc;
-            if (ok) {
-                const mm_fsm_t f0 = fsms[0];
-                h->pair_H = f0->split.H;
-                h->pair_ka = 0;
-                h->pair_nwc = 1;
-                h->pair_slotrows = 0;
-                for (int d = 0; d < 2; ++d)
-                    for (int s = 0; s < h->pair_H; ++s) {
-                        h->pair_ka = std::max(h->pair_ka, f0->srows[d][s]->g.KA);
-                        h->pair_nwc = std::max(h->pair_nwc, f0->srows[d][s]->g.NWC);
-                        h->pair_slotrows = std::max(h->pair_slotrows, f0->srows[d][s]->g.nslotrows);
-                    }
-                h->split_s1p = (f0->split.total + 2 + 3) & ~3;
-                const size_t lds = mm_split_lds_bytes(h->pair_H, 1, h->pair_slotrows, h->max_P1);
-                h->pairs_ok = h->pair_ka <= mm_split_ka(h->pair_H) && h->pair_nwc <= MM_SPLIT_NWC && lds > 0 && lds <= 160 * 1024;
-                if (h->dbg.verbose) fprintf(stderr, "[mm] teams of %d: LDS %zu bytes in phase B\n", h->pair_H, lds);
-                if (!h->pairs_ok) h->pair_H = 1;
-            }
-        }
-    }
+    bool rows = false;
+    int rc = pick_family(h, fsms, nq_max, s1_max, &rows);
+    if (rc) return rc;
+    std::vector<UttDesc> utts(B);
     if (h->semiring == MM_TROPICAL && h->dbg.kernel != DebugOpts::K_ITEM) {
         h->vit_ok = true;
         for (int64_t b = 0; b < B && h->vit_ok; ++b) {
             bool ok = false;
-            int rc = vit_variant(fsms[b], h->dbg, &ok);
+            rc = vit_variant(fsms[b], h->dbg, &ok);
             if (rc) return rc;
             h->vit_ok = ok;
             if (ok) {  // (one layout per batch: the first FSM's; an FSM that needed another one keeps the batch on the item kernel)
@@ -2121,52 +2220,13 @@ static int batch_create_impl(const mm_fsm_t *fsms, int64_t B, mm_batch_t *out) {
             }
         }
     }
-    // wave kernel, the other case: small graphs that none of the linear-domain kernels takes (deep left-to-right graphs:
-    // numerators), or the kernel is asked for by name
-    if (h->semiring == MM_LOG && !h->wave_ok && !h->lane_ok && !wave_first_tried && !h->rows_ok && !h->pairs_ok &&
-        (h->dbg.kernel == DebugOpts::K_WAVE ||
-         (h->dbg.kernel == DebugOpts::K_AUTO && (!h->fast_ok || (h->max_depth >= 64 && h->geo_kq[0] <= 3 && h->geo_kq[1] <= 3))))) {
-        // (= where the item kernel would run: quad_kernel_usable() says no for these; see there)
-        int rc = try_wave();
-        if (rc) return rc;
-    }
-    // (a batch of the wave kernel never runs the quad kernels, and one whose marked utterances go to the float64 pair kernels
-    // has the item kernel behind those: their quad forms are not built)
-    // stream kernels (mm_stream.hip): graphs beyond every register-resident form and beyond the quad kernels' LDS (more than ~3000
-    // states, more than 250 pdfs on different graphs / 506 on a shared one, weights outside the float range) -- what the item
-    // kernel ran until round 5
-    {
-        int64_t s1_max = 0;
-        for (int64_t b = 0; b < B; ++b) s1_max = std::max(s1_max, fsms[b]->S1);
-        const bool beyond = s1_max > 3000 || h->max_P1 > 250 || !h->fast_ok;
-        if (h->semiring == MM_LOG && !h->lane_ok && !h->wave_ok && !h->pairs_ok && !h->rows_ok &&
-            (h->dbg.kernel == DebugOpts::K_STREAM || (h->dbg.kernel == DebugOpts::K_AUTO && beyond))) {
-            h->stream_ok = true;
-            // teams of 2 or 4 workgroups per utterance and direction when the batch leaves compute units idle (round 6: a direction's
-            // record stream through ONE compute unit's memory path is what bounds a frame)
-            {
-                int dev = 0, cus = 0;
-                if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) h->n_cus = cus;
-            }
-            h->stream_H = (h->dbg.stream_h == 1 || h->dbg.stream_h == 2 || h->dbg.stream_h == 4) ? h->dbg.stream_h : mm_stream_pick_h(B, h->n_cus);
-            for (int64_t b = 0; b < B && h->stream_ok; ++b) {
-                bool ok = false;
-                int rc = stream_variant(fsms[b], h->stream_H, &ok);
-                if (rc) return rc;
-                h->stream_ok = ok && mm_stream_dev(fsms[b]->stream_h[stream_hidx(h->stream_H)]) != nullptr;
-            }
-            h->stream_S1 = int(s1_max);
-        }
-    }
-    const bool want_dpair = h->pairs_ok && !h->dbg.no_dpair;
-    h->quad_built = h->fast_ok && !h->wave_ok && !h->lane_ok && !h->stream_ok && !(want_dpair && h->dbg.kernel != DebugOpts::K_QUAD);
     // (the item forms -- the general fallback, the alpha / beta export, the total-sum family -- of a batch of the wave kernel go to
     // the device when an entry first needs them, ensure_item_forms(): a batch of new numerator graphs every training step
     // never does)
-    h->items_resident = !h->wave_ok && !(h->lane_ok && h->lane_redo_wave);
+    h->items_resident = h->fb != Fb::Wave && !h->lane_redo_wave;
     for (int64_t b = 0; b < B; ++b) {
         mm_fsm_t f = fsms[b];
-        int rc = h->items_resident ? fsm_to_device(f) : MM_OK;
+        rc = h->items_resident ? fsm_to_device(f) : MM_OK;
         QuadVariant *qv[2] = {nullptr, nullptr};
         for (int d = 0; d < 2 && !rc && h->quad_built; ++d) rc = quad_variant(f, d, h->geo_kq[d], h->dbg.verbose, &qv[d]);
         if (rc) return rc;
@@ -2180,17 +2240,17 @@ static int batch_create_impl(const mm_fsm_t *fsms, int64_t B, mm_batch_t *out) {
             u.init_f = qv[0]->d_init_f;
             u.map_bf = qv[1]->d_map_bf;
         }
-        if (h->lane_ok) u.lane = static_cast<const LaneDev *>(f->lane_blob);
-        if (h->stream_ok) u.stream = mm_stream_dev(f->stream_h[stream_hidx(h->stream_H)]);
+        if (h->fb == Fb::Lane) u.lane = static_cast<const LaneDev *>(f->lane_blob);
+        if (h->fb == Fb::Stream) u.stream = mm_stream_dev(f->stream_h[stream_hidx(h->stream_H)]);
         if (h->vit_ok) u.rv = f->vrow->rdev;
-        if (h->wave_ok || h->lane_redo_wave)
+        if (h->fb == Fb::Wave || h->lane_redo_wave)
             for (int d = 0; d < 2; ++d) u.rw[d] = f->wrows[d]->rdev;
-        if (h->pairs_ok && h->pair_H == 1)
+        if (h->fb == Fb::Pairs)
             for (int d = 0; d < 2; ++d) u.rp[d] = f->prows[d]->rdev;
-        if (h->pairs_ok && h->pair_H > 1)
+        if (h->fb == Fb::Split)
             for (int d = 0; d < 2; ++d)
                 for (int s = 0; s < h->pair_H; ++s) u.rps[d][s] = f->srows[d][s]->rdev;
-        if (h->rows_ok)
+        if (rows)
             for (int d = 0; d < 2; ++d) {
                 u.r[d] = f->rows[d]->rdev;
                 h->row_ka[d] = std::max(h->row_ka[d], f->rows[d]->g.KA);
@@ -2209,15 +2269,7 @@ static int batch_create_impl(const mm_fsm_t *fsms, int64_t B, mm_batch_t *out) {
         u.s1p_prefix = h->total_s1p;
         h->total_states += f->S1;
         h->total_s1p += f->S1p;
-        h->max_S1p = std::max(h->max_S1p, f->S1p);
-        h->max_P1 = std::max(h->max_P1, int(f->P1));
         if (h->items_resident) h->max_items = std::max(h->max_items, int(std::max(f->packed[0].items.size(), f->packed[1].items.size())));
-    }
-    {
-        int dev = 0, cus = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
-            h->n_cus = cus;
     }
     if (hipGetDevice(&h->device) != hipSuccess || hipMalloc(&h->d_utts, sizeof(UttDesc) * B) != hipSuccess ||
         hipMemcpy(h->d_utts, utts.data(), sizeof(UttDesc) * B, hipMemcpyHostToDevice) != hipSuccess) {
@@ -2233,7 +2285,7 @@ static int batch_create_impl(const mm_fsm_t *fsms, int64_t B, mm_batch_t *out) {
             }
         }
     }
-    if (want_dpair) {
+    if (on_pairs(h) && !h->dbg.no_dpair) {
         void *hp = nullptr;
         if (hipMalloc(&h->stat_dev, 4 * sizeof(int)) == hipSuccess && hipMemset(h->stat_dev, 0, 4 * sizeof(int)) == hipSuccess &&
             hipHostMalloc(&hp, 4 * sizeof(int), hipHostMallocMapped) == hipSuccess) {
@@ -2241,21 +2293,8 @@ static int batch_create_impl(const mm_fsm_t *fsms, int64_t B, mm_batch_t *out) {
             for (int k = 0; k < 4; ++k) h->stat_host[k] = 0;  // ([2], [3]: utterances the last alpha / beta export handed to the item kernel)
             h->dpair_ok = true;
             h->exact_first = h->dbg.exact_first;
-            {
-                PairLaunch pl;
-                pl.B = h->B;
-                pl.nwc = h->pair_nwc;
-                pl.slotrows = h->pair_slotrows;
-                pl.max_P1 = h->max_P1;
-                pl.pair_ka = h->pair_ka;
-                pl.H = h->pair_H;
-                h->wpair_ok = !h->dbg.no_wpair && mm_wpair_fits(pl);
-            }
+            h->wpair_ok = !h->dbg.no_wpair && mm_wpair_fits(pair_launch_of(h));
         }
-    }
-    if (h->fast_ok && h->geo_kq[0] <= 3 && h->geo_kq[1] <= 3 && !h->dbg.no_xcsr) {
-        h->xcsr = int((h->max_xcsr + 3) & ~int64_t(3));
-        if (h->max_xcsr > 16 * 1024 || quad_lds_bytes(h, 0) > 128 * 1024 || quad_lds_bytes(h, 1) > 128 * 1024) h->xcsr = 0;
     }
     if (h->dbg.verbose)
         fprintf(stderr, "[mm] batch of %lld created in %.1f ms\n", (long long)B, 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - tb0).count());
@@ -2342,7 +2381,7 @@ int mm_batch_set_gamma_mode(mm_batch_t h, int accumulate, float scale) {
     const bool plain = !accumulate && scale == 1.f;
     // (every other kernel family may compute an utterance TWICE -- the linear-domain kernels first, the exact ones for what they
     // mark -- and the second result must replace the first, not add to it)
-    if (!plain && !h->wave_ok)
+    if (!plain && h->fb != Fb::Wave)
         return fail(MM_ERR_UNSUPPORTED, "mm_batch_set_gamma_mode: only batches of the wave kernel (every graph <= 1023 states, <= 4096 arc slots per direction: "
                                         "LF-MMI numerators) scale or accumulate their posteriors");
     h->g_acc = accumulate != 0;
@@ -2427,6 +2466,63 @@ int mm_batch_team_xcd_stats(mm_batch_t h, int out[2]) {
     });
 }
 
+// (mm_batch_kernels, entry 0) what mm_pdfposteriors_f32 launches on a log batch
+static std::string fb_kernels(mm_batch_t h) {
+    const std::string exact = h->quad_ok ? "mm_fbq_kernel<" + std::to_string(h->geo_kq[0]) + ",*,0> + mm_fbq_kernel<" +
+                                               std::to_string(h->geo_kq[1]) + ",*,1>"
+                                         : std::string("mm_log_kernel<MODE_FB> (forward, backward)");
+    switch (h->fb) {
+    case Fb::Lane:
+        return "mm_lane_kernel<" + std::to_string(h->lane_S <= 8 ? 8 : h->lane_S <= 16 ? 16 : h->lane_S <= 32 ? 32 : 64) +
+            "> (one wave per utterance and direction, the graph in its registers, float64)";
+    case Fb::Wave:
+        return "mm_wave_kernel<" + std::to_string(h->wave_nseg <= 2 ? 2 : 4) + "," + std::to_string(h->max_P1 <= 128 ? 2 : 4) +
+            (h->wave_nseg <= 2 && h->B > h->n_cus ? ",two per CU>" : ">");
+    case Fb::Stream:
+        return "mm_stream_kernel (forward and backward recursions as workgroups of one grid" +
+            (h->stream_H > 1 ? ", teams of " + std::to_string(h->stream_H) + " workgroups per utterance and direction" : std::string()) +
+            "; arcs streamed from L2, the vector in LDS as wide-exponent "
+            "32-bit values), mm_stream_combine_kernel, mm_stream_finish_kernel, then for marked utterances only " + exact;
+    case Fb::Split: {
+        const std::string k = std::to_string(mm_pair_nj(h->max_P1, h->pair_H)), H = std::to_string(h->pair_H);
+        return "mm_fbs_kernel<" + k + ",A," + H + ">, then <" + k + ",B," + H + "> (forward and backward agents in one grid, teams of " + H +
+            " workgroups), mm_pair_finish_kernel, then for marked utterances only " +
+            (h->dpair_ok ? "mm_fbds_kernel<" + k + ",A," + H + ">, then <" + k + ",B," + H + "> (float64, one utterance per team" +
+                               (h->wpair_ok ? std::string("); FIRST and alone while the inputs are hard: mm_fbws_kernel<") + k + ",A," + H + ">, then <" + k +
+                                                  ",B," + H + "> (wide-exponent pairs, two utterances per team)"
+                                            : std::string("; FIRST and alone while the inputs are hard)")) +
+                               ", mm_dpair_finish_kernel, then for what those mark "
+                         : std::string()) +
+            exact;
+    }
+    case Fb::Pairs: {
+        const std::string k = std::to_string(mm_pair_nj(h->max_P1));
+        return "mm_fbp_kernel<" + k + ",A>, then <" + k + ",B> (forward and backward agents in one grid), mm_pair_finish_kernel, then for marked "
+            "utterances only " +
+            (h->dpair_ok ? "mm_fbd_kernel<" + k + ",A>, then <" + k + ",B> (float64, one utterance per workgroup" +
+                               (h->wpair_ok ? std::string("); FIRST and alone while the inputs are hard: mm_fbw_kernel<") + k + ",A>, then <" + k +
+                                                  ",B> (wide-exponent pairs, two utterances per workgroup)"
+                                            : std::string("; FIRST and alone while the inputs are hard)")) +
+                               ", mm_dpair_finish_kernel, then for what those mark "
+                         : std::string()) +
+            exact;
+    }
+    case Fb::Rows: {
+        auto ka = [&](int d) {
+            for (int k : kRowKA)
+                if (h->row_ka[d] <= k) return k;
+            return 0;
+        };
+        return "mm_fbr_kernel<" + std::to_string(ka(0)) + ",8192,0> + mm_fbr_kernel<" + std::to_string(ka(1)) +
+            ",8192,1>, then for marked utterances only " + exact;
+    }
+    case Fb::Quad:
+    case Fb::Item:
+        break;
+    }
+    return exact;
+}
+
 static bool export_on_pairs(mm_batch_t h, int dir);
 int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
     if (!h || !buf || n < 2) return fail(MM_ERR_INVALID, "mm_batch_kernels: bad argument");
@@ -2435,54 +2531,7 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
         return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: this ProbSemiring batch has no log twins (Float64 FSMs, or negative weights): mm_pdfposteriors_ex only");
     std::string s;
     if (entry == 0) {  // mm_pdfposteriors_f32
-        const bool quad = quad_kernel_usable(h);
-        const std::string exact = quad ? "mm_fbq_kernel<" + std::to_string(h->geo_kq[0]) + ",*,0> + mm_fbq_kernel<" +
-                                             std::to_string(h->geo_kq[1]) + ",*,1>"
-                                       : std::string("mm_log_kernel<MODE_FB> (forward, backward)");
-        if (h->lane_ok) {
-            s = "mm_lane_kernel<" + std::to_string(h->lane_S <= 8 ? 8 : h->lane_S <= 16 ? 16 : h->lane_S <= 32 ? 32 : 64) +
-                "> (one wave per utterance and direction, the graph in its registers, float64)";
-        } else if (h->wave_ok) {
-            s = "mm_wave_kernel<" + std::to_string(h->wave_nseg <= 2 ? 2 : 4) + "," + std::to_string(h->max_P1 <= 128 ? 2 : 4) +
-                (h->wave_nseg <= 2 && h->B > h->n_cus ? ",two per CU>" : ">");
-        } else if (h->stream_ok) {
-            s = "mm_stream_kernel (forward and backward recursions as workgroups of one grid" +
-                (h->stream_H > 1 ? ", teams of " + std::to_string(h->stream_H) + " workgroups per utterance and direction" : std::string()) +
-                "; arcs streamed from L2, the vector in LDS as wide-exponent "
-                "32-bit values), mm_stream_combine_kernel, mm_stream_finish_kernel, then for marked utterances only " + exact;
-        } else if (h->pairs_ok && h->pair_H > 1) {
-            const std::string k = std::to_string(mm_pair_nj(h->max_P1, h->pair_H)), H = std::to_string(h->pair_H);
-            s = "mm_fbs_kernel<" + k + ",A," + H + ">, then <" + k + ",B," + H + "> (forward and backward agents in one grid, teams of " + H +
-                " workgroups), mm_pair_finish_kernel, then for marked utterances only " +
-                (h->dpair_ok ? "mm_fbds_kernel<" + k + ",A," + H + ">, then <" + k + ",B," + H + "> (float64, one utterance per team" +
-                                   (h->wpair_ok ? std::string("); FIRST and alone while the inputs are hard: mm_fbws_kernel<") + k + ",A," + H + ">, then <" + k +
-                                                      ",B," + H + "> (wide-exponent pairs, two utterances per team)"
-                                                : std::string("; FIRST and alone while the inputs are hard)")) +
-                                   ", mm_dpair_finish_kernel, then for what those mark "
-                             : std::string()) +
-                exact;
-        } else if (h->pairs_ok) {
-            const std::string k = std::to_string(mm_pair_nj(h->max_P1));
-            s = "mm_fbp_kernel<" + k + ",A>, then <" + k + ",B> (forward and backward agents in one grid), mm_pair_finish_kernel, then for marked "
-                "utterances only " +
-                (h->dpair_ok ? "mm_fbd_kernel<" + k + ",A>, then <" + k + ",B> (float64, one utterance per workgroup" +
-                                   (h->wpair_ok ? std::string("); FIRST and alone while the inputs are hard: mm_fbw_kernel<") + k + ",A>, then <" + k +
-                                                      ",B> (wide-exponent pairs, two utterances per workgroup)"
-                                                : std::string("; FIRST and alone while the inputs are hard)")) +
-                                   ", mm_dpair_finish_kernel, then for what those mark "
-                             : std::string()) +
-                exact;
-        } else if (h->rows_ok) {
-            auto ka = [&](int d) {
-                for (int k : kRowKA)
-                    if (h->row_ka[d] <= k) return k;
-                return 0;
-            };
-            s = "mm_fbr_kernel<" + std::to_string(ka(0)) + ",8192,0> + mm_fbr_kernel<" + std::to_string(ka(1)) +
-                ",8192,1>, then for marked utterances only " + exact;
-        } else {
-            s = exact;
-        }
+        s = fb_kernels(h);
     } else if (entry == 1) {  // mm_viterbi_f32
         s = h->vit_ok ? "mm_vit_kernel + mm_vit_backtrace_kernel (mm_tropical_kernel + mm_backtrace_kernel when the int32 back-pointers are asked for)"
                       : "mm_tropical_kernel + mm_backtrace_kernel";
@@ -2507,48 +2556,62 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
     return MM_OK;
 }
 
-// (the pair kernels keep N + 2 vectors per utterance and one workspace slot more than utterances)
-static size_t ws_alpha_bytes(mm_batch_t h, int64_t N) {
-    // (+ 16 KB: the service waves copy whole LDS regions of a stored row without clamping, dma_row_b128)
-    if (h->pairs_ok) return align_up(size_t(h->B + 1) * size_t(h->pair_H > 1 ? h->split_s1p : h->max_S1p) * size_t(N + 2) * 4 + 16384, 256);
-    return align_up(size_t(h->total_s1p) * size_t(N + 1) * 4, 256);
-}
 static size_t ws_c_bytes(mm_batch_t h, int64_t N) { return align_up(size_t(h->B + 1) * size_t(N + 2) * 8, 256); }
-// (split kernels) what the workgroups of a team send each other: [2 phases][pairs][2 directions][H sets][2 slots][2 * split_s1p]
-// floats of rows, then [pairs][2][H][4 slots][512] floats of per-pdf partial sums; zeroed before every call
-static size_t ws_x_rows_bytes(mm_batch_t h) {
-    return h->pair_H > 1 ? size_t(2) * size_t((h->B + 1) / 2) * 2 * size_t(h->pair_H) * 2 * (2 * size_t(h->split_s1p)) * 4 : 0;
-}
-static size_t ws_x_bytes(mm_batch_t h) {
-    return h->pair_H > 1 ? align_up(ws_x_rows_bytes(h) + size_t((h->B + 1) / 2) * 2 * size_t(h->pair_H) * 4 * size_t(mm_pair_xps(h->max_P1, h->pair_H)) * 4, 256) : 0;
-}
-// ... and for the teams of the float64 kernels (one utterance per team: B "pairs")
-static size_t ws_xd_rows_bytes(mm_batch_t h) {
-    return h->pair_H > 1 && h->dpair_ok ? size_t(2) * size_t(h->B) * 2 * size_t(h->pair_H) * 2 * (2 * size_t(h->split_s1p)) * 4 : 0;
-}
-static size_t ws_xd_bytes(mm_batch_t h) {
-    // (+ 64 KB: the wide pair teams lay their slots of per-pdf sums -- two doubles per pdf, 16 bytes more per slot for 128 pdfs -- over
-    // the same area, (B + 1) / 2 teams instead of B)
-    return h->pair_H > 1 && h->dpair_ok ? align_up(ws_xd_rows_bytes(h) + size_t(h->B) * 2 * size_t(h->pair_H) * 4 * size_t(mm_pair_xps(h->max_P1, h->pair_H)) * 4 + 65536, 256) : 0;
-}
-static size_t ws_tail_bytes(mm_batch_t h) {  // longest-first order, redo marks, pair hand-over, per-direction log Z minima, team buffers
-    return 2 * align_up(size_t(h->B + 1) * 4, 256) + align_up(size_t(h->B + 1) * 2 * mm_pair_hand_bytes(), 256) +
-           align_up(size_t(h->B) * 6 * 8, 256) + ws_x_bytes(h) + ws_xd_bytes(h) + align_up(size_t(h->B + 1) * 4, 256);  // (last: redo2)
+
+// Where mm_pdfposteriors_f32 and the alpha / beta export keep what they keep in h->ws for N frames: byte offsets, in this order,
+// each aligned to 256 bytes.  The stored vectors, the per-frame offsets; longest-first order, redo marks, pair hand-over, the
+// per-utterance log Z minima; (split kernels) the float32 teams' exchange area, x_rows bytes of rows then per-pdf partial sums,
+// and the float64 teams'; the marks the float64 kernels leave for the log-domain kernels (redo2); the extra region: (quad kernels)
+// the emissions shifted by their per-frame maxima [B][N][P], the maxima [B][N] at em_max, or (stream kernels) their area, its
+// parts at stream[].
+struct WsLayout {
+    size_t alpha = 0, c = 0, order = 0, redo = 0, hand = 0, zmin = 0, x = 0, x_rows = 0, xd = 0, xd_rows = 0, redo2 = 0;
+    size_t extra = 0, em_max = 0, stream[4] = {0, 0, 0, 0}, total = 0;
+};
+
+static WsLayout ws_layout(mm_batch_t h, int64_t N) {
+    WsLayout L;
+    const size_t B = size_t(h->B), marks = align_up((B + 1) * 4, 256);
+    // (the pair kernels keep N + 2 vectors per utterance and one workspace slot more than utterances; + 16 KB: the service waves copy
+    // whole LDS regions of a stored row without clamping, dma_row_b128)
+    L.c = on_pairs(h) ? align_up((B + 1) * size_t(h->pair_H > 1 ? h->split_s1p : h->max_S1p) * size_t(N + 2) * 4 + 16384, 256)
+                      : align_up(size_t(h->total_s1p) * size_t(N + 1) * 4, 256);
+    L.order = L.c + ws_c_bytes(h, N);
+    L.redo = L.order + marks;
+    L.hand = L.redo + marks;
+    L.zmin = L.hand + align_up((B + 1) * 2 * mm_pair_hand_bytes(), 256);
+    L.x = L.zmin + align_up(B * 6 * 8, 256);
+    L.xd = L.redo2 = L.x;
+    if (h->pair_H > 1) {
+        // what the workgroups of a team send each other: [2 phases][pairs][2 directions][H sets][2 slots][2 * split_s1p] floats of
+        // rows, then [pairs][2][H][4 slots][mm_pair_xps] floats of per-pdf partial sums; zeroed before every call
+        const size_t H = size_t(h->pair_H), row = 2 * size_t(h->split_s1p) * 4, xps = size_t(mm_pair_xps(h->max_P1, h->pair_H)) * 4;
+        L.x_rows = 2 * ((B + 1) / 2) * 2 * H * 2 * row;
+        L.xd = L.redo2 = L.x + align_up(L.x_rows + ((B + 1) / 2) * 2 * H * 4 * xps, 256);
+        // ... and for the teams of the float64 kernels (one utterance per team: B "pairs"; + 64 KB: the wide pair teams lay their
+        // slots of per-pdf sums -- two doubles per pdf, 16 bytes more per slot for 128 pdfs -- over the same area, (B + 1) / 2 teams
+        // instead of B)
+        if (h->dpair_ok) {
+            L.xd_rows = 2 * B * 2 * H * 2 * row;
+            L.redo2 = L.xd + align_up(L.xd_rows + B * 2 * H * 4 * xps + 65536, 256);
+        }
+    }
+    L.extra = L.redo2 + marks;
+    L.total = L.extra;
+    if (h->fb == Fb::Stream) {  // (the backward direction's vectors and offsets, the frames' log Z, the teams' exchange area)
+        L.total += mm_stream_extra_bytes(h->B, h->total_s1p, N, L.stream, h->stream_H, h->stream_S1);
+        for (size_t &o : L.stream) o += L.extra;
+    } else if (h->quad_built) {
+        L.em_max = L.extra + align_up(B * size_t(N) * size_t(h->max_P1 - 1) * 4, 256);
+        L.total = L.em_max + align_up(B * size_t(N) * 4, 256);
+    }
+    return L;
 }
 
-// (quad kernels) the emissions shifted by their per-frame maxima [B][N][P], and the maxima [B][N]
-static size_t ws_shift_bytes(mm_batch_t h, int64_t N) {
-    if (h->stream_ok) {  // (stream kernels: the backward direction's vectors and offsets, the frames' log Z, the teams' exchange area)
-        size_t off[4];
-        return mm_stream_extra_bytes(h->B, h->total_s1p, N, off, h->stream_H, h->stream_S1);
-    }
-    if (!h->fast_ok || !h->quad_built) return 0;
-    return align_up(size_t(h->B) * size_t(N) * size_t(h->max_P1 - 1) * 4, 256) + align_up(size_t(h->B) * size_t(N) * 4, 256);
-}
 size_t mm_batch_workspace_bytes(mm_batch_t h, int64_t N) {
     if (!h || N < 0) return 0;
     if (h->log_twin) return mm_batch_workspace_bytes(h->log_twin, N) + align_up(size_t(h->B) * size_t(N) * size_t(h->max_P1 - 1) * 4, 256);
-    return ws_alpha_bytes(h, N) + ws_c_bytes(h, N) + ws_tail_bytes(h) + ws_shift_bytes(h, N);
+    return ws_layout(h, N).total;
 }
 
 
@@ -2564,9 +2627,7 @@ static int ensure_ws(mm_batch_t h, size_t bytes, void *stream = nullptr) {
     if (h->ws_bytes >= bytes) return MM_OK;
     // growing frees the old workspace: never while the caller's stream is capturing (a graph captured earlier on this
     // batch has the old pointers baked in; mm_batch_reserve is the way to size it up front)
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-        return fail(MM_ERR_INVALID, "the workspace would have to grow during stream capture: call mm_batch_reserve first");
+    if (capturing(stream)) return fail(MM_ERR_INVALID, "the workspace would have to grow during stream capture: call mm_batch_reserve first");
     if (h->ws) {
         HIP_TRY(hipFree(h->ws));  // synchronises: only on growth
         h->ws = nullptr;
@@ -2583,9 +2644,7 @@ static int ensure_ws(mm_batch_t h, size_t bytes, void *stream = nullptr) {
 static int ensure_prob_logv(mm_batch_t h, int64_t N, void *stream) {
     const size_t bytes = align_up(size_t(h->B) * size_t(N) * size_t(h->max_P1 - 1) * 4, 256);
     if (h->prob_logv_bytes >= bytes) return MM_OK;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (stream && hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-        return fail(MM_ERR_INVALID, "the workspace would have to grow during stream capture: call mm_batch_reserve first");
+    if (capturing(stream)) return fail(MM_ERR_INVALID, "the workspace would have to grow during stream capture: call mm_batch_reserve first");
     if (h->prob_logv) {
         HIP_TRY(hipFree(h->prob_logv));
         h->prob_logv = nullptr;
@@ -2664,49 +2723,186 @@ static int prob_pdfposteriors(mm_batch_t h, const float *V, int64_t vsb, int64_t
     return MM_OK;
 }
 
+// ---- mm_pdfposteriors_f32, one function per kernel family (h->fb): p holds the call, its marks set by the prologue
+
+// the item kernel for what the kernels before it marked (p.redo), both passes in ONE launch whose workgroups of the other utterances
+// leave at once (streamed items: its speed does not matter, the empty launch's does)
+static int redo_on_items(mm_batch_t h, const RunParams &p, void *stream) {
+    return launch(mm_log_kernel<MODE_FB, 0, 0, false, false>, mm_log_kernel<MODE_FB, 0, 0, false, true>, h, p, true, pick_geometry(h).NW, stream);
+}
+
+// the library's own zeroing kernel over `bytes` (a multiple of 16) at d
+static int zero_dev(void *d, size_t bytes, void *stream) {
+    const size_t zn = bytes / 16;
+    hipLaunchKernelGGL(mm_zero_kernel, dim3(unsigned(std::min<size_t>(2048, (zn + 255) / 256))), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<char *>(d), (unsigned long long)zn);
+    HIP_TRY(hipGetLastError());
+    return MM_OK;
+}
+
+// (split kernels) the team's sets and the float32 teams' exchange area, zeroed (a zero dword = not yet arrived).  The float64 teams'
+// area instead when `f64` (a call that goes to the float64 kernels with the whole batch leaves the float32 kernels' area alone); the
+// finish kernel zeroes the float64 area of the utterances it leaves marked.  (A kernel of the library's own, not hipMemsetAsync:
+// inside a captured hipGraph the runtime's memset node has been seen to overlap the team kernel behind it on replay -- the handshake
+// granules of a launch wiped after they were published, every team timing out and every utterance recomputed by the exact kernels:
+// round 6, tests/test_gpu_lfmmi.py::test_lfmmi_step_in_one_hip_graph; and the runtime's memset is two fill kernels, this is one)
+static int bind_team_x(mm_batch_t h, RunParams &p, char *ws, const WsLayout &L, bool f64, void *stream) {
+    const SplitInfo &si = h->fsms[0]->split;
+    for (int s = 0; s < h->pair_H; ++s) {
+        p.sp_base[s] = si.base[s];
+        p.sp_cnt[s] = si.count[s];
+    }
+    p.xbuf = reinterpret_cast<float *>(ws + L.x);
+    p.xps = reinterpret_cast<float *>(ws + L.x + L.x_rows);
+    p.x_slot = 2ll * h->split_s1p;
+    p.x_psn = mm_pair_xps(h->max_P1, h->pair_H);
+    p.x_phase = (long long)(L.x_rows / 8);
+    return f64 ? zero_dev(ws + L.xd, L.redo2 - L.xd, stream) : zero_dev(ws + L.x, L.xd - L.x, stream);
+}
+
+// the lane kernel decides per utterance whether its float64 range was enough (every workgroup writes its own mark: no zeroing
+// pass); what it marks -- the one path of a left-to-right graph through values 1000 log2 below their frames' maxima -- goes to
+// the wave kernel (whose workgroups of unmarked utterances leave at once; same workspace layout) or the item kernel
+static int fb_lane(mm_batch_t h, RunParams &p, char *ws, const WsLayout &L, void *stream) {
+    p.redo = reinterpret_cast<int *>(ws + L.redo);
+    h->last_redo = p.redo;
+    const int rc = mm_launch_lane(h->B, h->lane_S, p, static_cast<hipStream_t>(stream));
+    if (rc || h->dbg.no_redo) return rc;
+    if (h->lane_redo_wave) {
+        p.pair_zmin = reinterpret_cast<double *>(ws + L.zmin);
+        return mm_launch_wave(wave_launch_of(h), p, static_cast<hipStream_t>(stream));
+    }
+    return redo_on_items(h, p, stream);
+}
+
+// the stream kernels (forward launch, backward launch, finish), then -- for the utterances whose range marks stay: values beyond
+// the double's range that carry mass, normally none -- the item kernel
+static int fb_stream(mm_batch_t h, RunParams &p, char *ws, const WsLayout &L, void *stream) {
+    p.pair_zmin = reinterpret_cast<double *>(ws + L.zmin);
+    h->last_redo = p.redo;
+    h->last_z = p.pair_zmin;
+    p.xbuf = reinterpret_cast<float *>(ws + L.stream[0]);    // the backward direction's vectors
+    p.xbuf_d = reinterpret_cast<float *>(ws + L.stream[1]);  // ... and offsets (doubles)
+    p.xps = reinterpret_cast<float *>(ws + L.stream[2]);     // the frames' {log2 Z, overlap term} (doubles)
+    if (h->stream_H > 1) {  // the teams' exchange area: zeroed before every call (a zero dword = not yet arrived)
+        p.sx = reinterpret_cast<unsigned *>(ws + L.stream[3]);
+        p.sx_slot = (long long)mm_stream_slot(h->stream_S1);
+        const int rc = zero_dev(p.sx, mm_stream_exchange_bytes(h->B, h->stream_H, h->stream_S1), stream);
+        if (rc) return rc;
+    }
+    const int rc = mm_launch_stream(h->B, h->n_cus, h->stream_S1, h->max_P1, h->stream_H, p, static_cast<hipStream_t>(stream));
+    if (rc || h->dbg.no_redo) return rc;
+    return redo_on_items(h, p, stream);
+}
+
+static int fb_wave(mm_batch_t h, RunParams &p, char *ws, const WsLayout &L, void *stream) {
+    p.pair_zmin = reinterpret_cast<double *>(ws + L.zmin);
+    return mm_launch_wave(wave_launch_of(h), p, static_cast<hipStream_t>(stream));
+}
+
+// the quad kernels where they are usable, on emissions shifted by their per-frame maxima (see mm_shift_em_kernel), else -- and
+// where they turn out not to be (MM_ERR_UNSUPPORTED) -- the item kernel
+static int fb_exact(mm_batch_t h, const RunParams &p, char *ws, const WsLayout &L, void *stream) {
+    if (h->quad_ok) {
+        bool same_P = true;
+        for (int64_t b = 1; b < h->B && same_P; ++b) same_P = h->fsms[b]->P1 == h->fsms[0]->P1;
+        RunParams q = p;
+        float *E = nullptr;
+        if (same_P) {
+            float *Vs = reinterpret_cast<float *>(ws + L.extra);
+            E = reinterpret_cast<float *>(ws + L.em_max);
+            hipLaunchKernelGGL(mm_shift_em_kernel, dim3(unsigned(h->B), 8), dim3(256), 0, static_cast<hipStream_t>(stream), p, Vs, E);
+            HIP_TRY(hipGetLastError());
+            q.V = Vs;
+            q.vsb = int64_t(p.N) * int64_t(h->max_P1 - 1);
+            q.vsn = h->max_P1 - 1;
+        }
+        const int rc = launch_quad(h, q, stream);
+        if (rc != MM_ERR_UNSUPPORTED) {
+            if (!rc && same_P) {
+                hipLaunchKernelGGL(mm_shift_ttl_kernel, dim3(unsigned(h->B)), dim3(256), 0, static_cast<hipStream_t>(stream), p, E);
+                HIP_TRY(hipGetLastError());
+            }
+            return rc;
+        }
+    }
+    return launch_log<MODE_FB>(h, p, stream);
+}
+
+// the pair, team or row kernels, then -- for the utterances they marked (linear sums outside the trusted range), normally none:
+// every workgroup then leaves at once -- the float64 pair kernels (the whole batch, and first, when exact_first), and for what
+// THEY mark -- values beyond the double's range that carry mass -- the log-domain kernels
+static int fb_linear(mm_batch_t h, RunParams &p, char *ws, const WsLayout &L, bool exact_first, void *stream) {
+    h->last_redo = p.redo;
+    h->last_exact_first = exact_first;
+    int rc;
+    if (h->fb == Fb::Rows) {
+        rc = launch_rows(h, p, stream);
+    } else {
+        p.pair_s1p = h->pair_H > 1 ? h->split_s1p : h->max_S1p;
+        p.pair_hand = ws + L.hand;
+        p.pair_zmin = reinterpret_cast<double *>(ws + L.zmin);
+        if (h->fb == Fb::Split) {
+            p.xbuf_d = reinterpret_cast<float *>(ws + L.xd);
+            p.xps_d = reinterpret_cast<float *>(ws + L.xd + L.xd_rows);
+            p.x_phase_d = (long long)(L.xd_rows / 8);
+            p.x_H = h->dpair_ok ? h->pair_H : 0;
+            rc = bind_team_x(h, p, ws, L, exact_first, stream);
+            if (rc) return rc;
+        }
+        h->last_z = p.pair_zmin;
+        rc = exact_first ? MM_OK : launch_pairs(h, p, stream);
+    }
+    if (rc) return rc;
+    if (h->dbg.no_redo && !exact_first) return MM_OK;
+    if (h->dpair_ok) {
+        // a whole batch (exact_first: every utterance is marked): two utterances per workgroup on the wide pair kernels
+        const PairLaunch pl = pair_launch_of(h);
+        rc = exact_first && h->wpair_ok ? mm_launch_wpairs(pl, p, static_cast<hipStream_t>(stream)) : mm_launch_dpairs(pl, p, static_cast<hipStream_t>(stream));
+        if (rc) return rc;
+        h->last_redo2 = p.redo2;
+        p.redo = p.redo2;
+        if (h->dbg.no_redo || h->dbg.no_fallback) return MM_OK;
+        if (!h->quad_ok) return redo_on_items(h, p, stream);
+    }
+    return fb_exact(h, p, ws, L, stream);
+}
+
 int mm_pdfposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N,
                          float *gamma, int64_t gsb, int64_t gsn, int64_t gsp, float *ttl, void *stream) {
     if (h && h->semiring == MM_PROB) return prob_pdfposteriors(h, V, vsb, vsn, lens, N, gamma, gsb, gsn, gsp, ttl, stream);
     int rc = check_run(h, "mm_pdfposteriors_f32", V, N, MM_LOG);
     if (rc) return rc;
     if (!gamma || !ttl) return fail(MM_ERR_INVALID, "mm_pdfposteriors_f32: gamma/ttl is NULL");
-    h->last_redo = nullptr;
-    h->last_z = nullptr;
     // more utterances than CUs and different lengths: hand the workgroups out longest first; the pair kernels also
     // pair the utterances in that order (the two of a pair run the same number of frames)
-    const bool ordered = lens && (h->B > h->n_cus || h->pairs_ok) && h->B <= 8192;
-    rc = ensure_ws(h, mm_batch_workspace_bytes(h, N), stream);
+    const bool ordered = lens && (h->B > h->n_cus || on_pairs(h)) && h->B <= 8192;
+    const WsLayout L = ws_layout(h, N);
+    rc = ensure_ws(h, L.total, stream);
     if (rc) return rc;
-    RunParams p{};
-    p.utts = h->d_utts;
-    p.V = V;
-    p.vsb = vsb;
-    p.vsn = vsn;
-    p.lens = lens;
-    p.N = int(N);
-    p.B = int(h->B);
+    char *const ws = static_cast<char *>(h->ws);
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
     p.x_sleep = h->dbg.x_sleep;
     // (the backward agent's phase-B steps are ~10 % dearer than the forward agent's on the pair kernels -- cycle stamps, config 3:
     // 4990 against 4520 --, the phase-A steps alike: the cut that levels both launches lies at 0.48 of the frames; the steps of
     // the team kernels are bound by the exchange, the same in both directions)
     p.split_q10 = h->dbg.split_q10 > 0 ? h->dbg.split_q10 : (h->pair_H == 1 ? MM_PAIR_SPLIT_Q10 : 512);
-    p.x_timeout = std::min<unsigned long long>(10000000ull, std::max<unsigned long long>(200000ull, 1000ull * (unsigned long long)N));
+    p.x_timeout = x_timeout(N);
     p.lt_floor = h->lt_floor;
     p.clear_marks = h->keep_marks ? 0 : 1;
     p.g_scale = h->g_scale;
     p.g_acc = h->g_acc ? 1 : 0;
-    p.ws_alpha = static_cast<float *>(h->ws);
-    p.ws_c = reinterpret_cast<double *>(static_cast<char *>(h->ws) + ws_alpha_bytes(h, N));
+    p.ws_alpha = reinterpret_cast<float *>(ws + L.alpha);
+    p.ws_c = reinterpret_cast<double *>(ws + L.c);
     p.gamma = gamma;
     p.gsb = gsb;
     p.gsn = gsn;
     p.gsp = gsp;
     p.ttl = ttl;
     p.xcsr = h->xcsr;
-    char *const tail0 = static_cast<char *>(h->ws) + ws_alpha_bytes(h, N) + ws_c_bytes(h, N);
-    int *const order = ordered ? reinterpret_cast<int *>(tail0) : nullptr;  // (first of the tail)
+    int *const order = ordered ? reinterpret_cast<int *>(ws + L.order) : nullptr;
     p.order = order;
-    const bool marks = !h->wave_ok && !h->lane_ok && (h->rows_ok || h->pairs_ok || h->stream_ok);
+    const bool marks = h->fb == Fb::Rows || on_pairs(h) || h->fb == Fb::Stream;
     // Which kernels first?  The float32 pair kernels, unless the inputs of the last finished call were beyond them for some of
     // its utterances (a sharp acoustic model marks every utterance) AND starting with the float64 kernels costs no more rounds
     // of workgroups than the float32 kernels followed by the float64 kernels for that many utterances would -- a launch lasts as
@@ -2717,7 +2913,7 @@ int mm_pdfposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
     // choice follows the data back as well.  Read without synchronising: the count of whatever call finished last.
     bool exact_first = false;
     if (marks) {
-        p.redo = reinterpret_cast<int *>(tail0 + align_up(size_t(h->B + 1) * 4, 256));
+        p.redo = reinterpret_cast<int *>(ws + L.redo);
         if (h->dpair_ok) {
             const int64_t M = h->stat_host[0], H = h->pair_H, cus = std::max(1, h->n_cus);
             auto rounds = [&](int64_t wgs) { return (wgs + cus - 1) / cus; };
@@ -2725,10 +2921,8 @@ int mm_pdfposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
             // float32 kernels followed by a round of the float64 ones for ANY number of marked utterances)
             const bool by_rounds = M > 0 && (h->wpair_ok || rounds(2 * h->B * H) <= rounds(2 * ((h->B + 1) / 2) * H) + rounds(2 * std::min<int64_t>(M, h->B) * H));
             // (a capture must not bake in the marks of whatever call finished last: the automatic choice is float32-first there)
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            const bool capturing = hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-            exact_first = h->exact_first >= 0 ? h->exact_first != 0 : (by_rounds && !capturing);
-            p.redo2 = reinterpret_cast<int *>(tail0 + ws_tail_bytes(h) - align_up(size_t(h->B + 1) * 4, 256));
+            exact_first = h->exact_first >= 0 ? h->exact_first != 0 : (by_rounds && !capturing(stream));
+            p.redo2 = reinterpret_cast<int *>(ws + L.redo2);
             p.stat_dev = h->stat_dev;
             p.stat_xcd = h->xcd_counting ? 1 : 0;
             p.stat_host = h->stat_host;
@@ -2743,165 +2937,18 @@ int mm_pdfposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
                            lens, int(h->B), int(N), order, p.redo, p.redo2, exact_first ? 1 : 0);
         HIP_TRY(hipGetLastError());
     }
-#ifdef MM_STAMPS
-    if (!g_dbg) {
-        g_dbg_n = size_t(16) * MM_MAX_WAVES * size_t(h->B);
-        (void)hipMalloc(&g_dbg, sizeof(unsigned long long) * g_dbg_n);
+    bind_stamps(h, p);
+    switch (h->fb) {
+    case Fb::Lane: return fb_lane(h, p, ws, L, stream);
+    case Fb::Stream: return fb_stream(h, p, ws, L, stream);
+    case Fb::Wave: return fb_wave(h, p, ws, L, stream);
+    case Fb::Rows:
+    case Fb::Pairs:
+    case Fb::Split: return fb_linear(h, p, ws, L, exact_first, stream);
+    case Fb::Quad:
+    case Fb::Item: break;
     }
-    p.dbg = g_dbg;
-#endif
-    if (h->lane_ok) {
-        // the lane kernel decides per utterance whether its float64 range was enough (every workgroup writes its own mark: no
-        // zeroing pass); what it marks -- the one path of a left-to-right graph through values 1000 log2 below their frames'
-        // maxima -- goes to the item kernel, both passes in ONE launch whose workgroups leave at once otherwise
-        p.redo = reinterpret_cast<int *>(tail0 + align_up(size_t(h->B + 1) * 4, 256));
-        h->last_redo = p.redo;
-        rc = mm_launch_lane(h->B, h->lane_S, p, static_cast<hipStream_t>(stream));
-        if (rc || h->dbg.no_redo) return rc;
-        if (h->lane_redo_wave) {  // (the wave kernel's workgroups of unmarked utterances leave at once; same workspace layout)
-            p.pair_zmin = reinterpret_cast<double *>(tail0 + 2 * align_up(size_t(h->B + 1) * 4, 256) + align_up(size_t(h->B + 1) * 2 * mm_pair_hand_bytes(), 256));
-            WaveLaunch wlc;
-            wlc.B = h->B;
-            wlc.nseg = h->wave_nseg;
-            wlc.max_P1 = h->max_P1;
-            wlc.n_cus = h->n_cus;
-            return mm_launch_wave(wlc, p, static_cast<hipStream_t>(stream));
-        }
-        return launch(mm_log_kernel<MODE_FB, 0, 0, false, false>, mm_log_kernel<MODE_FB, 0, 0, false, true>, h, p, true, pick_geometry(h).NW, stream);
-    }
-    if (h->stream_ok) {
-        // the stream kernels (forward launch, backward launch, finish), then -- for the utterances whose range marks stay: values
-        // beyond the double's range that carry mass, normally none -- the item kernel, both passes in one launch
-        p.pair_zmin = reinterpret_cast<double *>(tail0 + 2 * align_up(size_t(h->B + 1) * 4, 256) + align_up(size_t(h->B + 1) * 2 * mm_pair_hand_bytes(), 256));
-        h->last_redo = p.redo;
-        h->last_z = p.pair_zmin;
-        {
-            size_t off[4];
-            (void)mm_stream_extra_bytes(h->B, h->total_s1p, N, off, h->stream_H, h->stream_S1);
-            char *base = tail0 + ws_tail_bytes(h);
-            p.xbuf = reinterpret_cast<float *>(base + off[0]);    // the backward direction's vectors
-            p.xbuf_d = reinterpret_cast<float *>(base + off[1]);  // ... and offsets (doubles)
-            p.xps = reinterpret_cast<float *>(base + off[2]);     // the frames' {log2 Z, overlap term} (doubles)
-            if (h->stream_H > 1) {  // the teams' exchange area: zeroed before every call (a zero dword = not yet arrived)
-                p.sx = reinterpret_cast<unsigned *>(base + off[3]);
-                p.sx_slot = (long long)mm_stream_slot(h->stream_S1);
-                const size_t zn = mm_stream_exchange_bytes(h->B, h->stream_H, h->stream_S1) / 16;
-                hipLaunchKernelGGL(mm_zero_kernel, dim3(unsigned(std::min<size_t>(2048, (zn + 255) / 256))), dim3(256), 0, static_cast<hipStream_t>(stream),
-                                   reinterpret_cast<char *>(p.sx), (unsigned long long)zn);
-                HIP_TRY(hipGetLastError());
-            }
-        }
-        rc = mm_launch_stream(h->B, h->n_cus, h->stream_S1, h->max_P1, h->stream_H, p, static_cast<hipStream_t>(stream));
-        if (rc || h->dbg.no_redo) return rc;
-        return launch(mm_log_kernel<MODE_FB, 0, 0, false, false>, mm_log_kernel<MODE_FB, 0, 0, false, true>, h, p, true, pick_geometry(h).NW, stream);
-    }
-    if (h->wave_ok) {
-        char *tail = static_cast<char *>(h->ws) + ws_alpha_bytes(h, N) + ws_c_bytes(h, N);
-        p.pair_zmin = reinterpret_cast<double *>(tail + 2 * align_up(size_t(h->B + 1) * 4, 256) + align_up(size_t(h->B + 1) * 2 * mm_pair_hand_bytes(), 256));
-        WaveLaunch wlc;
-        wlc.B = h->B;
-        wlc.nseg = h->wave_nseg;
-        wlc.max_P1 = h->max_P1;
-        wlc.n_cus = h->n_cus;
-        return mm_launch_wave(wlc, p, static_cast<hipStream_t>(stream));
-    }
-    if (h->rows_ok || h->pairs_ok) {
-        // the pair or row kernels, then -- for the utterances they marked (linear sums outside the trusted range),
-        // normally none: every workgroup then leaves at once -- the exact kernels
-        char *tail = tail0;
-        h->last_redo = p.redo;
-        h->last_exact_first = exact_first;
-        if (h->pairs_ok) {
-            p.pair_s1p = h->pair_H > 1 ? h->split_s1p : h->max_S1p;
-            p.pair_hand = tail + 2 * align_up(size_t(h->B + 1) * 4, 256);
-            p.pair_zmin = reinterpret_cast<double *>(static_cast<char *>(p.pair_hand) + align_up(size_t(h->B + 1) * 2 * mm_pair_hand_bytes(), 256));
-            if (h->pair_H > 1) {
-                const SplitInfo &si = h->fsms[0]->split;
-                for (int s = 0; s < h->pair_H; ++s) {
-                    p.sp_base[s] = si.base[s];
-                    p.sp_cnt[s] = si.count[s];
-                }
-                p.xbuf = reinterpret_cast<float *>(reinterpret_cast<char *>(p.pair_zmin) + align_up(size_t(h->B) * 6 * 8, 256));
-                p.xps = reinterpret_cast<float *>(reinterpret_cast<char *>(p.xbuf) + ws_x_rows_bytes(h));
-                p.x_slot = 2ll * h->split_s1p;
-                p.x_psn = mm_pair_xps(h->max_P1, h->pair_H);
-                p.x_phase = (long long)(ws_x_rows_bytes(h) / 8);
-                p.x_sleep = h->dbg.x_sleep;
-                p.xbuf_d = reinterpret_cast<float *>(reinterpret_cast<char *>(p.xbuf) + ws_x_bytes(h));
-                p.xps_d = reinterpret_cast<float *>(reinterpret_cast<char *>(p.xbuf_d) + ws_xd_rows_bytes(h));
-                p.x_phase_d = (long long)(ws_xd_rows_bytes(h) / 8);
-                // (one memset node over what this call can touch: a call that goes to the float64 kernels with the whole batch leaves
-                // the float32 kernels' area alone, one that starts with the float32 kernels zeroes both -- marks are not known here)
-                p.x_H = h->dpair_ok ? h->pair_H : 0;
-                // (one memset node: the float64 kernels' area when they take the whole batch, else the float32 kernels' -- the
-                // finish kernel then zeroes the float64 area of the utterances it leaves marked)
-                // (a kernel of the library's own, not hipMemsetAsync: inside a captured hipGraph the runtime's memset node has been seen
-                // to overlap the team kernel behind it on replay -- the handshake granules of a launch wiped after they were
-                // published, every team timing out and every utterance recomputed by the exact kernels: round 6,
-                // tests/test_gpu_lfmmi.py::test_lfmmi_step_in_one_hip_graph; and the runtime's memset is two fill kernels, this is one)
-                {
-                    char *zp = reinterpret_cast<char *>(exact_first ? p.xbuf_d : p.xbuf);
-                    const size_t zn = (exact_first ? ws_xd_bytes(h) : ws_x_bytes(h)) / 16;  // (both sizes are multiples of 256)
-                    const unsigned zb = unsigned(std::min<size_t>(2048, (zn + 255) / 256));
-                    hipLaunchKernelGGL(mm_zero_kernel, dim3(zb), dim3(256), 0, static_cast<hipStream_t>(stream), zp, (unsigned long long)zn);
-                    HIP_TRY(hipGetLastError());
-                }
-            }
-            h->last_z = p.pair_zmin;
-            rc = exact_first ? MM_OK : launch_pairs(h, p, stream);
-        } else {
-            rc = launch_rows(h, p, stream);
-        }
-        if (rc) return rc;
-        if (h->dbg.no_redo && !exact_first) return MM_OK;
-        if (h->dpair_ok) {
-            // the float64 pair kernels for the marked utterances (workgroups of the others leave at once); what THEY mark --
-            // values beyond the double's range that carry mass -- is left in redo2 for the log-domain kernels below
-            PairLaunch pl;
-            pl.B = h->B;
-            pl.nwc = h->pair_nwc;
-            pl.slotrows = h->pair_slotrows;
-            pl.max_P1 = h->max_P1;
-            pl.pair_ka = h->pair_ka;
-            pl.H = h->pair_H;
-            // a whole batch (exact_first: every utterance is marked): two utterances per workgroup on the wide pair kernels
-            rc = exact_first && h->wpair_ok ? mm_launch_wpairs(pl, p, static_cast<hipStream_t>(stream)) : mm_launch_dpairs(pl, p, static_cast<hipStream_t>(stream));
-            if (rc) return rc;
-            h->last_redo2 = p.redo2;
-            p.redo = p.redo2;
-            if (h->dbg.no_redo || h->dbg.no_fallback) return MM_OK;
-            // what the float64 kernels hand on (values beyond a double's range that carry mass: normally nothing) goes to the
-            // item kernel, both passes in ONE launch (streamed items: its speed does not matter, the empty launch's does)
-            if (!quad_kernel_usable(h))
-                return launch(mm_log_kernel<MODE_FB, 0, 0, false, false>, mm_log_kernel<MODE_FB, 0, 0, false, true>, h, p, true, pick_geometry(h).NW, stream);
-        }
-    }
-    if (quad_kernel_usable(h)) {
-        // the quad kernels run on emissions shifted by their per-frame maxima (see mm_shift_em_kernel)
-        bool same_P = true;
-        for (int64_t b = 1; b < h->B && same_P; ++b) same_P = h->fsms[b]->P1 == h->fsms[0]->P1;
-        RunParams q = p;
-        float *Vs = nullptr, *E = nullptr;
-        if (same_P) {
-            char *base = static_cast<char *>(h->ws) + ws_alpha_bytes(h, N) + ws_c_bytes(h, N) + ws_tail_bytes(h);
-            Vs = reinterpret_cast<float *>(base);
-            E = reinterpret_cast<float *>(base + align_up(size_t(h->B) * size_t(N) * size_t(h->max_P1 - 1) * 4, 256));
-            hipLaunchKernelGGL(mm_shift_em_kernel, dim3(unsigned(h->B), 8), dim3(256), 0, static_cast<hipStream_t>(stream), p, Vs, E);
-            HIP_TRY(hipGetLastError());
-            q.V = Vs;
-            q.vsb = N * int64_t(h->max_P1 - 1);
-            q.vsn = h->max_P1 - 1;
-        }
-        rc = launch_quad(h, q, stream);
-        if (rc != MM_ERR_UNSUPPORTED) {
-            if (!rc && same_P) {
-                hipLaunchKernelGGL(mm_shift_ttl_kernel, dim3(unsigned(h->B)), dim3(256), 0, static_cast<hipStream_t>(stream), p, E);
-                HIP_TRY(hipGetLastError());
-            }
-            return rc;
-        }
-    }
-    return launch_log<MODE_FB>(h, p, stream);
+    return fb_exact(h, p, ws, L, stream);
 }
 
 // The arc forms of a batch (mm_kernel_arcs.hip): per FSM, the slot of the backward item form that holds each caller entry and the
@@ -2909,8 +2956,7 @@ int mm_pdfposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
 // Made on the first mm_arcposteriors_f32 call, like the item forms: never during a stream capture.
 static int ensure_arc_forms(mm_batch_t h, void *stream) {
     if (h->d_arcs) return MM_OK;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+    if (capturing(stream))
         return fail(MM_ERR_INVALID, "the arc forms of this batch are not on the device yet: run mm_arcposteriors_f32 once outside a stream capture");
     std::vector<ArcDev> arcs(size_t(h->B));
     int64_t slots = 0;
@@ -3004,14 +3050,7 @@ int mm_arcposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
     rc = ensure_ws(h, std::max(mm_batch_workspace_bytes(h, N), arc_ws_bytes(h, N, off)), stream);
     if (rc) return rc;
     char *ws = static_cast<char *>(h->ws);
-    RunParams p{};
-    p.utts = h->d_utts;
-    p.V = V;
-    p.vsb = vsb;
-    p.vsn = vsn;
-    p.lens = lens;
-    p.N = int(N);
-    p.B = int(h->B);
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
     p.ws_alpha = reinterpret_cast<float *>(ws);
     p.ws_c = reinterpret_cast<double *>(ws + off[0]);
     if (bigv) {
@@ -3033,19 +3072,8 @@ int mm_arcposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
 // alpha / beta export on the pair kernels (mm_pairs_tu.hip: mm_fbx_kernel + mm_pair_export_kernel): one shared graph in the pair
 // form whose every state takes part (the packer drops states that cannot be reached or cannot reach the final state -- their
 // posteriors are zero, their alpha / beta are not), log semiring, up to 250 pdfs
-static PairLaunch pair_launch_of(mm_batch_t h) {
-    PairLaunch pl;
-    pl.B = h->B;
-    pl.nwc = h->pair_nwc;
-    pl.slotrows = h->pair_slotrows;
-    pl.max_P1 = h->max_P1;
-    pl.pair_ka = h->pair_ka;
-    pl.H = h->pair_H;
-    pl.small = h->pair_H == 1 && h->max_S1p <= 128;
-    return pl;
-}
 static bool export_on_pairs(mm_batch_t h, int dir) {
-    if (h->semiring != MM_LOG || !h->pairs_ok) return false;
+    if (!on_pairs(h)) return false;
     if (!(h->pair_H == 1 ? mm_pair_export_fits(pair_launch_of(h)) : mm_split_export_fits(pair_launch_of(h)))) return false;
     return h->fsms[0]->export_ok[dir];
 }
@@ -3057,14 +3085,7 @@ static int run_export(mm_batch_t h, int mode, const float *V, int64_t vsb, int64
     if (rc) return rc;
     if (!out) return fail(MM_ERR_INVALID, std::string(who) + ": out is NULL");
     if (out_stride_n < h->total_states) return fail(MM_ERR_DIM, std::string(who) + ": out_stride_n < total states");
-    RunParams p{};
-    p.utts = h->d_utts;
-    p.V = V;
-    p.vsb = vsb;
-    p.vsn = vsn;
-    p.lens = lens;
-    p.N = int(N);
-    p.B = int(h->B);
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
     p.out = out;
     p.out_stride_n = out_stride_n;
     // (inputs whose vectors leave float32's range in most utterances -- the reference's WSJ denominator in the forward direction: its
@@ -3077,45 +3098,32 @@ static int run_export(mm_batch_t h, int mode, const float *V, int64_t vsb, int64
     if (linear_first && h->exact_first == 1) linear_first = false;
     else if (linear_first && h->stat_host && h->exact_first < 0) {
         const int dirx = mode == MODE_ALPHA ? 0 : 1;
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        const bool capturing = hipStreamIsCapturing(static_cast<hipStream_t>(stream), &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
         const bool probe = (++h->export_calls[dirx] & 31u) == 0u;
-        if (!capturing && !probe && 2 * int64_t(h->stat_host[2 + dirx]) > h->B) linear_first = false;
+        if (!capturing(stream) && !probe && 2 * int64_t(h->stat_host[2 + dirx]) > h->B) linear_first = false;
     }
     if (linear_first) {
         // phase A of ONE direction over all N + 1 frames with two utterances per workgroup (linear domain, float32), the layout
         // pass, then -- for the utterances whose values left float32's range (marked; sharp emissions) -- the item kernel
-        rc = ensure_ws(h, mm_batch_workspace_bytes(h, N), stream);
+        const WsLayout L = ws_layout(h, N);
+        rc = ensure_ws(h, L.total, stream);
         if (rc) return rc;
-        char *const tail0 = static_cast<char *>(h->ws) + ws_alpha_bytes(h, N) + ws_c_bytes(h, N);
-        p.ws_alpha = static_cast<float *>(h->ws);
-        p.ws_c = reinterpret_cast<double *>(static_cast<char *>(h->ws) + ws_alpha_bytes(h, N));
-        p.redo = reinterpret_cast<int *>(tail0 + align_up(size_t(h->B + 1) * 4, 256));
+        char *const ws = static_cast<char *>(h->ws);
+        p.ws_alpha = reinterpret_cast<float *>(ws + L.alpha);
+        p.ws_c = reinterpret_cast<double *>(ws + L.c);
+        p.redo = reinterpret_cast<int *>(ws + L.redo);
         p.pair_s1p = h->pair_H > 1 ? h->split_s1p : h->max_S1p;
-        p.pair_hand = tail0 + 2 * align_up(size_t(h->B + 1) * 4, 256);
-        p.pair_zmin = reinterpret_cast<double *>(static_cast<char *>(p.pair_hand) + align_up(size_t(h->B + 1) * 2 * mm_pair_hand_bytes(), 256));
+        p.pair_hand = ws + L.hand;
+        p.pair_zmin = reinterpret_cast<double *>(ws + L.zmin);
         p.split_q10 = 512;
         p.lt_floor = h->lt_floor;
         p.x_sleep = h->dbg.x_sleep;
-        p.x_timeout = std::min<unsigned long long>(10000000ull, std::max<unsigned long long>(200000ull, 1000ull * (unsigned long long)N));
+        p.x_timeout = x_timeout(N);
         hipLaunchKernelGGL(mm_prologue_kernel, dim3(unsigned((h->B + 1 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                            (const int *)nullptr, int(h->B), int(N), (int *)nullptr, p.redo, (int *)nullptr, 0);
         HIP_TRY(hipGetLastError());
         if (h->pair_H > 1) {  // the teams' exchange areas (the float32 team kernels': phase A's rows), zeroed like before a pdfposteriors call
-            const SplitInfo &si = h->fsms[0]->split;
-            for (int s = 0; s < h->pair_H; ++s) {
-                p.sp_base[s] = si.base[s];
-                p.sp_cnt[s] = si.count[s];
-            }
-            p.xbuf = reinterpret_cast<float *>(reinterpret_cast<char *>(p.pair_zmin) + align_up(size_t(h->B) * 6 * 8, 256));
-            p.xps = reinterpret_cast<float *>(reinterpret_cast<char *>(p.xbuf) + ws_x_rows_bytes(h));
-            p.x_slot = 2ll * h->split_s1p;
-            p.x_psn = mm_pair_xps(h->max_P1, h->pair_H);
-            p.x_phase = (long long)(ws_x_rows_bytes(h) / 8);
-            const size_t zn = ws_x_bytes(h) / 16;
-            hipLaunchKernelGGL(mm_zero_kernel, dim3(unsigned(std::min<size_t>(2048, (zn + 255) / 256))), dim3(256), 0, static_cast<hipStream_t>(stream),
-                               reinterpret_cast<char *>(p.xbuf), (unsigned long long)zn);
-            HIP_TRY(hipGetLastError());
+            rc = bind_team_x(h, p, ws, L, false, stream);
+            if (rc) return rc;
             rc = mm_launch_split_export(pair_launch_of(h), p, mode == MODE_ALPHA ? 0 : 1, static_cast<hipStream_t>(stream));
         } else {
             rc = mm_launch_pair_export(pair_launch_of(h), p, mode == MODE_ALPHA ? 0 : 1, static_cast<hipStream_t>(stream));
@@ -3267,7 +3275,7 @@ int mm_viterbi_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const
     if (rc) return rc;
     if (!path || !score) return fail(MM_ERR_INVALID, "mm_viterbi_f32: path/score is NULL");
     if (path_stride_b < N) return fail(MM_ERR_DIM, "mm_viterbi_f32: path_stride_b < N");
-    RunParams p{};
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
     if (!bp) {
         // (int32 rows for the item kernel, or one-byte rows padded to 256 bytes for the row-lane kernels: what this batch runs)
         rc = ensure_ws(h, ws_vit_bytes(h, N), stream);
@@ -3278,25 +3286,12 @@ int mm_viterbi_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const
     } else if (bp_stride_n < h->total_states) {
         return fail(MM_ERR_DIM, "mm_viterbi_f32: bp_stride_n < total states");
     }
-    p.utts = h->d_utts;
-    p.V = V;
-    p.vsb = vsb;
-    p.vsn = vsn;
-    p.lens = lens;
-    p.N = int(N);
-    p.B = int(h->B);
     p.bp = bp;
     p.bp_stride_n = bp_stride_n;
     p.path = path;
     p.path_stride_b = path_stride_b;
     p.score = score;
-#ifdef MM_STAMPS
-    if (!g_dbg) {
-        g_dbg_n = size_t(16) * MM_MAX_WAVES * size_t(h->B);
-        (void)hipMalloc(&g_dbg, sizeof(unsigned long long) * g_dbg_n);
-    }
-    p.dbg = g_dbg;
-#endif
+    bind_stamps(h, p);
     if (h->vit_ok && p.stop_at_len) {  // (internal back-pointers: the compact form)
         VitLaunch vl;
         vl.B = h->B;
