@@ -95,14 +95,20 @@ size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 }  // namespace
 
-// The quad form of one FSM laid out for KQ quads per lane (mm_pack.h), resident on the device.
-struct QuadVariant {  // the quad form of ONE direction of an FSM for one KQ (quads per lane)
+// One hipMalloc, freed with its owner.
+struct HipFree {
+    void operator()(void *p) const { (void)hipFree(p); }
+};
+using DevMem = std::unique_ptr<void, HipFree>;
+
+// The quad form of ONE direction of an FSM laid out for KQ quads per lane (mm_pack.h), resident on the device.
+struct QuadVariant {
     int KQ = 0, dir = 0;
     QuadGraph g;
     std::vector<float> init_f;      // dir 0: alpha_hat in forward numbering
     std::vector<uint16_t> map_bf;   // dir 1: backward position -> forward position (the alpha store's order)
     std::vector<uint16_t> dist;     // internal numbering
-    void *blob = nullptr;
+    DevMem blob;
     QuadDev qdev;
     const float *d_init_f = nullptr;
     const unsigned short *d_map_bf = nullptr;
@@ -114,9 +120,31 @@ struct RowVariant {
     std::vector<float> init;     // forward: alpha_hat by position
     std::vector<uint32_t> ptab;  // wave form: [4 waves][2 segments][4 addresses + info][64 lanes] (wave_pdf_table)
     int pdf_nps = 0;             // ... segments per wave it uses (1 or 2)
-    void *blob = nullptr;
-    std::shared_ptr<void> arena; // ... or a share of one device allocation for many forms (mm_fsm_create_many): freed with its last user
+    std::shared_ptr<void> mem;   // its device image: an allocation of its own, or a share of one allocation for many forms
+                                 // (mm_fsm_create_many: freed with its last user)
     RowDev rdev;
+};
+// The forms of one family: both directions ([direction]), the sets of a team ([direction * H + set]), or one.
+using RowForms = std::unique_ptr<RowVariant[]>;
+
+struct StreamFree {
+    void operator()(StreamForm *s) const { mm_stream_free(s); }
+};
+
+// A form that is built at most once per FSM.  `stage` goes to Tried BEFORE the attempt: a form that did not fit, or whose upload
+// failed, is not built again.  Packed (the wave forms only): `form` is packed on the host -- by a worker thread -- and waits for the
+// calling thread to upload it.
+template <class P>
+struct Once {
+    P form;
+    enum : char { New, Packed, Tried } stage = New;
+    bool ready() const { return stage == Tried && form; }  // complete and on the device
+    bool first(bool *ok) {  // *ok: it is there already; true for the one caller that builds it
+        *ok = ready();
+        if (stage == Tried) return false;
+        stage = Tried;
+        return true;
+    }
 };
 
 struct mm_fsm_s {
@@ -143,25 +171,18 @@ struct mm_fsm_s {
     bool export_ok[2] = {false, false};  // the pruned forms (qmat) give the reference's alpha (0) / beta (1) recursion: see mm_fsm_create
     int depth = 0;         // most arcs from an initial state to any (useful) state
     int64_t nquads[2] = {0, 0};
-    std::map<int, QuadVariant *> variants;  // by 2 * KQ + direction
-    RowVariant *rows[2] = {nullptr, nullptr};  // row-lane forms (built on first use; rows_tried: do not retry)
-    bool rows_tried = false;
-    bool pairs_tried = false;
-    RowVariant *prows[2] = {nullptr, nullptr};  // ... and their pair variants (mm_kernel_pairs.hip)
-    // split pair forms (mm_rows.h make_rows_split): [direction][set], for FSMs beyond the registers / LDS of one compute unit
-    RowVariant *srows[2][MM_SPLIT_HMAX] = {};
+    std::map<int, std::unique_ptr<QuadVariant>> variants;  // by 2 * KQ + direction; never evicted
+    Once<RowForms> rows;    // row-lane forms (mm_kernel_rows.hip)
+    Once<RowForms> prows;   // ... and their pair variants (mm_kernel_pairs.hip)
+    // split pair forms (mm_rows.h make_rows_split) for teams of 2, 4, 8 (split_hidx), for FSMs beyond the registers / LDS of one
+    // compute unit: one team size per FSM -- the first that fits, `split` says which and how
+    Once<RowForms> srows[3];
     SplitInfo split;
-    int split_tried = 0;  // bit H: the split forms for teams of H have been tried
-    RowVariant *wrows[2] = {nullptr, nullptr};  // wave forms (mm_kernel_wave.hip)
-    RowVariant *wpend[2] = {nullptr, nullptr};  // ... packed, not yet uploaded (wave_pack)
-    bool wave_tried = false, wave_packed = false;
-    void *lane_blob = nullptr;                  // lane form (mm_kernel_lane.hip: up to 64 states): the device image, the LaneDev at its start
-    bool lane_tried = false;
-    StreamForm *stream_h[3] = {nullptr, nullptr, nullptr};  // stream forms (mm_stream.hip: graphs beyond the register-resident forms) for teams of 1, 2, 4 workgroups
-    bool stream_tried[3] = {false, false, false};
-    RowVariant *vrow = nullptr;                 // Viterbi form (mm_kernel_vit.hip)
-    bool vit_tried = false;
-    int vit_n4 = 0, vit_n2 = 0;                 // its layout: positions of 4 / of 2 arc slots per wave
+    Once<RowForms> wrows;   // wave forms (mm_kernel_wave.hip; Packed: wave_pack has run, wave_variants has not)
+    Once<DevMem> lane;      // lane form (mm_kernel_lane.hip: up to 64 states): the device image, the LaneDev at its start
+    Once<std::unique_ptr<StreamForm, StreamFree>> stream_h[3];  // stream forms (mm_stream.hip: graphs beyond the register-resident forms) for teams of 1, 2, 4 workgroups
+    Once<RowForms> vrow;    // Viterbi form (mm_kernel_vit.hip)
+    int vit_n4 = 0, vit_n2 = 0;  // its layout: positions of 4 / of 2 arc slots per wave
     // what the generic path (mm_generic.hip: any semiring, float32 or float64) works on: both matrices and alpha_hat as
     // they were handed over, in double, natural units (log weights for Log / Tropical, probabilities for Prob)
     FsmGenView gen;
@@ -171,7 +192,7 @@ struct mm_fsm_s {
     std::vector<float> init;  // dense alpha_hat, engine domain
     std::vector<int32_t> s2p;
     int device = -1;
-    void *dev_blob = nullptr;
+    DevMem dev_blob;
     size_t dev_bytes = 0;
     GraphDev gdev[2];
     const float *d_init = nullptr;
@@ -183,7 +204,7 @@ struct mm_fsm_s {
     std::vector<int64_t> bwd_caller;
     int64_t kphony = -1;
     std::vector<int32_t> init_order;
-    void *arc_blob = nullptr;
+    DevMem arc_blob;
 };
 
 // Test/diagnostic switches.  Read from the environment at mm_batch_create (and once per process for the entries that have no
@@ -856,15 +877,14 @@ static int fsm_create_impl(int semiring, int64_t S1, int64_t nnz, int layout, in
     return MM_OK;
 }
 
-static int upload(const Blob &bl, void **out) {
+// one device allocation (DevMem: freed with its owner) holding a blob
+static int upload(const Blob &bl, DevMem &out) {
     void *blob = nullptr;
     HIP_TRY(hipMalloc(&blob, bl.host.size() ? bl.host.size() : 256));
+    DevMem own(blob);
     hipError_t e = hipMemcpy(blob, bl.host.data(), bl.host.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(blob);
-        return fail(MM_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    *out = blob;
+    if (e != hipSuccess) return fail(MM_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    out = std::move(own);
     return MM_OK;
 }
 
@@ -891,10 +911,9 @@ static int fsm_to_device(mm_fsm_t f) {
         for (int64_t s = 0; s < f->S1; ++s) pdf_rows[size_t(fill[f->s2p[s]]++)] = int32_t(s);
     }
     const size_t o_pptr = bl.add(pdf_ptr), o_prows = bl.add(pdf_rows);
-    void *blob = nullptr;
-    int rc = upload(bl, &blob);
+    int rc = upload(bl, f->dev_blob);
     if (rc) return rc;
-    char *base = static_cast<char *>(blob);
+    char *base = static_cast<char *>(f->dev_blob.get());
     for (int d = 0; d < 2; ++d) {
         f->gdev[d].items = reinterpret_cast<const ItemMeta *>(base + o_items[d]);
         f->gdev[d].rowinfo = reinterpret_cast<const RowInfo *>(base + o_rows[d]);
@@ -907,20 +926,26 @@ static int fsm_to_device(mm_fsm_t f) {
     f->d_s2p = reinterpret_cast<const int *>(base + o_s2p);
     f->d_pdf_ptr = reinterpret_cast<const int *>(base + o_pptr);
     f->d_pdf_rows = reinterpret_cast<const int *>(base + o_prows);
-    f->dev_blob = blob;
     f->dev_bytes = bl.host.size();
     f->device = dev;
     return MM_OK;
+}
+
+// alpha_hat in the order of a form (position -> original state)
+static std::vector<float> init_by(mm_fsm_t f, const std::vector<int32_t> &order) {
+    std::vector<float> v(size_t(f->S1));
+    for (int64_t i = 0; i < f->S1; ++i) v[size_t(i)] = f->init[size_t(order[size_t(i)])];
+    return v;
 }
 
 // build (once per direction and KQ) and upload the quad form of an FSM
 static int quad_variant(mm_fsm_t f, int dir, int KQ, bool verbose, QuadVariant **out) {
     auto it = f->variants.find(2 * KQ + dir);
     if (it != f->variants.end()) {
-        *out = it->second;
+        *out = it->second.get();
         return MM_OK;
     }
-    QuadVariant *v = new QuadVariant();
+    auto v = std::make_unique<QuadVariant>();
     v->KQ = KQ;
     v->dir = dir;
     v->g = make_quads(f->S1, f->qmat[dir].rowptr, f->qmat[dir].col, f->qmat[dir].val, f->s2p, f->P1, dir == 1, KQ);
@@ -929,8 +954,7 @@ static int quad_variant(mm_fsm_t f, int dir, int KQ, bool verbose, QuadVariant *
                 dir, KQ, v->g.quads.size(), (long long)f->qmat[dir].rowptr[f->S1], v->g.conflict_before,
                 v->g.conflict_after);
     if (dir == 0) {
-        v->init_f.resize(f->S1);
-        for (int64_t i = 0; i < f->S1; ++i) v->init_f[i] = f->init[v->g.order[i]];
+        v->init_f = init_by(f, v->g.order);
     } else {
         // the forward numbering does not depend on KQ (rows by decreasing quads): take it from any forward form
         std::vector<int32_t> order_f, pos_f;
@@ -955,12 +979,9 @@ static int quad_variant(mm_fsm_t f, int dir, int KQ, bool verbose, QuadVariant *
     const size_t o_q = bl.add(v->g.quads), o_rec = bl.add(v->g.recs), o_ptr = bl.add(v->g.rowptr);
     const size_t o_col = bl.add(v->g.col), o_w = bl.add(v->g.w), o_pse = bl.add(v->g.pdfstart);
     const size_t o_dist = bl.add(v->dist), o_initf = bl.add(v->init_f), o_map = bl.add(v->map_bf);
-    int rc = upload(bl, &v->blob);
-    if (rc) {
-        delete v;
-        return rc;
-    }
-    char *base = static_cast<char *>(v->blob);
+    int rc = upload(bl, v->blob);
+    if (rc) return rc;
+    char *base = static_cast<char *>(v->blob.get());
     v->qdev.quads = reinterpret_cast<const Quad *>(base + o_q);
     v->qdev.recs = reinterpret_cast<const RowRec *>(base + o_rec);
     v->qdev.rowptr = reinterpret_cast<const int *>(base + o_ptr);
@@ -974,8 +995,8 @@ static int quad_variant(mm_fsm_t f, int dir, int KQ, bool verbose, QuadVariant *
     v->qdev.pad = 0;
     v->d_init_f = reinterpret_cast<const float *>(base + o_initf);
     v->d_map_bf = reinterpret_cast<const unsigned short *>(base + o_map);
-    f->variants[2 * KQ + dir] = v;
-    *out = v;
+    *out = v.get();
+    f->variants[2 * KQ + dir] = std::move(v);
     return MM_OK;
 }
 
@@ -984,21 +1005,21 @@ struct RowBlob {
     Blob bl;
     size_t o_w, o_a, o_s, o_sc, o_ptr, o_col, o_cw, o_pdf, o_pse, o_init, o_ord, o_pt;
 };
-static void row_variant_blob(RowVariant *v, bool pad, RowBlob &rb) {
+static void row_variant_blob(RowVariant &v, bool pad, RowBlob &rb) {
     // (zero rows up to MM_ROW_KA_PAD arc slots: the kernels load their whole register window unconditionally)
     if (pad) {
-        v->g.w.resize(size_t(MM_ROW_KA_PAD) * 64 * v->g.NWC, 0.f);
-        v->g.addr.resize(size_t(MM_ROW_KA_PAD) * 64 * v->g.NWC, 0u);
+        v.g.w.resize(size_t(MM_ROW_KA_PAD) * 64 * v.g.NWC, 0.f);
+        v.g.addr.resize(size_t(MM_ROW_KA_PAD) * 64 * v.g.NWC, 0u);
     }
     Blob &bl = rb.bl;
-    rb.o_w = bl.add(v->g.w), rb.o_a = bl.add(v->g.addr), rb.o_s = bl.add(v->g.slots), rb.o_sc = bl.add(v->g.sched);
-    rb.o_ptr = bl.add(v->g.rowptr), rb.o_col = bl.add(v->g.col), rb.o_cw = bl.add(v->g.cw);
-    rb.o_pdf = bl.add(v->g.rowpdf), rb.o_pse = bl.add(v->g.pdfse), rb.o_init = bl.add(v->init), rb.o_ord = bl.add(v->g.order);
-    rb.o_pt = bl.add(v->ptab);
+    rb.o_w = bl.add(v.g.w), rb.o_a = bl.add(v.g.addr), rb.o_s = bl.add(v.g.slots), rb.o_sc = bl.add(v.g.sched);
+    rb.o_ptr = bl.add(v.g.rowptr), rb.o_col = bl.add(v.g.col), rb.o_cw = bl.add(v.g.cw);
+    rb.o_pdf = bl.add(v.g.rowpdf), rb.o_pse = bl.add(v.g.pdfse), rb.o_init = bl.add(v.init), rb.o_ord = bl.add(v.g.order);
+    rb.o_pt = bl.add(v.ptab);
 }
 // ... and the form's device descriptor once the blob sits at `base`
-static void row_variant_bind(mm_fsm_t f, RowVariant *v, const RowBlob &rb, char *base, float thr) {
-    RowDev &d = v->rdev;
+static void row_variant_bind(mm_fsm_t f, RowVariant &v, const RowBlob &rb, char *base, float thr) {
+    RowDev &d = v.rdev;
     d.w = reinterpret_cast<const float *>(base + rb.o_w);
     d.addr = reinterpret_cast<const unsigned *>(base + rb.o_a);
     d.slots = reinterpret_cast<const unsigned *>(base + rb.o_s);
@@ -1010,22 +1031,60 @@ static void row_variant_bind(mm_fsm_t f, RowVariant *v, const RowBlob &rb, char 
     d.pdfse = reinterpret_cast<const unsigned short *>(base + rb.o_pse);
     d.init = reinterpret_cast<const float *>(base + rb.o_init);
     d.order = reinterpret_cast<const int *>(base + rb.o_ord);
-    d.ptab = v->ptab.empty() ? nullptr : reinterpret_cast<const unsigned *>(base + rb.o_pt);
-    d.KA = v->g.KA;
-    d.NWC = v->g.NWC;
-    d.nslotrows = v->g.nslotrows;
-    d.fpos = v->g.pos[f->S1 - 1];
+    d.ptab = v.ptab.empty() ? nullptr : reinterpret_cast<const unsigned *>(base + rb.o_pt);
+    d.KA = v.g.KA;
+    d.NWC = v.g.NWC;
+    d.nslotrows = v.g.nslotrows;
+    d.fpos = v.g.pos[f->S1 - 1];
     d.rows = int(f->S1);
     d.thr = thr;
 }
-static int upload_row_variant(mm_fsm_t f, RowVariant *v, int dir, float thr, bool pad = true) {
+// a row-lane form to a device allocation of its own
+static int upload_row_variant(mm_fsm_t f, RowVariant &v, float thr, bool pad = true) {
     RowBlob rb;
     row_variant_blob(v, pad, rb);
-    int rc = upload(rb.bl, &v->blob);
+    DevMem mem;
+    int rc = upload(rb.bl, mem);
     if (rc) return rc;
-    row_variant_bind(f, v, rb, static_cast<char *>(v->blob), thr);
-    (void)dir;
+    v.mem = std::move(mem);
+    row_variant_bind(f, v, rb, static_cast<char *>(v.mem.get()), thr);
     return MM_OK;
+}
+
+// ---- pack options: one function per form, for the builders below and for the host-only mm_debug_*_product entries
+
+// the row forms.  windows = false (mm_debug_row_product_ex alone): KA is not rounded up to one of the kernels' register windows
+static RowPackOpts row_pack_opts(bool windows) {
+    const size_t n = sizeof(kRowKA) / sizeof(kRowKA[0]);
+    RowPackOpts opt;
+    opt.rs = MM_ROW_RS;
+    opt.ka_max = kRowKA[n - 1];
+    for (size_t i = 0; i < n && windows; ++i) opt.ka_choices[i] = kRowKA[i];
+    return opt;
+}
+
+// the pair forms of direction dir (same schedule rules as the row forms; 8-byte positions, one copy of the vector, the other
+// direction's numbering in the slot table).  lag = false (mm_debug_row_product_ex alone): the backward agent's group_speed stays 1
+static RowPackOpts pair_pack_opts(const DebugOpts &dbg, int dir, bool lag) {
+    RowPackOpts opt;
+    opt.rs = MM_ROW_RS;
+    opt.ka_max = MM_PAIR_KA;
+    opt.pair = true;
+    opt.pdf_halves = !dbg.no_pdf_halves;
+    for (float &x : opt.group_speed) x = 1.f;  // (the waves of a SIMD progress together: mm_rows.h)
+    // (cost of a finish in arcs: measured with cycle stamps on config 3 -- the backward agent's finishes are the dearer
+    // ones, its phase B is the longest kernel of a call: 8 / 24 against 8 / 8 shortens it by 4 %)
+    if (dbg.finish_cost > 0) opt.finish_cost = dbg.finish_cost;
+    else if (dir == 1) opt.finish_cost = 24;
+    if (dbg.group_speed[0] > 0) {
+        for (int i = 0; i < 4; ++i) opt.group_speed[i] = dbg.group_speed[i];
+    } else if (dir == 1 && lag) {  // (the backward agent's younger waves still lag a little: stamps, -1..2 % with these weights)
+        const float sp[4] = {1.08f, 1.04f, 0.97f, 0.92f};
+        for (int i = 0; i < 4; ++i) opt.group_speed[i] = sp[i];
+    }
+    opt.ka_choices[0] = MM_PAIR_KA;
+    opt.bank_opt = dbg.bankopt ? 1 : 0;
+    return opt;
 }
 
 // options of the split pair forms (mm_rows.h make_rows_split; the kernels: mm_kernel_pairs.hip with H > 1)
@@ -1043,83 +1102,32 @@ static void split_pack_opts(const DebugOpts &dbg, RowPackOpts &opt, RowPackOpts 
     if (dbg.finish_cost <= 0) optb.finish_cost = 24;
 }
 
-// the pair variants of the row-lane forms (same schedule rules; 8-byte positions, one copy of the vector, the other
-// direction's numbering in the slot table)
-static int pair_variants(mm_fsm_t f, const DebugOpts &dbg, bool *ok) {
-    const bool verbose = dbg.verbose;
-    *ok = f->prows[0] && f->prows[1];
-    if (*ok || f->pairs_tried) return MM_OK;
-    f->pairs_tried = true;
-    // (the row forms' conditions, with the pair kernels' own pdf capacity: 251 .. 506 pdfs run their NJ = 8 instances, which the row
-    // kernels do not have)
-    if (f->semiring != MM_LOG || !f->fast_ok || f->P1 > MM_PAIR_P1MAX || (f->S1 + 1) * 4 > MM_ROW_RS) {
-        if (verbose) fprintf(stderr, "[mm] pair form: not tried (semiring %d, fast_ok %d, P1 %d, S1 %lld)\n", f->semiring, int(f->fast_ok), int(f->P1), (long long)f->S1);
-        return MM_OK;
-    }
+// the wave forms.  lean = false (mm_debug_wave_product alone): place, naive_stats and q_positions stay at the packer's defaults
+static RowPackOpts wave_pack_opts(bool lean) {
     RowPackOpts opt;
-    opt.rs = MM_ROW_RS;
-    opt.ka_max = MM_PAIR_KA;
-    opt.pair = true;
-    opt.pdf_halves = !dbg.no_pdf_halves;
-    for (float &x : opt.group_speed) x = 1.f;  // (the waves of a SIMD progress together: mm_rows.h)
-    if (dbg.finish_cost > 0) opt.finish_cost = dbg.finish_cost;
-    if (dbg.group_speed[0] > 0)
-        for (int i = 0; i < 4; ++i) opt.group_speed[i] = dbg.group_speed[i];
-    opt.ka_choices[0] = MM_PAIR_KA;
-    opt.bank_opt = dbg.bankopt ? 1 : 0;
-    RowVariant *rv[2] = {new RowVariant(), new RowVariant()};
-    const std::vector<int32_t> none;
-    // (cost of a finish in arcs: measured with cycle stamps on config 3 -- the backward agent's finishes are the dearer
-    // ones, its phase B is the longest kernel of a call: 8 / 24 against 8 / 8 shortens it by 4 %)
-    RowPackOpts optb = opt;
-    if (dbg.finish_cost <= 0) optb.finish_cost = 24;
-    if (dbg.group_speed[0] <= 0) {  // (the backward agent's younger waves still lag a little: stamps, -1..2 % with these weights)
-        const float sp[4] = {1.08f, 1.04f, 0.97f, 0.92f};
-        for (int i = 0; i < 4; ++i) optb.group_speed[i] = sp[i];
-    }
-    bool fits = make_rows(f->S1, f->qmat[0].rowptr, f->qmat[0].col, f->qmat[0].val, f->s2p, f->P1, false, none, opt, rv[0]->g) &&
-                make_rows(f->S1, f->qmat[1].rowptr, f->qmat[1].col, f->qmat[1].val, f->s2p, f->P1, true, rv[0]->g.pos, optb, rv[1]->g);
-    if (verbose && !fits) fprintf(stderr, "[mm] pair form: the graph does not fit the register windows (KA %d)\n", MM_PAIR_KA);
-    // (arc weights below 2^-60 leave too little of the float range to the values: such graphs run on the other kernels)
-    if (fits && std::min(rv[0]->g.wmin_log2, rv[1]->g.wmin_log2) < -60.f) {
-        if (verbose) fprintf(stderr, "[mm] pair form: arc weights down to 2^%.0f\n", std::min(rv[0]->g.wmin_log2, rv[1]->g.wmin_log2));
-        fits = false;
-    }
-    if (fits) set_partner(rv[0]->g, rv[1]->g.pos);
-    const float thr = fits ? 125.f + std::min(rv[0]->g.wmin_log2, rv[1]->g.wmin_log2) : 0.f;
-    int rc = MM_OK;
-    for (int dir = 0; dir < 2 && fits && !rc; ++dir) {
-        if (verbose)
-            fprintf(stderr, "[mm] pair form dir %d: KA %d, %d compute waves, %d segments, arcs/slots %.3f, cost %d..%d, "
-                            "LDS cycles/gather (bank model) %.2f -> %.2f\n",
-                    dir, rv[dir]->g.KA, rv[dir]->g.NWC, rv[dir]->g.nslotrows - 2, rv[dir]->g.pad_eff, rv[dir]->g.mincost,
-                    rv[dir]->g.maxcost, rv[dir]->g.conflict_before, rv[dir]->g.conflict_after);
-        if (dir == 0) {
-            rv[0]->init.resize(size_t(f->S1));
-            for (int64_t i = 0; i < f->S1; ++i) rv[0]->init[i] = f->init[rv[0]->g.order[i]];
-        }
-        rc = upload_row_variant(f, rv[dir], dir, thr);
-    }
-    if (!fits || rc) {
-        for (RowVariant *x : rv) {
-            if (x->blob) (void)hipFree(x->blob);
-            delete x;
-        }
-        return rc;
-    }
-    f->prows[0] = rv[0];
-    f->prows[1] = rv[1];
-    *ok = true;
-    return MM_OK;
+    opt.rs = MM_WAVE_RS;
+    opt.nwc_max = MM_WAVE_WAVES;
+    opt.ka_max = 16;  // (4 segments of 4 slots per wave)
+    opt.copies = 1;
+    opt.acap_force = 4;
+    opt.seg_stride = 4;
+    opt.log_weights = true;
+    opt.want_partner = true;
+    opt.spread_pdf = true;
+    opt.finish_cost = 4;
+    for (float &x : opt.group_speed) x = 1.f;
+    if (!lean) return opt;
+    // (greedy placement without the local search: the wave kernel is bound by its waves' latency chains, not by LDS cycles --
+    // 0.434 -> 0.437 ms on the WSJ numerators x 128 -- and the search is half the host time of packing a small graph)
+    opt.place = 1;
+    opt.naive_stats = false;
+    opt.q_positions = false;  // (the wave kernel sums the posteriors per pdf through its own tables: wave_pdf_table)
+    if (process_debug_opts().wave_place >= 0) opt.place = process_debug_opts().wave_place;
+    return opt;
 }
 
-// the Viterbi form of a tropical FSM (built once; *ok = false if it does not fit: a row of more than 255 arcs, more than 8
-// segments per wave -- 5760 rows at most)
-static int vit_variant(mm_fsm_t f, const DebugOpts &dbg, bool *ok) {
-    *ok = f->vrow != nullptr;
-    if (*ok || f->vit_tried) return MM_OK;
-    f->vit_tried = true;
-    if (f->semiring != MM_TROPICAL || f->P1 > 256) return MM_OK;
+// the Viterbi form, but for its layout (mix_n4, mix_n2, ka_max: vit_variant tries the kernel's instances)
+static RowPackOpts vit_pack_opts() {
     RowPackOpts opt;
     opt.rs = 65536;
     opt.nwc_max = 15;
@@ -1129,7 +1137,94 @@ static int vit_variant(mm_fsm_t f, const DebugOpts &dbg, bool *ok) {
     opt.keep_order = true;
     opt.finish_cost = 4;
     for (float &x : opt.group_speed) x = 1.f;
-    RowVariant *v = new RowVariant();
+    return opt;
+}
+
+// ---- the builders: each form once per FSM (Once), owned by the builder until it is complete and on the device
+
+// Both directions of a row-lane family from the pruned matrices: the forward form, the backward form in the forward numbering,
+// the forward form's partner words (where the kernels read them), alpha_hat in the forward form's order.  Empty: does not fit.
+static RowForms pack_both(mm_fsm_t f, const RowPackOpts &opt, const RowPackOpts &optb, bool partner) {
+    RowForms rv = std::make_unique<RowVariant[]>(2);
+    const Csr *m = f->qmat;
+    const std::vector<int32_t> none;
+    if (!make_rows(f->S1, m[0].rowptr, m[0].col, m[0].val, f->s2p, f->P1, false, none, opt, rv[0].g) ||
+        !make_rows(f->S1, m[1].rowptr, m[1].col, m[1].val, f->s2p, f->P1, true, rv[0].g.pos, optb, rv[1].g))
+        return nullptr;
+    if (partner) set_partner(rv[0].g, rv[1].g.pos);
+    rv[0].init = init_by(f, rv[0].g.order);
+    return rv;
+}
+// (arc weights below 2^-60 leave too little of the float range to the values of the linear-domain kernels: such graphs run on the
+// other kernels)
+static float wmin_log2(const RowForms &rv) { return std::min(rv[0].g.wmin_log2, rv[1].g.wmin_log2); }
+
+static void say_rows(const char *name, int dir, const RowGraph &g) {
+    fprintf(stderr, "[mm] %s form dir %d: KA %d, %d compute waves, %d segments, arcs/slots %.3f, cost %d..%d, "
+                    "LDS cycles/gather (bank model) %.2f -> %.2f\n",
+            name, dir, g.KA, g.NWC, g.nslotrows - 2, g.pad_eff, g.mincost, g.maxcost, g.conflict_before, g.conflict_after);
+}
+
+// build (once) and upload the row-lane forms of both directions of an FSM; *ok = false if it does not fit them
+static int row_variants(mm_fsm_t f, bool verbose, bool *ok) {
+    if (!f->rows.first(ok)) return MM_OK;
+    if (f->semiring != MM_LOG || !f->fast_ok || f->P1 > 250 || (f->S1 + 1) * 4 > MM_ROW_RS) return MM_OK;
+    RowForms rv = pack_both(f, row_pack_opts(true), row_pack_opts(true), false);
+    if (!rv || !(wmin_log2(rv) >= -60.f)) return MM_OK;
+    for (int dir = 0; dir < 2; ++dir) {
+        const RowGraph &g = rv[dir].g;
+        if (verbose) say_rows("row", dir, g);
+        for (int w = 0; w < g.NWC && verbose; ++w) {
+            const RowSched &sc = g.sched[w];
+            int last = 0;
+            for (int k = 0; k < 64; ++k)
+                if ((sc.endmask >> k) & 1) last = k;
+            fprintf(stderr, "[mm]   wave %2d: %u segments, %d arcs, lg %llx\n", w, sc.nslots & 0xffffu,
+                    2 * (last + 1 - int(sc.nslots >> 16)), (unsigned long long)sc.lg);
+        }
+        int rc = upload_row_variant(f, rv[dir], 125.f + wmin_log2(rv));
+        if (rc) return rc;
+    }
+    f->rows.form = std::move(rv);
+    *ok = true;
+    return MM_OK;
+}
+
+// the pair variants of the row-lane forms (built once; *ok = false if the FSM does not fit them)
+static int pair_variants(mm_fsm_t f, const DebugOpts &dbg, bool *ok) {
+    const bool verbose = dbg.verbose;
+    if (!f->prows.first(ok)) return MM_OK;
+    // (the row forms' conditions, with the pair kernels' own pdf capacity: 251 .. 506 pdfs run their NJ = 8 instances, which the row
+    // kernels do not have)
+    if (f->semiring != MM_LOG || !f->fast_ok || f->P1 > MM_PAIR_P1MAX || (f->S1 + 1) * 4 > MM_ROW_RS) {
+        if (verbose) fprintf(stderr, "[mm] pair form: not tried (semiring %d, fast_ok %d, P1 %d, S1 %lld)\n", f->semiring, int(f->fast_ok), int(f->P1), (long long)f->S1);
+        return MM_OK;
+    }
+    RowForms rv = pack_both(f, pair_pack_opts(dbg, 0, true), pair_pack_opts(dbg, 1, true), true);
+    if (verbose && !rv) fprintf(stderr, "[mm] pair form: the graph does not fit the register windows (KA %d)\n", MM_PAIR_KA);
+    if (rv && wmin_log2(rv) < -60.f) {
+        if (verbose) fprintf(stderr, "[mm] pair form: arc weights down to 2^%.0f\n", wmin_log2(rv));
+        rv.reset();
+    }
+    if (!rv) return MM_OK;
+    for (int dir = 0; dir < 2; ++dir) {
+        if (verbose) say_rows("pair", dir, rv[dir].g);
+        int rc = upload_row_variant(f, rv[dir], 125.f + wmin_log2(rv));
+        if (rc) return rc;
+    }
+    f->prows.form = std::move(rv);
+    *ok = true;
+    return MM_OK;
+}
+
+// the Viterbi form of a tropical FSM (built once; *ok = false if it does not fit: a row of more than 255 arcs, more than 8
+// segments per wave -- 5760 rows at most)
+static int vit_variant(mm_fsm_t f, const DebugOpts &dbg, bool *ok) {
+    if (!f->vrow.first(ok)) return MM_OK;
+    if (f->semiring != MM_TROPICAL || f->P1 > 256) return MM_OK;
+    RowPackOpts opt = vit_pack_opts();
+    RowForms rv = std::make_unique<RowVariant[]>(1);
+    RowVariant &v = rv[0];
     const std::vector<int32_t> none;
     // per wave N4 positions of 4 arc slots and N2 of 2: the cheapest layout the graph fits (the kernel's instances)
     static const int shapes[3][2] = {{1, 5}, {2, 4}, {6, 0}};
@@ -1138,44 +1233,28 @@ static int vit_variant(mm_fsm_t f, const DebugOpts &dbg, bool *ok) {
         opt.mix_n4 = sh[0];
         opt.mix_n2 = sh[1];
         opt.ka_max = 4 * sh[0] + 2 * sh[1];
-        if (make_rows(f->S1, f->mat[0].rowptr, f->mat[0].col, f->mat[0].val, f->s2p, f->P1, false, none, opt, v->g)) {
+        if (make_rows(f->S1, f->mat[0].rowptr, f->mat[0].col, f->mat[0].val, f->s2p, f->P1, false, none, opt, v.g)) {
             fits = true;
             f->vit_n4 = sh[0];
             f->vit_n2 = sh[1];
             break;
         }
     }
-    if (!fits) {
-        delete v;
-        return MM_OK;
-    }
-    v->init.resize(size_t(f->S1));
-    for (int64_t i = 0; i < f->S1; ++i) v->init[i] = f->init[v->g.order[i]];
+    if (!fits) return MM_OK;
+    v.init = init_by(f, v.g.order);
     if (dbg.verbose)
-        fprintf(stderr, "[mm] Viterbi form: %d waves, %d segments, %d x 4 + %d x 2 arc slots per lane, arcs/slots %.3f\n", v->g.NWC,
-                v->g.nslotrows - 2, f->vit_n4, f->vit_n2, v->g.pad_eff);
-    int rc = upload_row_variant(f, v, 0, 0.f, false);
-    if (rc) {
-        delete v;
-        return rc;
-    }
-    f->vrow = v;
+        fprintf(stderr, "[mm] Viterbi form: %d waves, %d segments, %d x 4 + %d x 2 arc slots per lane, arcs/slots %.3f\n", v.g.NWC,
+                v.g.nslotrows - 2, f->vit_n4, f->vit_n2, v.g.pad_eff);
+    int rc = upload_row_variant(f, v, 0.f, false);
+    if (rc) return rc;
+    f->vrow.form = std::move(rv);
     *ok = true;
     return MM_OK;
 }
 
-// The per-pdf sums of the wave kernel (C_hat' * (A .* B), src/inference.jl:155) as packed segments of their own: pdf p
-// with n_p states gets a group of L_p = pow2(ceil(n_p / 4)) adjacent lanes, each of which reads 4 of the states' values
-// (byte addresses relative to the vector u in the numbering of `g`: 4 * position; unused slots read the trash position,
-// which holds zero(K)); the lanes of a group combine by a butterfly.  Groups are placed largest first, so every group
-// starts at a multiple of its size; a segment is 64 lanes.  Segment s runs on compute wave 3 - s % 4 as its pdf segment
-// s / 4.  tab[((w * 2 + j) * 5 + k) * 64 + lane]: k < 4 the addresses, k = 4: 4 * pdf of the group's first lane (the lane
-// that stores; others: the trash slot 4 * P1p) | log2(L) << 16.  Returns the segments per wave (1 or 2), 0 if it does not fit.
 // the lane form of an FSM (mm_kernel_lane.hip): up to 64 real states, every one on a real pdf, up to 64 pdfs; built once
 static int lane_variant(mm_fsm_t f, bool *ok) {
-    *ok = f->lane_blob != nullptr;
-    if (*ok || f->lane_tried) return MM_OK;
-    f->lane_tried = true;
+    if (!f->lane.first(ok)) return MM_OK;
     const int64_t S = f->S1 - 1;
     const int P = f->P1 - 1;
     if (f->semiring != MM_LOG || S < 1 || S > 64 || P < 1 || P > 64) return MM_OK;
@@ -1213,18 +1292,16 @@ static int lane_variant(mm_fsm_t f, bool *ok) {
     std::vector<char> head(align_up(mm_lane_dev_bytes(), 256), 0);
     const size_t o_head = bl.add(head), o_w0 = bl.add(w0), o_w1 = bl.add(w1), o_init = bl.add(init), o_fin = bl.add(fin), o_s2p = bl.add(s2p),
                  o_pp = bl.add(pdf_ptr), o_ps = bl.add(pdf_states);
-    void *blob = nullptr;
-    HIP_TRY(hipMalloc(&blob, bl.host.size()));
-    char *base = static_cast<char *>(blob);
+    void *raw = nullptr;
+    HIP_TRY(hipMalloc(&raw, bl.host.size()));
+    DevMem blob(raw);
+    char *base = static_cast<char *>(raw);
     mm_lane_dev_fill(bl.host.data() + o_head, reinterpret_cast<const double *>(base + o_w0), reinterpret_cast<const double *>(base + o_w1),
                      reinterpret_cast<const float *>(base + o_init), reinterpret_cast<const float *>(base + o_fin),
                      reinterpret_cast<const int *>(base + o_s2p), reinterpret_cast<const int *>(base + o_pp),
                      reinterpret_cast<const int *>(base + o_ps), int(S), P, ident ? 1 : 0);
-    if (hipMemcpy(blob, bl.host.data(), bl.host.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(blob);
-        return fail(MM_ERR_HIP, "lane form: upload failed");
-    }
-    f->lane_blob = blob;
+    if (hipMemcpy(raw, bl.host.data(), bl.host.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(MM_ERR_HIP, "lane form: upload failed");
+    f->lane.form = std::move(blob);
     *ok = true;
     return MM_OK;
 }
@@ -1232,22 +1309,29 @@ static int lane_variant(mm_fsm_t f, bool *ok) {
 // the stream form of an FSM for teams of H workgroups (mm_stream.hip): built once per H; *ok = false if the graph does not fit it
 static int stream_hidx(int H) { return H == 4 ? 2 : (H == 2 ? 1 : 0); }
 static int stream_variant(mm_fsm_t f, int H, bool *ok) {
-    const int k = stream_hidx(H);
-    *ok = f->stream_h[k] != nullptr;
-    if (f->stream_h[k] || f->stream_tried[k]) return MM_OK;
-    f->stream_tried[k] = true;
+    auto &o = f->stream_h[stream_hidx(H)];
+    if (!o.first(ok)) return MM_OK;
     if (f->semiring != MM_LOG) return MM_OK;
     const int64_t *rp[2] = {f->mat[0].rowptr.data(), f->mat[1].rowptr.data()};
     const int32_t *cl[2] = {f->mat[0].col.data(), f->mat[1].col.data()};
     const float *vl[2] = {f->mat[0].val.data(), f->mat[1].val.data()};
     int dev = -1;
     const bool have_dev = hipGetDevice(&dev) == hipSuccess;
-    int rc = mm_stream_build(f->S1, f->P1, rp, cl, vl, f->init.data(), f->s2p.data(), have_dev, H, &f->stream_h[k]);
+    StreamForm *sf = nullptr;
+    int rc = mm_stream_build(f->S1, f->P1, rp, cl, vl, f->init.data(), f->s2p.data(), have_dev, H, &sf);
+    o.form.reset(sf);
     if (rc) return rc;
-    *ok = f->stream_h[k] != nullptr;
+    *ok = sf != nullptr;
     return MM_OK;
 }
 
+// The per-pdf sums of the wave kernel (C_hat' * (A .* B), src/inference.jl:155) as packed segments of their own: pdf p
+// with n_p states gets a group of L_p = pow2(ceil(n_p / 4)) adjacent lanes, each of which reads 4 of the states' values
+// (byte addresses relative to the vector u in the numbering of `g`: 4 * position; unused slots read the trash position,
+// which holds zero(K)); the lanes of a group combine by a butterfly.  Groups are placed largest first, so every group
+// starts at a multiple of its size; a segment is 64 lanes.  Segment s runs on compute wave 3 - s % 4 as its pdf segment
+// s / 4.  tab[((w * 2 + j) * 5 + k) * 64 + lane]: k < 4 the addresses, k = 4: 4 * pdf of the group's first lane (the lane
+// that stores; others: the trash slot 4 * P1p) | log2(L) << 16.  Returns the segments per wave (1 or 2), 0 if it does not fit.
 static int wave_pdf_table(const RowGraph &g, const std::vector<int32_t> &s2p, int64_t S1, int32_t P1, std::vector<uint32_t> &tab) {
     std::vector<std::vector<uint32_t>> src(static_cast<size_t>(P1));
     std::vector<std::pair<int32_t, int32_t>> bypos;  // (position, pdf): a fixed order of the states of a pdf
@@ -1300,81 +1384,46 @@ static int wave_pdf_table(const RowGraph &g, const std::vector<int32_t> &s2p, in
 
 // host part of the wave forms (no device call: mm_batch_create runs it for the FSMs of a batch on several host threads --
 // an LF-MMI step brings a batch of numerator graphs that were never seen before, and packing them one after the other
-// cost 150 ms per 128 graphs against 0.4 ms of kernel time).  Leaves the packed forms in f->wpend, or nothing if the FSM
-// does not fit them.
+// cost 150 ms per 128 graphs against 0.4 ms of kernel time).  Leaves the packed forms with the FSM (stage Packed),
+// or nothing if it does not fit them.
 static void wave_pack(mm_fsm_t f) {
-    if (f->wrows[0] || f->wave_tried || f->wave_packed) return;
-    f->wave_packed = true;
+    Once<RowForms> &o = f->wrows;
+    if (o.stage != o.New) return;
+    o.stage = o.Packed;
     if (f->semiring != MM_LOG || f->P1 > 256 || f->qmat[0].rowptr.empty()) return;
-    RowPackOpts opt;
-    opt.rs = MM_WAVE_RS;
-    opt.nwc_max = MM_WAVE_WAVES;
-    opt.ka_max = 16;  // (4 segments of 4 slots per wave)
-    opt.copies = 1;
-    opt.acap_force = 4;
-    opt.seg_stride = 4;
-    opt.log_weights = true;
-    opt.want_partner = true;
-    opt.spread_pdf = true;
-    opt.finish_cost = 4;
-    for (float &x : opt.group_speed) x = 1.f;
-    // (greedy placement without the local search: the wave kernel is bound by its waves' latency chains, not by LDS cycles --
-    // 0.434 -> 0.437 ms on the WSJ numerators x 128 -- and the search is half the host time of packing a small graph)
-    opt.place = 1;
-    opt.naive_stats = false;
-    opt.q_positions = false;  // (the wave kernel sums the posteriors per pdf through its own tables: wave_pdf_table)
-    if (process_debug_opts().wave_place >= 0) opt.place = process_debug_opts().wave_place;
-    // (owned until they are handed to the FSM: the packer may throw -- an allocation that fails)
-    std::unique_ptr<RowVariant> rv[2] = {std::make_unique<RowVariant>(), std::make_unique<RowVariant>()};
-    const std::vector<int32_t> none;
-    bool fits = make_rows(f->S1, f->qmat[0].rowptr, f->qmat[0].col, f->qmat[0].val, f->s2p, f->P1, false, none, opt, rv[0]->g) &&
-                make_rows(f->S1, f->qmat[1].rowptr, f->qmat[1].col, f->qmat[1].val, f->s2p, f->P1, true, rv[0]->g.pos, opt, rv[1]->g);
-    for (int d = 0; d < 2 && fits; ++d) {
-        rv[d]->pdf_nps = wave_pdf_table(rv[d]->g, f->s2p, f->S1, f->P1, rv[d]->ptab);
-        fits = rv[d]->pdf_nps > 0;
+    const RowPackOpts opt = wave_pack_opts(true);
+    RowForms rv = pack_both(f, opt, opt, true);
+    for (int d = 0; d < 2 && rv; ++d) {
+        rv[d].pdf_nps = wave_pdf_table(rv[d].g, f->s2p, f->S1, f->P1, rv[d].ptab);
+        if (rv[d].pdf_nps <= 0) rv.reset();
     }
-    if (!fits) return;
-    set_partner(rv[0]->g, rv[1]->g.pos);
-    rv[0]->init.resize(size_t(f->S1));
-    for (int64_t i = 0; i < f->S1; ++i) rv[0]->init[i] = f->init[rv[0]->g.order[i]];
-    f->wpend[0] = rv[0].release();
-    f->wpend[1] = rv[1].release();
+    o.form = std::move(rv);
 }
 
 // the wave forms of an FSM (built once; *ok = false if it does not fit them: more than 16 segments of 64 rows, ...)
 static int wave_variants(mm_fsm_t f, const DebugOpts &dbg, bool *ok) {
-    *ok = f->wrows[0] && f->wrows[1];
-    if (*ok || f->wave_tried) return MM_OK;
-    wave_pack(f);
-    f->wave_tried = true;
-    RowVariant *rv[2] = {f->wpend[0], f->wpend[1]};
-    f->wpend[0] = f->wpend[1] = nullptr;
-    if (!rv[0]) return MM_OK;
-    int rc = MM_OK;
-    for (int d = 0; d < 2 && !rc; ++d) {
+    Once<RowForms> &o = f->wrows;
+    wave_pack(f);  // (unless a worker thread has: try_wave, mm_fsm_create_many)
+    if (!o.first(ok)) return MM_OK;
+    RowForms rv = std::move(o.form);
+    if (!rv) return MM_OK;
+    for (int d = 0; d < 2; ++d) {
         if (dbg.verbose)
             fprintf(stderr, "[mm] wave form dir %d: %d segments, arcs/slots %.3f, LDS cycles/gather (bank model) %.2f -> %.2f\n", d,
-                    rv[d]->g.nslotrows - 2, rv[d]->g.pad_eff, rv[d]->g.conflict_before, rv[d]->g.conflict_after);
-        rc = upload_row_variant(f, rv[d], d, 0.f, false);
+                    rv[d].g.nslotrows - 2, rv[d].g.pad_eff, rv[d].g.conflict_before, rv[d].g.conflict_after);
+        int rc = upload_row_variant(f, rv[d], 0.f, false);
+        if (rc) return rc;
     }
-    if (rc) {
-        for (RowVariant *x : rv) {
-            if (x->blob) (void)hipFree(x->blob);
-            delete x;
-        }
-        return rc;
-    }
-    f->wrows[0] = rv[0];
-    f->wrows[1] = rv[1];
+    o.form = std::move(rv);
     *ok = true;
     return MM_OK;
 }
 
-// the split pair forms of an FSM for teams of H workgroups (built once; *ok = false if it does not fit them)
+// the split pair forms of an FSM for teams of H workgroups (built once per H; *ok = false if it does not fit them)
+static int split_hidx(int H) { return H == 8 ? 2 : (H == 4 ? 1 : 0); }
+static const RowVariant &split_row(mm_fsm_t f, int d, int set) { return f->srows[split_hidx(f->split.H)].form[d * f->split.H + set]; }
 static int split_variants(mm_fsm_t f, const DebugOpts &dbg, int H, bool *ok) {
-    *ok = f->split.H == H && f->srows[0][0] != nullptr;
-    if (*ok || f->srows[0][0] != nullptr || (f->split_tried >> H) & 1) return MM_OK;  // (one team size per FSM: the first that fits)
-    f->split_tried |= 1 << H;
+    if (!f->srows[split_hidx(H)].first(ok) || f->split.H) return MM_OK;  // (one team size per FSM: the first that fits)
     if (f->semiring != MM_LOG || !f->fast_ok || mm_pair_nj(f->P1, H) == 0 || H > MM_SPLIT_HMAX) return MM_OK;
     RowPackOpts opt, optb;
     split_pack_opts(dbg, opt, optb, H);
@@ -1394,8 +1443,8 @@ static int split_variants(mm_fsm_t f, const DebugOpts &dbg, int H, bool *ok) {
             return MM_OK;
         }
     const float NINF = -std::numeric_limits<float>::infinity();
-    int rc = MM_OK;
-    for (int d = 0; d < 2 && !rc; ++d) {
+    RowForms rv = std::make_unique<RowVariant[]>(size_t(2 * H));
+    for (int d = 0; d < 2; ++d) {
         // rowpdf / init by position of the TEAM's vector (0xffff / -inf at the alignment padding between the regions)
         std::vector<uint16_t> rowpdf_g(size_t(info.total) + 1, uint16_t(0xffff));
         std::vector<float> init_g(size_t(info.total) + 1, NINF);
@@ -1403,93 +1452,29 @@ static int split_variants(mm_fsm_t f, const DebugOpts &dbg, int H, bool *ok) {
             rowpdf_g[size_t(info.gpos[d][size_t(r)])] = uint16_t(f->s2p[size_t(r)]);
             if (d == 0) init_g[size_t(info.gpos[d][size_t(r)])] = f->init[size_t(r)];
         }
-        for (int h = 0; h < H && !rc; ++h) {
-            RowVariant *v = new RowVariant();
-            v->g = std::move(gs[size_t(d * H + h)]);
+        for (int h = 0; h < H; ++h) {
+            RowVariant &v = rv[size_t(d * H + h)];
+            v.g = std::move(gs[size_t(d * H + h)]);
             if (dbg.verbose)
                 fprintf(stderr, "[mm] split form dir %d set %d/%d: %d rows at %d, KA %d, %d compute waves, %d segments, arcs/slots %.3f, "
                                 "cost %d..%d, LDS cycles/gather (bank model) %.2f -> %.2f\n",
-                        d, h, H, info.count[h], info.base[h], v->g.KA, v->g.NWC, v->g.nslotrows - 2, v->g.pad_eff, v->g.mincost,
-                        v->g.maxcost, v->g.conflict_before, v->g.conflict_after);
-            v->g.rowpdf = rowpdf_g;
-            v->init = init_g;
-            rc = upload_row_variant(f, v, d, 125.f + wmin);
-            v->rdev.rows = info.total;
-            v->rdev.fpos = info.gpos[d][size_t(f->S1 - 1)];
-            f->srows[d][h] = v;
+                        d, h, H, info.count[h], info.base[h], v.g.KA, v.g.NWC, v.g.nslotrows - 2, v.g.pad_eff, v.g.mincost,
+                        v.g.maxcost, v.g.conflict_before, v.g.conflict_after);
+            v.g.rowpdf = rowpdf_g;
+            v.init = init_g;
+            int rc = upload_row_variant(f, v, 125.f + wmin);
+            if (rc) return rc;
+            v.rdev.rows = info.total;  // (the team's vector, not the set's)
+            v.rdev.fpos = info.gpos[d][size_t(f->S1 - 1)];
         }
     }
-    if (rc) {
-        for (int d = 0; d < 2; ++d)
-            for (int h = 0; h < H; ++h)
-                if (f->srows[d][h]) {
-                    if (f->srows[d][h]->blob) (void)hipFree(f->srows[d][h]->blob);
-                    delete f->srows[d][h];
-                    f->srows[d][h] = nullptr;
-                }
-        return rc;
-    }
+    f->srows[split_hidx(H)].form = std::move(rv);
     f->split = std::move(info);
     *ok = true;
     return MM_OK;
 }
 
-// build (once) and upload the row-lane forms of both directions of an FSM; *ok = false if it does not fit them
-static int row_variants(mm_fsm_t f, bool verbose, bool *ok) {
-    *ok = f->rows[0] && f->rows[1];
-    if (f->rows_tried) return MM_OK;
-    f->rows_tried = true;
-    if (f->semiring != MM_LOG || !f->fast_ok || f->P1 > 250 || (f->S1 + 1) * 4 > MM_ROW_RS) return MM_OK;
-    RowPackOpts opt;
-    opt.rs = MM_ROW_RS;
-    opt.ka_max = kRowKA[sizeof(kRowKA) / sizeof(kRowKA[0]) - 1];
-    for (size_t i = 0; i < sizeof(kRowKA) / sizeof(kRowKA[0]); ++i) opt.ka_choices[i] = kRowKA[i];
-    RowVariant *rv[2] = {new RowVariant(), new RowVariant()};
-    const std::vector<int32_t> none;
-    // (arc weights below 2^-60 leave too little of the float range to the values: such graphs run on the other kernels)
-    bool fits = make_rows(f->S1, f->qmat[0].rowptr, f->qmat[0].col, f->qmat[0].val, f->s2p, f->P1, false, none, opt, rv[0]->g) &&
-                make_rows(f->S1, f->qmat[1].rowptr, f->qmat[1].col, f->qmat[1].val, f->s2p, f->P1, true, rv[0]->g.pos, opt, rv[1]->g);
-    fits = fits && std::min(rv[0]->g.wmin_log2, rv[1]->g.wmin_log2) >= -60.f;
-    if (!fits) {
-        delete rv[0];
-        delete rv[1];
-        return MM_OK;
-    }
-    for (int dir = 0; dir < 2; ++dir) {
-        RowVariant *v = rv[dir];
-        if (verbose)
-            fprintf(stderr, "[mm] row form dir %d: KA %d, %d compute waves, %d segments, arcs/slots %.3f, cost %d..%d, "
-                            "LDS cycles/gather (bank model) %.2f -> %.2f\n",
-                    dir, v->g.KA, v->g.NWC, v->g.nslotrows - 2, v->g.pad_eff, v->g.mincost, v->g.maxcost, v->g.conflict_before,
-                    v->g.conflict_after);
-        if (verbose)
-            for (int w = 0; w < v->g.NWC; ++w) {
-                const RowSched &sc = v->g.sched[w];
-                int last = 0;
-                for (int k = 0; k < 64; ++k)
-                    if ((sc.endmask >> k) & 1) last = k;
-                fprintf(stderr, "[mm]   wave %2d: %u segments, %d arcs, lg %llx\n", w, sc.nslots & 0xffffu,
-                        2 * (last + 1 - int(sc.nslots >> 16)), (unsigned long long)sc.lg);
-            }
-        if (dir == 0) {
-            v->init.resize(f->S1);
-            for (int64_t i = 0; i < f->S1; ++i) v->init[i] = f->init[v->g.order[i]];
-        }
-        int rc = upload_row_variant(f, v, dir, 125.f + std::min(rv[0]->g.wmin_log2, rv[1]->g.wmin_log2));
-        if (rc) {
-            for (RowVariant *x : rv) {
-                if (x->blob) (void)hipFree(x->blob);
-                delete x;
-            }
-            return rc;
-        }
-    }
-    f->rows[0] = rv[0];
-    f->rows[1] = rv[1];
-    *ok = true;
-    return MM_OK;
-}
-
+// (the forms free themselves with the FSM)
 int mm_fsm_destroy(mm_fsm_t f) {
     if (!f) return MM_OK;
     if (f->log_twin) (void)mm_fsm_destroy(f->log_twin);
@@ -1498,22 +1483,6 @@ int mm_fsm_destroy(mm_fsm_t f) {
             mm_generic_free(d);
             d = nullptr;
         }
-    if (f->dev_blob) (void)hipFree(f->dev_blob);
-    if (f->lane_blob) (void)hipFree(f->lane_blob);
-    if (f->arc_blob) (void)hipFree(f->arc_blob);
-    for (StreamForm *sf : f->stream_h) mm_stream_free(sf);
-    for (auto &kv : f->variants) {
-        if (kv.second->blob) (void)hipFree(kv.second->blob);
-        delete kv.second;
-    }
-    auto drop = [](RowVariant *rv) {
-        if (!rv) return;
-        if (rv->blob) (void)hipFree(rv->blob);
-        delete rv;
-    };
-    for (RowVariant *rv : {f->rows[0], f->rows[1], f->prows[0], f->prows[1], f->wrows[0], f->wrows[1], f->wpend[0], f->wpend[1], f->vrow}) drop(rv);
-    for (int d = 0; d < 2; ++d)
-        for (int hh = 0; hh < MM_SPLIT_HMAX; ++hh) drop(f->srows[d][hh]);  // (teams of up to MM_SPLIT_HMAX sets)
     delete f;
     return MM_OK;
 }
@@ -1617,17 +1586,13 @@ int mm_debug_row_product_ex(mm_fsm_t f, int direction, int flags, const float *i
     if (!f || !in || !out || direction < 0 || direction > 1 || flags < 0 || flags > 31)
         return fail(MM_ERR_INVALID, "mm_debug_row_product: bad argument");
     if (f->semiring != MM_LOG) return fail(MM_ERR_INVALID, "mm_debug_row_product: log-semiring FSMs only");
-    RowPackOpts opt;
-    opt.rs = MM_ROW_RS;
-    opt.ka_max = kRowKA[sizeof(kRowKA) / sizeof(kRowKA[0]) - 1];
-    if (flags & 1) {  // the pair form as pair_variants() builds it
-        opt.pair = true;
-        opt.pdf_halves = !process_debug_opts().no_pdf_halves;
-        opt.ka_max = MM_PAIR_KA;
-        opt.ka_choices[0] = MM_PAIR_KA;
-        for (float &x : opt.group_speed) x = 1.f;
-        if (direction == 1) opt.finish_cost = 24;
-    }
+    // The options of the forms that ship (row_pack_opts, pair_pack_opts), but: the matrices are mat[], not the pruned qmat[]; of the
+    // debug switches only the process's MM_NO_PDF_HALVES is read; the row form's KA is not rounded to a register window and the pair
+    // form's backward group_speed stays 1; the forward numbering of a backward pair product is packed with the backward options
+    // (finish_cost 24); copies, copy_perm and bank_opt are the caller's flags.
+    DebugOpts dbg;
+    dbg.no_pdf_halves = process_debug_opts().no_pdf_halves;
+    RowPackOpts opt = (flags & 1) ? pair_pack_opts(dbg, direction, false) : row_pack_opts(false);
     opt.copies = (flags >> 1) & 3;
     opt.copy_perm = (flags & 8) != 0;
     opt.bank_opt = (flags & 16) ? 1 : 0;
@@ -1677,7 +1642,7 @@ int mm_debug_stream_team_product(mm_fsm_t f, int H, int direction, const float *
         int rc = stream_variant(f, H, &ok);
         if (rc) return rc;
         if (!ok) return fail(MM_ERR_UNSUPPORTED, "mm_debug_stream_team_product: the FSM does not fit the stream form");
-        mm_stream_eval(f->stream_h[stream_hidx(H)], direction, in, out, stats);
+        mm_stream_eval(f->stream_h[stream_hidx(H)].form.get(), direction, in, out, stats);
         return int(MM_OK);
     });
 }
@@ -1685,18 +1650,8 @@ int mm_debug_stream_team_product(mm_fsm_t f, int H, int direction, const float *
 int mm_debug_wave_product(mm_fsm_t f, int direction, const float *in, float *out, double stats[4]) {
     if (!f || !in || !out || direction < 0 || direction > 1) return fail(MM_ERR_INVALID, "mm_debug_wave_product: bad argument");
     if (f->semiring != MM_LOG) return fail(MM_ERR_INVALID, "mm_debug_wave_product: log-semiring FSMs only");
-    RowPackOpts opt;
-    opt.rs = MM_WAVE_RS;
-    opt.nwc_max = MM_WAVE_WAVES;
-    opt.ka_max = 16;
-    opt.finish_cost = 4;
-    opt.copies = 1;
-    opt.acap_force = 4;
-    opt.seg_stride = 4;
-    opt.log_weights = true;
-    opt.want_partner = true;
-    opt.spread_pdf = true;
-    for (float &x : opt.group_speed) x = 1.f;
+    // (the options of wave_pack but for place, naive_stats, q_positions -- the packer's defaults here; mat[], not the pruned qmat[])
+    const RowPackOpts opt = wave_pack_opts(false);
     RowGraph gf, g;
     const std::vector<int32_t> none;
     if (!make_rows(f->S1, f->mat[0].rowptr, f->mat[0].col, f->mat[0].val, f->s2p, f->P1, false, none, opt, gf) ||
@@ -1722,7 +1677,7 @@ int mm_debug_split_product(mm_fsm_t f, int H, int direction, const float *in, fl
         return fail(MM_ERR_INVALID, "mm_debug_split_product: bad argument");
     if (f->semiring != MM_LOG) return fail(MM_ERR_INVALID, "mm_debug_split_product: log-semiring FSMs only");
     RowPackOpts opt, optb;
-    split_pack_opts(DebugOpts(), opt, optb, H);
+    split_pack_opts(DebugOpts(), opt, optb, H);  // (no debug switch is read; mat[], not the pruned qmat[])
     std::vector<RowGraph> gs;
     SplitInfo info;
     if (!make_rows_split(H, f->S1, f->mat[0].rowptr, f->mat[0].col, f->mat[0].val, f->mat[1].rowptr, f->mat[1].col,
@@ -1824,12 +1779,12 @@ static int fsm_create_many_impl(int64_t n, int semiring, int layout, int index_b
             if (f->semiring == MM_LOG && f->P1 <= 250 && f->S1 <= 1023 && f->qmat[0].rowptr[size_t(f->S1)] <= 16 * 64 * 4) {
                 wave_pack(f);
                 ns_pack += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tb).count();
-                if (f->wpend[0] && f->wpend[1]) {
+                if (f->wrows.form) {
                     size_t tot = 0;
                     for (int d = 0; d < 2; ++d) {
                         RowBlob rb;
                         rb.bl.dry = true;
-                        row_variant_blob(f->wpend[d], false, rb);
+                        row_variant_blob(f->wrows.form[d], false, rb);
                         tot += align_up(rb.bl.size(), 256);
                     }
                     bytes[size_t(i)] = tot;
@@ -1870,7 +1825,7 @@ static int fsm_create_many_impl(int64_t n, int semiring, int layout, int index_b
     }
     void *dev = nullptr;
     if (hipMalloc(&dev, total) != hipSuccess) return undo(MM_ERR_HIP, "mm_fsm_create_many: device allocation failed");
-    std::shared_ptr<void> arena(dev, [](void *q) { (void)hipFree(q); });
+    std::shared_ptr<void> arena(dev, HipFree());
     lap("arena allocated");
     std::lock_guard<std::mutex> guard(g_stage_lock);
     if (g_stage_bytes < total) {
@@ -1891,7 +1846,7 @@ static int fsm_create_many_impl(int64_t n, int semiring, int layout, int index_b
         for (int d = 0; d < 2; ++d) {
             RowBlob &rb = rbs[size_t(i) * 2 + d];
             rb.bl.ext = g_stage + o;
-            row_variant_blob(f->wpend[d], false, rb);
+            row_variant_blob(f->wrows.form[d], false, rb);
             o += align_up(rb.bl.size(), 256);
         }
     });
@@ -1903,15 +1858,13 @@ static int fsm_create_many_impl(int64_t n, int semiring, int layout, int index_b
         mm_fsm_t f = out[i];
         size_t o = off[size_t(i)];
         for (int d = 0; d < 2; ++d) {
-            RowVariant *rv = f->wpend[d];
+            RowVariant &rv = f->wrows.form[d];
             const RowBlob &rb = rbs[size_t(i) * 2 + d];
-            rv->arena = arena;
+            rv.mem = arena;
             row_variant_bind(f, rv, rb, static_cast<char *>(dev) + o, 0.f);
             o += align_up(rb.bl.size(), 256);
-            f->wrows[d] = rv;
-            f->wpend[d] = nullptr;
         }
-        f->wave_tried = true;
+        f->wrows.stage = f->wrows.Tried;
     }
     return MM_OK;
 }
@@ -1936,7 +1889,7 @@ static int try_wave(mm_batch_t h, const mm_fsm_t *fsms, bool *ok) {
     {   // pack the forms of the FSMs that are new, on the host's cores
         std::vector<mm_fsm_t> todo;
         for (int64_t b = 0; b < B; ++b)
-            if (!fsms[b]->wrows[0] && !fsms[b]->wave_tried && !fsms[b]->wave_packed &&
+            if (fsms[b]->wrows.stage == fsms[b]->wrows.New &&
                 std::find(todo.begin(), todo.end(), fsms[b]) == todo.end())
                 todo.push_back(fsms[b]);
         const size_t nthr = std::min<size_t>({todo.size() / 4, size_t(std::max(1u, std::thread::hardware_concurrency())), size_t(16)});
@@ -1951,7 +1904,7 @@ static int try_wave(mm_batch_t h, const mm_fsm_t *fsms, bool *ok) {
                         try {
                             wave_pack(todo[i]);
                         } catch (...) {
-                            todo[i]->wave_packed = false;
+                            todo[i]->wrows.stage = todo[i]->wrows.New;
                         }
                     }
                 });
@@ -1965,8 +1918,8 @@ static int try_wave(mm_batch_t h, const mm_fsm_t *fsms, bool *ok) {
         *ok = fit;
         // (segments of a wave's registers: the state segments, and twice the pdf segments -- the kernel has NSEG / 2 of those)
         if (fit)
-            h->wave_nseg = std::max({h->wave_nseg, std::max(fsms[b]->wrows[0]->g.KA, fsms[b]->wrows[1]->g.KA) / 4,
-                                     2 * std::max(fsms[b]->wrows[0]->pdf_nps, fsms[b]->wrows[1]->pdf_nps)});
+            h->wave_nseg = std::max({h->wave_nseg, std::max(fsms[b]->wrows.form[0].g.KA, fsms[b]->wrows.form[1].g.KA) / 4,
+                                     2 * std::max(fsms[b]->wrows.form[0].pdf_nps, fsms[b]->wrows.form[1].pdf_nps)});
     }
     return MM_OK;
 }
@@ -2049,9 +2002,9 @@ static int pick_family(mm_batch_t h, const mm_fsm_t *fsms, const int64_t nq_max[
         if (rc) return rc;
         pairs = ok;
         if (ok) {
-            h->pair_ka = std::max(fsms[0]->prows[0]->g.KA, fsms[0]->prows[1]->g.KA);
-            h->pair_nwc = std::max(fsms[0]->prows[0]->g.NWC, fsms[0]->prows[1]->g.NWC);
-            h->pair_slotrows = std::max(fsms[0]->prows[0]->g.nslotrows, fsms[0]->prows[1]->g.nslotrows);
+            h->pair_ka = std::max(fsms[0]->prows.form[0].g.KA, fsms[0]->prows.form[1].g.KA);
+            h->pair_nwc = std::max(fsms[0]->prows.form[0].g.NWC, fsms[0]->prows.form[1].g.NWC);
+            h->pair_slotrows = std::max(fsms[0]->prows.form[0].g.nslotrows, fsms[0]->prows.form[1].g.nslotrows);
             pairs = h->pair_ka <= MM_PAIR_KA && mm_pair_lds_bytes(1, h->pair_slotrows, h->max_P1) <= 160 * 1024;
         }
     }
@@ -2073,9 +2026,9 @@ static int pick_family(mm_batch_t h, const mm_fsm_t *fsms, const int64_t nq_max[
             h->pair_slotrows = 0;
             for (int d = 0; d < 2; ++d)
                 for (int s = 0; s < h->pair_H; ++s) {
-                    h->pair_ka = std::max(h->pair_ka, f0->srows[d][s]->g.KA);
-                    h->pair_nwc = std::max(h->pair_nwc, f0->srows[d][s]->g.NWC);
-                    h->pair_slotrows = std::max(h->pair_slotrows, f0->srows[d][s]->g.nslotrows);
+                    h->pair_ka = std::max(h->pair_ka, split_row(f0, d, s).g.KA);
+                    h->pair_nwc = std::max(h->pair_nwc, split_row(f0, d, s).g.NWC);
+                    h->pair_slotrows = std::max(h->pair_slotrows, split_row(f0, d, s).g.nslotrows);
                 }
             h->split_s1p = (f0->split.total + 2 + 3) & ~3;
             const size_t lds = mm_split_lds_bytes(h->pair_H, 1, h->pair_slotrows, h->max_P1);
@@ -2107,7 +2060,7 @@ static int pick_family(mm_batch_t h, const mm_fsm_t *fsms, const int64_t nq_max[
             bool ok = false;
             int rc = stream_variant(fsms[b], h->stream_H, &ok);
             if (rc) return rc;
-            stream = ok && mm_stream_dev(fsms[b]->stream_h[stream_hidx(h->stream_H)]) != nullptr;
+            stream = ok && mm_stream_dev(fsms[b]->stream_h[stream_hidx(h->stream_H)].form.get()) != nullptr;
         }
         h->stream_S1 = int(s1_max);
     }
@@ -2215,7 +2168,7 @@ static int batch_create_impl(const mm_fsm_t *fsms, int64_t B, mm_batch_t *out) {
                     h->vit_n2 = fsms[b]->vit_n2;
                 }
                 h->vit_ok = fsms[b]->vit_n4 == h->vit_n4 && fsms[b]->vit_n2 == h->vit_n2;
-                h->vit_arcs = std::max(h->vit_arcs, int(fsms[b]->vrow->g.col.size()));
+                h->vit_arcs = std::max(h->vit_arcs, int(fsms[b]->vrow.form[0].g.col.size()));
                 h->vit_ok = h->vit_ok && size_t(fsms[b]->S1p) * 4 <= 24576;  // (the kernel's state vectors: mm_vit_tu.hip)
             }
         }
@@ -2240,22 +2193,22 @@ static int batch_create_impl(const mm_fsm_t *fsms, int64_t B, mm_batch_t *out) {
             u.init_f = qv[0]->d_init_f;
             u.map_bf = qv[1]->d_map_bf;
         }
-        if (h->fb == Fb::Lane) u.lane = static_cast<const LaneDev *>(f->lane_blob);
-        if (h->fb == Fb::Stream) u.stream = mm_stream_dev(f->stream_h[stream_hidx(h->stream_H)]);
-        if (h->vit_ok) u.rv = f->vrow->rdev;
+        if (h->fb == Fb::Lane) u.lane = static_cast<const LaneDev *>(f->lane.form.get());
+        if (h->fb == Fb::Stream) u.stream = mm_stream_dev(f->stream_h[stream_hidx(h->stream_H)].form.get());
+        if (h->vit_ok) u.rv = f->vrow.form[0].rdev;
         if (h->fb == Fb::Wave || h->lane_redo_wave)
-            for (int d = 0; d < 2; ++d) u.rw[d] = f->wrows[d]->rdev;
+            for (int d = 0; d < 2; ++d) u.rw[d] = f->wrows.form[d].rdev;
         if (h->fb == Fb::Pairs)
-            for (int d = 0; d < 2; ++d) u.rp[d] = f->prows[d]->rdev;
+            for (int d = 0; d < 2; ++d) u.rp[d] = f->prows.form[d].rdev;
         if (h->fb == Fb::Split)
             for (int d = 0; d < 2; ++d)
-                for (int s = 0; s < h->pair_H; ++s) u.rps[d][s] = f->srows[d][s]->rdev;
+                for (int s = 0; s < h->pair_H; ++s) u.rps[d][s] = split_row(f, d, s).rdev;
         if (rows)
             for (int d = 0; d < 2; ++d) {
-                u.r[d] = f->rows[d]->rdev;
-                h->row_ka[d] = std::max(h->row_ka[d], f->rows[d]->g.KA);
-                h->row_nwc[d] = std::max(h->row_nwc[d], f->rows[d]->g.NWC);
-                h->row_slotrows[d] = std::max(h->row_slotrows[d], f->rows[d]->g.nslotrows);
+                u.r[d] = f->rows.form[d].rdev;
+                h->row_ka[d] = std::max(h->row_ka[d], f->rows.form[d].g.KA);
+                h->row_nwc[d] = std::max(h->row_nwc[d], f->rows.form[d].g.NWC);
+                h->row_slotrows[d] = std::max(h->row_slotrows[d], f->rows.form[d].g.nslotrows);
             }
         u.init = f->d_init;
         u.s2p = f->d_s2p;
@@ -2982,15 +2935,13 @@ static int ensure_arc_forms(mm_batch_t h, void *stream) {
             Blob bl;
             (void)bl.add(k2slot);  // (at 0)
             (void)bl.add(f->init_order);
-            void *blob = nullptr;
-            const int rc = upload(bl, &blob);
+            const int rc = upload(bl, f->arc_blob);
             if (rc) return rc;
-            f->arc_blob = blob;
         }
         ArcDev &a = arcs[size_t(b)];
         const size_t o_i = align_up(size_t(f->nnz) * 4, 256);  // (where Blob::add put init_order, behind k2slot)
-        a.k2slot = static_cast<const int *>(f->arc_blob);
-        a.init_states = reinterpret_cast<const int *>(static_cast<const char *>(f->arc_blob) + o_i);
+        a.k2slot = static_cast<const int *>(f->arc_blob.get());
+        a.init_states = reinterpret_cast<const int *>(static_cast<const char *>(f->arc_blob.get()) + o_i);
         a.slot_off = slots;
         a.nnz = int(f->nnz);
         a.n_init = int(f->init_order.size());
