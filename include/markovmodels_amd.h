@@ -113,7 +113,8 @@ int64_t mm_batch_total_states(mm_batch_t batch);
 /* Names of the kernels a run entry launches for this batch (the engine picks them from the graphs' sizes and
  * shapes): entry 0 = mm_pdfposteriors_f32, 1 = mm_viterbi_f32, 2 = what the last mm_pdfposteriors_ex call on the batch launched
  * (the recursion kernel; for ProbSemiring FSMs in float32 with general state maps, the emission GEMM C_hat * V_hat on the matrix
- * cores before it), 3 = mm_alpharecursion_f32 / mm_betarecursion_f32, 4 = mm_arcposteriors_f32 (log batches only).
+ * cores before it), 3 = mm_alpharecursion_f32 / mm_betarecursion_f32, 4 = mm_arcposteriors_f32 (log batches only),
+ * 5 = mm_samplepaths_f32 (log batches only).
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -174,6 +175,42 @@ int mm_pdfposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, i
  * synchronisation; it can be captured in a hipGraph once a first call has made the batch's arc forms and sized the workspace. */
 int mm_arcposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
                          float *counts, int64_t c_stride_b, float *init_counts, int64_t i_stride_b, float *ttl, void *stream);
+
+/* Posterior path sampling (forward filtering, backward sampling): nsamples state sequences per utterance, drawn from the
+ * posterior over complete paths
+ *   P(s_1 .. s_len | V) = alpha_hat(s_1) * prod_n lhs_n(s_n) * prod_n T_hat(s_n, s_n+1) * omega(s_len) / Z_b
+ * (expand() semantics as mm_pdfposteriors_f32; omega = the column of the phony final state).  The forward half of the item kernel
+ * runs ONCE per call; a second kernel walks the frames backwards and draws, given the state j of frame n + 1, the state i of
+ * frame n with probability proportional to alpha_n(i) * T_hat_ij.
+ *   V, lens, N   as mm_pdfposteriors_f32
+ *   nsamples     K >= 1 samples per utterance
+ *   seed         any value: the key of the generator (see below)
+ *   paths        device int32, out: the state (0-based, the caller's numbering) of sample k of utterance b at frame n at
+ *                paths[b*path_stride_b + k*path_stride_k + n] for n < len_b, -1 for len_b <= n < N -- the convention of
+ *                mm_viterbi_f32's path; the phony final state never appears.  An utterance without an accepting path
+ *                (len_b = 0 included): all -1.  NULL: MM_ERR_INVALID; path_stride_k < N or
+ *                path_stride_b < nsamples*path_stride_k: MM_ERR_DIM
+ *   logprob      device float, out (NULL: not computed): logprob[b*lp_stride_b + k] = the natural-log posterior probability of
+ *                the sampled STATE SEQUENCE, log alpha_hat(s_1) + sum log lhs + sum log T_hat + log omega(s_len) - log Z_b,
+ *                accumulated in float64 along the chain; -inf for an utterance without a path.  Parallel entries of T_hat between
+ *                the same two states count as ONE transition whose weight is their sum: both the draw and the reported
+ *                probability are over state sequences.  lp_stride_b < nsamples: MM_ERR_DIM
+ *   ttl          device float[B], out (NULL: not written): log Z_b, the value mm_pdfposteriors_f32 returns; -inf without a path
+ * The random numbers.  The result is a function of (graphs, V, lens, N, seed) and of the indices (b, k) alone -- not of nsamples,
+ * of the launch geometry, of the stream or of earlier calls: the first K' samples of a call with K > K' are the samples of a call
+ * with K', and a repeated call returns the same bits.  The generator is counter based and has no state on the device:
+ * Philox-4x32-10 with the 64 bits of `seed` as its key and (b, k, frame, chunk of 64 in-arcs) as its counter, its words turned
+ * into uniforms strictly inside (0, 1).  The streams of different (b, k) are independent, and the key is the POSITION b in the
+ * batch, not the utterance's content: two utterances with the same graph and emissions receive different samples, and an
+ * utterance moved to another position of the batch receives other samples of the same distribution.  A state of probability zero
+ * (alpha = 0, or an emission of -inf) is never drawn, whatever the uniform.
+ * MM_LOG batches only: Tropical and ProbSemiring batches return MM_ERR_UNSUPPORTED.  Runs on every log batch (any size) whatever
+ * kernels mm_pdfposteriors_f32 picks for it.  Stream contract of mm_arcposteriors_f32: launches on `stream` only, no host
+ * synchronisation; it can be captured in a hipGraph once a first call has put the batch's item and sampling forms on the device
+ * and sized the workspace (a capture before that returns MM_ERR_INVALID). */
+int mm_samplepaths_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                       int64_t nsamples, int64_t seed, int32_t *paths, int64_t path_stride_b, int64_t path_stride_k,
+                       float *logprob, int64_t lp_stride_b, float *ttl, void *stream);
 
 /* alpha-recursion(alpha_hat, T_hat', C_hat*V_hat) (src/inference.jl:62-74) as
  * called from pdfposteriors (:150-152): out is the reference's state_A, a

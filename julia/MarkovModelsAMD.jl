@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, samplepaths, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -238,6 +238,33 @@ function arcposteriors(b::ROCBatch, V::ROCArray{Float32,3}, fsms::AbstractVector
     mats = [SparseMatrixCSC(size(T, 1), size(T, 2), copy(T.colptr), copy(T.rowval), c[1:nnz(T), u]) for (u, T) in enumerate(Ts)]
     inits = [SparseVector(length(a), copy(SparseArrays.nonzeroinds(a)), iv[1:nnz(a), u]) for (u, a) in enumerate(αs)]
     mats, inits, Array(ttl)
+end
+
+"""
+    samplepaths(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing; nsamples = 1, seed = 0) -> (paths, logprob, ttl)
+
+State sequences drawn from the posterior over complete paths (mm_samplepaths_f32 in the header: forward filtering, backward
+sampling) of a log-semiring batch.  `V` and `lens` as for `pdfposteriors`.  Returns `paths`, an N × nsamples × B `Array{Int32}`
+of 1-based states (0 beyond an utterance's length, and everywhere for an utterance without a path), the natural-log posterior
+probability of every sampled sequence (nsamples × B) and ttl = log Z.  A sample depends on the graphs, `V`, `lens`, `seed` and
+its indices (utterance, sample) alone: the same `seed` gives the same samples, and the first K′ samples of a call with
+`nsamples = K` are the samples of a call with `nsamples = K′`.
+"""
+function samplepaths(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing; nsamples::Integer = 1, seed::Integer = 0)
+    P, N, B = size(V)
+    P == b.P || throw(DimensionMismatch("V has $P pdfs, the FSMs $(b.P)"))
+    K = Int64(nsamples)
+    K >= 1 || throw(ArgumentError("nsamples must be at least 1"))
+    paths = ROCArray{Int32}(undef, N, K, B)
+    logprob = ROCArray{Float32}(undef, K, B)
+    ttl = ROCArray{Float32}(undef, B)
+    lp = lens === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(lens))
+    check(ccall((:mm_samplepaths_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Int64, Int64, Ptr{Int32}, Int64, Int64,
+         Ptr{Float32}, Int64, Ptr{Float32}, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, lp, N, K, seed % Int64, pointer(paths), N * K, N, pointer(logprob), K, pointer(ttl),
+        AMDGPU.stream().stream))
+    Array(paths) .+ Int32(1), Array(logprob), Array(ttl)      # (the library's states are 0-based, -1 = no state)
 end
 
 """

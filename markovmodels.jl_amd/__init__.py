@@ -2,7 +2,7 @@
 
 Host-side mirror of the reference's hot-path interface (src/MarkovModels.jl:14-45:
 FSM, nstates, rawunion, CompiledFSM, batch, compile, expand, alpha-recursion,
-beta-recursion, pdfposteriors, arcposteriors, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
+beta-recursion, pdfposteriors, arcposteriors, samplepaths, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
 The directory name contains a dot, so load it with
 ``__graft_entry__.load_package()`` (importlib) rather than a plain import.
 """
@@ -23,6 +23,7 @@ from .inference import (  # noqa: F401
     expand,
     maxstateposteriors,
     pdfposteriors,
+    samplepaths,
     totalcumsum,
     totalsum,
     totalweightsum,

@@ -205,6 +205,10 @@ struct mm_fsm_s {
     int64_t kphony = -1;
     std::vector<int32_t> init_order;
     DevMem arc_blob;
+    // path sampling (MM_LOG): the sampling form -- T_hat' by destination as SampleRec lists, parallel entries merged -- made on the
+    // first mm_samplepaths_f32 call that needs it; the list of the phony final state (the omega column)
+    DevMem samp_blob;
+    int samp_fin_start = 0, samp_fin_deg = 0;
 };
 
 // Test/diagnostic switches.  Read from the environment at mm_batch_create (and once per process for the entries that have no
@@ -231,6 +235,7 @@ struct DebugOpts {
     int split_q10 = 0;              // MM_SPLIT_Q10: where the pair kernels cut the frames between the agents (1024ths; 0: the engine's choice)
     int x_sleep = 8;                // MM_SPLIT_SLEEP: split kernels, 64-clock units the exchange wave sleeps before a step's first poll
     float group_speed[4] = {0, 0, 0, 0};  // MM_GROUP_SPEED=a,b,c,d
+    bool sample_nostage = false;    // MM_SAMPLE_NOSTAGE: mm_sample_kernel gathers alpha~ from global memory whatever the size (a measurement aid)
 };
 static DebugOpts read_debug_opts() {
     DebugOpts d;
@@ -245,6 +250,7 @@ static DebugOpts read_debug_opts() {
     d.no_xcsr = getenv("MM_NO_XCSR") != nullptr;
     d.verbose = getenv("MM_VERBOSE") != nullptr;
     d.bigv = getenv("MM_BIGV") != nullptr;
+    d.sample_nostage = getenv("MM_SAMPLE_NOSTAGE") != nullptr;
     d.no_redo = getenv("MM_NO_REDO") != nullptr;
     d.no_dpair = getenv("MM_NO_DPAIR") != nullptr;
     d.no_wpair = getenv("MM_NO_WPAIR") != nullptr;
@@ -336,6 +342,8 @@ struct mm_batch_s {
     // sums of all their backward slots, the most caller entries / initial states of one FSM
     ArcDev *d_arcs = nullptr;
     int64_t arc_slots = 0, arc_max_nnz = 0, arc_max_init = 0;
+    // path sampling (mm_samplepaths_f32): the utterances' SampleDev descriptors on the device (made on the first call)
+    SampleDev *d_samp = nullptr;
 };
 
 static bool on_pairs(mm_batch_t h) { return h->fb == Fb::Pairs || h->fb == Fb::Split; }
@@ -2282,6 +2290,7 @@ int mm_batch_destroy(mm_batch_t h) {
     if (h->gen.ws) (void)hipFree(h->gen.ws);
     if (h->gen.d_utts) (void)hipFree(h->gen.d_utts);
     if (h->d_arcs) (void)hipFree(h->d_arcs);
+    if (h->d_samp) (void)hipFree(h->d_samp);
     delete h;
     return MM_OK;
 }
@@ -2477,6 +2486,7 @@ static std::string fb_kernels(mm_batch_t h) {
 }
 
 static bool export_on_pairs(mm_batch_t h, int dir);
+static bool sample_stages(mm_batch_t h);
 int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
     if (!h || !buf || n < 2) return fail(MM_ERR_INVALID, "mm_batch_kernels: bad argument");
     if (entry == 0) h = twin_of(h);  // (ProbSemiring: the fast entry runs the log twins' kernels)
@@ -2500,6 +2510,11 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
         const Geometry g = pick_geometry(h);
         s = "mm_log_kernel<MODE_FB," + std::to_string(g.NI) + ",1> (forward) + mm_arc_kernel<" + std::to_string(g.NI) +
             "> (backward, the arcs' sums by their owning lanes) + mm_arc_scatter_kernel";
+    } else if (entry == 5) {  // mm_samplepaths_f32
+        if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_samplepaths_f32 runs on log-semiring batches only");
+        const Geometry g = pick_geometry(h);
+        s = "mm_log_kernel<MODE_FB," + std::to_string(g.NI) + ",1> (forward) + mm_sample_kernel<" + (sample_stages(h) ? "lds" : "global") +
+            "> (backward sampling, one wave per chain; alpha~ rows " + (sample_stages(h) ? "staged in LDS by DMA" : "gathered from global memory") + ")";
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -3018,6 +3033,125 @@ int mm_arcposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
     ap.isb = isb;
     ap.ttl = ttl;
     return mm_launch_arcs(h->B, NW, g.NI, bigv, size_t(L.total) * 4, p, ap, static_cast<hipStream_t>(stream));
+}
+
+// ---- posterior path sampling (mm_kernel_sample.hip)
+// mm_sample_kernel keeps two alpha~ rows in LDS where they fit (and the item kernel's vectors do: BIGV batches gather from global memory)
+static bool sample_stages(mm_batch_t h) {
+    const Geometry g = pick_geometry(h);
+    const LdsPlan L = lds_plan(h->max_S1p, (h->max_P1 + 3) & ~3, true);
+    const bool bigv = size_t(L.total) * 4 > 160 * 1024 || h->dbg.bigv || g.NI == 0;
+    return !bigv && !h->dbg.sample_nostage && size_t(h->max_S1p) * 8 <= 160 * 1024;
+}
+// The sampling forms of a batch: per FSM, T_hat' by destination over the real states plus the omega column as lists of SampleRec
+// (source, log2 weight, the source's own list), parallel entries of one (source, destination) merged by log-add -- the draw and
+// the reported probability are over STATE sequences -- uploaded once per FSM; per utterance a SampleDev.  Made on the first
+// mm_samplepaths_f32 call, like the item and arc forms: never during a stream capture.
+static int ensure_sample_forms(mm_batch_t h, void *stream) {
+    if (h->d_samp) return MM_OK;
+    if (capturing(stream))
+        return fail(MM_ERR_INVALID, "the sampling forms of this batch are not on the device yet: run mm_samplepaths_f32 once outside a stream capture");
+    std::vector<SampleDev> forms(size_t(h->B));
+    for (int64_t b = 0; b < h->B; ++b) {
+        mm_fsm_t f = h->fsms[size_t(b)];
+        if (!f->samp_blob) {
+            if (f->nnz > INT32_MAX) return fail(MM_ERR_UNSUPPORTED, "mm_samplepaths_f32: more than 2^31 - 1 arcs in one FSM");
+            const Csr &m = f->mat[0];  // row j: the arcs into j, sources ascending
+            const int64_t S1 = f->S1, fin = S1 - 1;
+            const float NINF = -std::numeric_limits<float>::infinity();
+            std::vector<int32_t> start(size_t(S1) + 1, 0);
+            std::vector<SampleRec> recs;
+            recs.reserve(size_t(f->nnz));
+            for (int64_t j = 0; j < S1; ++j) {
+                start[size_t(j)] = int32_t(recs.size());
+                for (int64_t k = m.rowptr[size_t(j)]; k < m.rowptr[size_t(j) + 1];) {
+                    const int32_t i = m.col[size_t(k)];
+                    double mx = -std::numeric_limits<double>::infinity(), sum = 0.0;
+                    int64_t e = k;
+                    for (; e < m.rowptr[size_t(j) + 1] && m.col[size_t(e)] == i; ++e) mx = std::max(mx, double(m.val[size_t(e)]));
+                    for (int64_t q = k; q < e; ++q)
+                        if (m.val[size_t(q)] > NINF) sum += std::exp2(double(m.val[size_t(q)]) - mx);
+                    // (the phony final state is never a source: its self-loop is not part of any path of len_b frames)
+                    if (sum > 0.0 && i != fin) recs.push_back(SampleRec{i, float(mx + std::log2(sum)), 0, 0});
+                    k = e;
+                }
+            }
+            start[size_t(S1)] = int32_t(recs.size());
+            for (SampleRec &r : recs) {
+                r.start = start[size_t(r.src)];
+                r.deg = start[size_t(r.src) + 1] - r.start;
+            }
+            f->samp_fin_start = start[size_t(fin)];
+            f->samp_fin_deg = start[size_t(S1)] - start[size_t(fin)];
+            Blob bl;
+            (void)bl.add(recs);  // (at 0)
+            const int rc = upload(bl, f->samp_blob);
+            if (rc) return rc;
+        }
+        forms[size_t(b)] = SampleDev{static_cast<const SampleRec *>(f->samp_blob.get()), f->samp_fin_start, f->samp_fin_deg};
+    }
+    void *d = nullptr;
+    HIP_TRY(hipMalloc(&d, sizeof(SampleDev) * size_t(h->B)));
+    if (hipMemcpy(d, forms.data(), sizeof(SampleDev) * size_t(h->B), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return fail(MM_ERR_HIP, "mm_samplepaths_f32: upload of the sampling descriptors failed");
+    }
+    h->d_samp = static_cast<SampleDev *>(d);
+    return MM_OK;
+}
+
+int mm_samplepaths_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, int64_t nsamples, int64_t seed,
+                       int32_t *paths, int64_t psb, int64_t psk, float *logprob, int64_t lsb, float *ttl, void *stream) {
+    if (h && h->semiring != MM_LOG)
+        return fail(MM_ERR_UNSUPPORTED, "mm_samplepaths_f32: log-semiring batches only (this batch is " +
+                                            std::string(h->semiring == MM_TROPICAL ? "tropical" : "ProbSemiring") + ")");
+    int rc = check_run(h, "mm_samplepaths_f32", V, N, MM_LOG);
+    if (rc) return rc;
+    if (!paths) return fail(MM_ERR_INVALID, "mm_samplepaths_f32: paths is NULL");
+    if (nsamples < 1) return fail(MM_ERR_INVALID, "mm_samplepaths_f32: nsamples " + std::to_string(nsamples) + " < 1");
+    if (nsamples > INT32_MAX) return fail(MM_ERR_UNSUPPORTED, "mm_samplepaths_f32: more than 2^31 - 1 samples");
+    if (psk < N) return fail(MM_ERR_DIM, "mm_samplepaths_f32: path_stride_k " + std::to_string(psk) + " < N = " + std::to_string(N));
+    if (psb / nsamples < psk)
+        return fail(MM_ERR_DIM, "mm_samplepaths_f32: path_stride_b " + std::to_string(psb) + " < nsamples * path_stride_k");
+    if (logprob && lsb < nsamples) return fail(MM_ERR_DIM, "mm_samplepaths_f32: lp_stride_b " + std::to_string(lsb) + " < nsamples = " + std::to_string(nsamples));
+    // (the item forms first, as mm_arcposteriors_f32: pick_geometry sizes the workgroups by them)
+    rc = ensure_item_forms(h, stream);
+    if (rc) return rc;
+    rc = ensure_sample_forms(h, stream);
+    if (rc) return rc;
+    const Geometry g = pick_geometry(h);
+    const int P1p = (h->max_P1 + 3) & ~3;
+    LdsPlan L = lds_plan(h->max_S1p, P1p, true);
+    const bool bigv = size_t(L.total) * 4 > 160 * 1024 || h->dbg.bigv || g.NI == 0;
+    if (bigv) {
+        if (!h->ws_big) return fail(MM_ERR_UNSUPPORTED, "FSM too large for the LDS and no global-memory vectors were allocated");
+        L = lds_plan(0, P1p, true);
+        if (size_t(L.total) * 4 > 160 * 1024) return fail(MM_ERR_UNSUPPORTED, "too many pdfs for the LDS: " + std::to_string(h->max_P1));
+    }
+    // workspace: the item kernel's alpha~ store and offsets
+    const size_t off_c = align_up(size_t(h->total_s1p) * size_t(N + 1) * 4, 256);
+    rc = ensure_ws(h, std::max(mm_batch_workspace_bytes(h, N), off_c + ws_c_bytes(h, N)), stream);
+    if (rc) return rc;
+    char *ws = static_cast<char *>(h->ws);
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    p.ws_alpha = reinterpret_cast<float *>(ws);
+    p.ws_c = reinterpret_cast<double *>(ws + off_c);
+    if (bigv) {
+        p.ws_big = h->ws_big;
+        p.big_stride = 4ll * h->max_S1p;
+    }
+    SampleParams sp{};
+    sp.forms = h->d_samp;
+    sp.paths = paths;
+    sp.psb = psb;
+    sp.psk = psk;
+    sp.logprob = logprob;
+    sp.lsb = lsb;
+    sp.ttl = ttl;
+    sp.K = int(nsamples);
+    sp.key0 = unsigned(uint64_t(seed));
+    sp.key1 = unsigned(uint64_t(seed) >> 32);
+    return mm_launch_sample(h->B, g.NW, g.NI, bigv, size_t(L.total) * 4, sample_stages(h), h->max_S1p, h->n_cus, p, sp, static_cast<hipStream_t>(stream));
 }
 
 // alpha / beta export on the pair kernels (mm_pairs_tu.hip: mm_fbx_kernel + mm_pair_export_kernel): one shared graph in the pair

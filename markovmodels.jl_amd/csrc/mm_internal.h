@@ -173,4 +173,32 @@ struct ArcParams {
 // NI: register-resident items per wave (8, or 0 for FSMs of more than 65534 states); bigv: the state vectors in global memory
 int mm_launch_arcs(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, const RunParams &p, const ArcParams &ap, hipStream_t stream);
 
+// ---- posterior path sampling (mm_sample_tu.hip: mm_log_kernel's forward half, then mm_sample_kernel on the sampling form)
+#define MM_SAMPLE_NW 8  // waves of a workgroup of mm_sample_kernel that run chains (+ one that stages the alpha~ rows)
+#define MM_SAMPLE_CW 8  // the most chains one wave carries in registers (1, 2, 4 or 8: mm_sample_tu.hip sample_cw)
+struct SampleRec {  // one in-arc i -> j of the sampling form, in the list of its destination j (parallel entries merged)
+    int32_t src;    // i
+    float w;        // log2 T_hat_ij
+    int32_t start;  // the in-list of i: where the walk goes on when i is drawn (no second dependent load per frame)
+    int32_t deg;
+};
+struct SampleDev {  // one FSM's sampling form (mm_engine.hip ensure_sample_forms)
+    const SampleRec *recs;
+    int fin_start, fin_deg;  // the in-list of the phony final state = the omega column (its self-loop left out)
+};
+struct SampleParams {
+    const SampleDev *forms;  // [B]
+    int *paths;
+    long long psb, psk;
+    float *logprob;  // NULL: not asked for
+    long long lsb;
+    float *ttl;      // NULL: not asked for
+    int K;
+    unsigned key0, key1;  // the seed's two halves: the key of the counter-based generator
+};
+// forward launch as mm_launch_arcs (NW, NI, bigv, lds_bytes of the item kernel); stage: the alpha~ rows go through the LDS of
+// mm_sample_kernel (2 * max_S1p floats), else they are gathered from global memory
+int mm_launch_sample(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, bool stage, int max_S1p, int n_cus, const RunParams &p,
+                     const SampleParams &sp, hipStream_t stream);
+
 }  // namespace mm

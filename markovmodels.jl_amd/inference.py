@@ -407,6 +407,27 @@ class BatchedFSM:
         out = (counts, ttl) + ((init,) if want_init else ())
         return tuple(t.cpu().numpy() for t in out) if as_numpy else out
 
+    def samplepaths(self, V, lens=None, nsamples=1, seed=0, want_logprob=False):
+        """Posterior path samples (mm_samplepaths_f32): ``(paths[B, K, N] int32, ttl[B])``, plus ``logprob[B, K]`` when
+        ``want_logprob``.  ``paths[b, k, n]`` is the 0-based state of sample k of utterance b at frame n (-1 for n >= len_b, and
+        everywhere for an utterance without a path), drawn from the posterior over complete state sequences; ``logprob`` the
+        natural-log posterior probability of each sampled sequence; ``ttl`` = log Z, as ``pdfposteriors`` returns it.  A sample
+        depends on (graphs, V, lens, seed) and its indices (b, k) alone: the same seed gives the same samples, the first K' of K
+        samples are the samples of a call with K'.  Log batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        K = int(nsamples)
+        paths = torch.empty((B, max(K, 0), N), dtype=torch.int32, device=Vt.device)
+        ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        lp = torch.empty((B, max(K, 0)), dtype=torch.float32, device=Vt.device) if want_logprob else None
+        check(lib.mm_samplepaths_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
+                                     lt.data_ptr() if lt is not None else None, N, K, int(seed),
+                                     paths.data_ptr(), max(K, 0) * N, N,
+                                     lp.data_ptr() if lp is not None else None, max(K, 0) if lp is not None else 0,
+                                     ttl.data_ptr(), self._stream(torch)))
+        out = (paths, ttl) + ((lp,) if want_logprob else ())
+        return tuple(t.cpu().numpy() for t in out) if as_numpy else out
+
     def maxstateposteriors(self, V, lens=None):
         """Max-marginals of the tropical semiring, (sum S1) x (N+1), computed on the device."""
         return self._export(lib.mm_maxstateposteriors_f32, V, lens)
@@ -489,11 +510,11 @@ class BatchedFSM:
 
     def kernels(self, semiring: str = "log") -> str:
         """The kernels the engine launches for this batch (informational): "log" = pdfposteriors, "tropical" = bestpath, "export" =
-        alpharecursion / betarecursion, "arcs" = arcposteriors."""
+        alpharecursion / betarecursion, "arcs" = arcposteriors, "sample" = samplepaths."""
         import ctypes
 
         buf = ctypes.create_string_buffer(512)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4}[semiring], buf, 512))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5}[semiring], buf, 512))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -797,6 +818,17 @@ def arcposteriors(fsm, Vhats, Chats=None, want_init=False):
     bf = _as_batch(fsm, Chats)
     V, lens = _need_expanded(Vhats, bf.semiring)
     return bf.arcposteriors(V, lens, want_init=want_init)
+
+
+def samplepaths(fsm, Vhats, Chats=None, nsamples=1, seed=0):
+    """State sequences drawn from the posterior over complete paths (forward filtering, backward sampling): per utterance a
+    ``[K, len_b]`` int32 array of 0-based states (what ``bestpath`` returns for its one path) and the ``[K]`` natural-log posterior
+    probabilities of the sampled sequences -- see ``BatchedFSM.samplepaths``.  ``fsm`` and the arguments as for ``bestpath``, on a
+    log-semiring FSM; V_hats must be what ``expand`` makes.  The same ``seed`` gives the same samples."""
+    bf = _as_batch(fsm, Chats)
+    V, lens = _need_expanded(Vhats, bf.semiring)
+    paths, _, lp = bf.samplepaths(V, lens, nsamples=nsamples, seed=seed, want_logprob=True)
+    return [paths[b, :, : lens[b]].copy() for b in range(bf.B)], [lp[b].copy() for b in range(bf.B)]
 
 
 def alpharecursion(fsm, Vhats, Chats=None):

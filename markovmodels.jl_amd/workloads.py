@@ -178,7 +178,9 @@ def sample_paths(g: GraphSpec, B: int, N: int, seed: int = 0, tail: int = 96) ->
     """B accepting state paths of exactly N frames drawn from the graph's own distribution (initial weights, then the arcs'
     probabilities; the last `tail` frames restricted to the arcs from which a final state is still reachable in exactly the
     frames that are left, and the last state drawn by its final weight).  Returns states[B, N] (0-based).  What a TRAINED acoustic
-    model's outputs are consistent with (examples/test_cuda.jl:124-143 feeds network outputs): `path_consistent_emissions`."""
+    model's outputs are consistent with (examples/test_cuda.jl:124-143 feeds network outputs): `path_consistent_emissions`.
+    A host-side sampler from the graph's PRIOR, used to make benchmark emissions -- not `samplepaths`, which draws from the
+    posterior given emissions, on the device."""
     rng = np.random.default_rng(seed)
     S = g.S
     order = np.argsort(g.src, kind="stable")
