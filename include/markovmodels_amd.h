@@ -114,7 +114,7 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * shapes): entry 0 = mm_pdfposteriors_f32, 1 = mm_viterbi_f32, 2 = what the last mm_pdfposteriors_ex call on the batch launched
  * (the recursion kernel; for ProbSemiring FSMs in float32 with general state maps, the emission GEMM C_hat * V_hat on the matrix
  * cores before it), 3 = mm_alpharecursion_f32 / mm_betarecursion_f32, 4 = mm_arcposteriors_f32 (log batches only),
- * 5 = mm_samplepaths_f32 (log batches only).
+ * 5 = mm_samplepaths_f32 (log batches only), 6 = mm_expectedcost_f32 (log batches only).
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -211,6 +211,51 @@ int mm_arcposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, i
 int mm_samplepaths_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
                        int64_t nsamples, int64_t seed, int32_t *paths, int64_t path_stride_b, int64_t path_stride_k,
                        float *logprob, int64_t lp_stride_b, float *ttl, void *stream);
+
+/* Expected path cost under the path posterior and its gradient: any frame-decomposable Bayes risk; with
+ * cost = -[pdf equals the reference alignment's pdf] over the denominator graph, lattice-free sMBR (Kanda et al., Interspeech 2018).
+ * For utterance b with expanded emissions lhs = C_hat * expand(V_b) (frames 1..N+1, length len_b, exactly mm_pdfposteriors_f32's
+ * semantics) and costs cost_b(n, p) for the len_b real frames and the P real pdfs (the phony pdf costs 0; frames beyond len_b
+ * cost 0 and are NOT READ; the formulas count frames from 1 as the reference does, the arrays from 0 as V does):
+ *
+ *   A(pi)        = sum_{n=1..len_b} cost_b(n, pdf(s_n))                    for a complete state sequence pi = s_1 .. s_{N+1}
+ *   risk_b       = sum_pi P(pi | V_b) * A(pi)
+ *   grad_b(n,p)  = d risk_b / d V_b(n,p)    = sum_{j : pdf(j) = p} gamma_n(j) * (E[A | s_n = j] - risk_b)
+ *   gamma_b(n,p) = d risk_b / d cost_b(n,p) = the pdf posterior, as mm_pdfposteriors_f32 returns it
+ *
+ * E[A | s_n = j] = r_n(j) + s_n(j) with the two conditional expectations
+ *   r_1(j) = cost(1, pdf j)     r_n(j) = cost(n, pdf j) + sum_i P(s_{n-1}=i | s_n=j, V_{1..n}) * r_{n-1}(i),  P(i | j) ~ alpha_{n-1}(i) T_hat_ij
+ *   s_{N+1}(.) = 0              s_n(i) = sum_j P(s_{n+1}=j | s_n=i, V) * (cost(n+1, pdf j) + s_{n+1}(j)),     P(j | i) ~ T_hat_ij lhs_{n+1}(j) beta_{n+1}(j)
+ * Both are convex combinations plus an addition; a state no path reaches takes r = s = 0 (0/0 := 0); risk_b = r_{N+1}(final).
+ * It follows that risk_b = sum_{n,p} gamma_b(n,p) * cost_b(n,p), that sum_p grad_b(n,p) = 0 for every frame, and that a cost that
+ * does not depend on p (cost(n,p) = c_n) gives risk_b = sum_{n<len_b} c_n and grad = 0.
+ *   V, lens, N   as mm_pdfposteriors_f32
+ *   cost         device, laid out like V: element (b, n, p) at cost[b*c_stride_b + n*c_stride_n + p], n < len_b only; must be
+ *                finite there (a non-finite one makes that utterance's outputs unspecified and touches no other utterance).
+ *                NULL: MM_ERR_INVALID; c_stride_n < P: MM_ERR_DIM
+ *   risk         device float[B], out.  NULL: MM_ERR_INVALID
+ *   grad         device, out: element (b, n, p) at grad[b*g_stride_b + n*g_stride_n + p*g_stride_p] (mm_pdfposteriors_f32's meaning
+ *                of the three strides: the reference's column-major layout is g_stride_b = 1, g_stride_p = B, g_stride_n = B*P);
+ *                frames n >= len_b are exact zeros.  NULL: MM_ERR_INVALID; strides that cannot hold B x N x P distinct elements
+ *                (sorted by stride, each must reach past the extent of the one before): MM_ERR_DIM
+ *   gamma        device, out with grad's strides (NULL: not written)
+ *   ttl          device float[B], out (NULL: not written): log Z_b, the value mm_pdfposteriors_f32 returns
+ * An utterance without an accepting path (len_b = 0 included) gets risk 0, grad 0, gamma 0, ttl = -inf.
+ * MM_LOG batches only: Tropical and ProbSemiring batches return MM_ERR_UNSUPPORTED.  Runs on the item form of every FSM (any size),
+ * one workgroup per utterance: a forward kernel that carries r beside alpha~ (one 8-byte gather per arc), a backward kernel that
+ * carries s beside beta~ and adds the per-pdf sums over fixed lists -- no atomics, so a repeated call returns the same bits.  r and
+ * s are carried centred by per-frame float64 offsets, so the float32 values stay near zero whatever the length, and the frame's
+ * posterior mean of E[A | s_n] - risk_b (zero by the law of total expectation) is taken out of grad, which removes the rounding the
+ * states of a frame share.  The exact, mark
+ * and gamma policies and the posterior floor do not apply.  Workspace: the alpha~ store of the item kernel and an r store of the
+ * same size, float32 (sum_b S1p_b) x (N + 1) each (config 3 of bench.py at B = 256, N = 1500: 3.1 GB each), grown by the call.
+ * Stream contract of mm_arcposteriors_f32: launches on `stream` only, no host synchronisation; it can be captured in a hipGraph
+ * once a first call has put the batch's item forms on the device and sized the workspace (a capture before that returns
+ * MM_ERR_INVALID). */
+int mm_expectedcost_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                        const float *cost, int64_t c_stride_b, int64_t c_stride_n,
+                        float *risk, float *grad, float *gamma, int64_t g_stride_b, int64_t g_stride_n, int64_t g_stride_p,
+                        float *ttl, void *stream);
 
 /* alpha-recursion(alpha_hat, T_hat', C_hat*V_hat) (src/inference.jl:62-74) as
  * called from pdfposteriors (:150-152): out is the reference's state_A, a

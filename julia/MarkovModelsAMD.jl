@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, samplepaths, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, samplepaths, expectedcost, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -265,6 +265,33 @@ function samplepaths(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing; nsampl
         b.handle, pointer(V), P * N, P, lp, N, K, seed % Int64, pointer(paths), N * K, N, pointer(logprob), K, pointer(ttl),
         AMDGPU.stream().stream))
     Array(paths) .+ Int32(1), Array(logprob), Array(ttl)      # (the library's states are 0-based, -1 = no state)
+end
+
+"""
+    expectedcost(b::ROCBatch, V::ROCArray{Float32,3}, cost::ROCArray{Float32,3}, lens = nothing) -> (risk, grad, γ, ttl)
+
+Expected cost of a path under the path posterior and its gradient (mm_expectedcost_f32 in the header) of a log-semiring batch.
+`V` and `lens` as for `pdfposteriors`; `cost` laid out like `V` (P × N × B): what an utterance pays for a state of pdf p at frame
+n (finite inside the length, not read beyond it).  Returns `risk` (B), `grad` = ∂ risk / ∂ V and `γ` = ∂ risk / ∂ cost (the pdf
+posteriors), both B × P × N like `pdfposteriors`' γ, and ttl = log Z.  With `cost = -onehot(reference pdfs)` on the denominator
+graph, `risk` is the lattice-free sMBR objective (minus the expected number of correct frames).
+"""
+function expectedcost(b::ROCBatch, V::ROCArray{Float32,3}, cost::ROCArray{Float32,3}, lens = nothing)
+    P, N, B = size(V)
+    P == b.P || throw(DimensionMismatch("V has $P pdfs, the FSMs $(b.P)"))
+    size(cost) == size(V) || throw(DimensionMismatch("cost is $(size(cost)), V $(size(V))"))
+    risk = ROCArray{Float32}(undef, B)
+    grad = ROCArray{Float32}(undef, B, P, N)
+    γ = ROCArray{Float32}(undef, B, P, N)
+    ttl = ROCArray{Float32}(undef, B)
+    lp = lens === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(lens))
+    check(ccall((:mm_expectedcost_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Float32}, Int64, Int64,
+         Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int64, Int64, Int64, Ptr{Float32}, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, lp, N, pointer(cost), P * N, P,
+        pointer(risk), pointer(grad), pointer(γ), 1, B * P, B, pointer(ttl),
+        AMDGPU.stream().stream))
+    risk, grad, γ, ttl
 end
 
 """

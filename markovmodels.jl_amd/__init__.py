@@ -2,7 +2,7 @@
 
 Host-side mirror of the reference's hot-path interface (src/MarkovModels.jl:14-45:
 FSM, nstates, rawunion, CompiledFSM, batch, compile, expand, alpha-recursion,
-beta-recursion, pdfposteriors, arcposteriors, samplepaths, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
+beta-recursion, pdfposteriors, arcposteriors, samplepaths, expectedcost, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
 The directory name contains a dot, so load it with
 ``__graft_entry__.load_package()`` (importlib) rather than a plain import.
 """
@@ -21,6 +21,7 @@ from .inference import (  # noqa: F401
     compiled_cache_clear,
     compiled_cache_stats,
     expand,
+    expectedcost,
     maxstateposteriors,
     pdfposteriors,
     samplepaths,
@@ -33,3 +34,4 @@ from .inference import (  # noqa: F401
 from . import dist, linalg  # noqa: F401
 from .linalg import SparseCSR, SparseVector, eldiv_, elmul_, mul_  # noqa: F401
 from .lfmmi import lfmmi_loss  # noqa: F401
+from .mbr import expected_cost, smbr_loss  # noqa: F401

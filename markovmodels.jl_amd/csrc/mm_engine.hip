@@ -2487,6 +2487,7 @@ static std::string fb_kernels(mm_batch_t h) {
 
 static bool export_on_pairs(mm_batch_t h, int dir);
 static bool sample_stages(mm_batch_t h);
+static bool cost_bigv(mm_batch_t h);
 int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
     if (!h || !buf || n < 2) return fail(MM_ERR_INVALID, "mm_batch_kernels: bad argument");
     if (entry == 0) h = twin_of(h);  // (ProbSemiring: the fast entry runs the log twins' kernels)
@@ -2515,6 +2516,12 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
         const Geometry g = pick_geometry(h);
         s = "mm_log_kernel<MODE_FB," + std::to_string(g.NI) + ",1> (forward) + mm_sample_kernel<" + (sample_stages(h) ? "lds" : "global") +
             "> (backward sampling, one wave per chain; alpha~ rows " + (sample_stages(h) ? "staged in LDS by DMA" : "gathered from global memory") + ")";
+    } else if (entry == 6) {  // mm_expectedcost_f32
+        if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_expectedcost_f32 runs on log-semiring batches only");
+        const Geometry g = pick_geometry(h);
+        const std::string inst = "<" + std::to_string(g.NI) + "," + (cost_bigv(h) ? "global" : "lds") + ">";
+        s = "mm_cost_fwd_kernel" + inst + " (forward: alpha~ and r) + mm_cost_bwd_kernel" + inst + " (backward: beta~ and s, gamma and grad per pdf); state vectors " +
+            (cost_bigv(h) ? "in global memory" : "in LDS");
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -3033,6 +3040,84 @@ int mm_arcposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
     ap.isb = isb;
     ap.ttl = ttl;
     return mm_launch_arcs(h->B, NW, g.NI, bigv, size_t(L.total) * 4, p, ap, static_cast<hipStream_t>(stream));
+}
+
+// ---- expected path cost and its gradient (mm_kernel_cost.hip)
+static bool cost_bigv(mm_batch_t h) {
+    return mm_cost_lds_bytes(h->max_S1p, (h->max_P1 + 3) & ~3) > 160 * 1024 || h->dbg.bigv || pick_geometry(h).NI == 0;
+}
+// workspace of mm_expectedcost_f32: the alpha~ store and its offsets as the item kernel keeps them, the r store and its offsets,
+// and for FSMs beyond the LDS the state vectors of both kernels ([B][8 * max S1p] floats)
+static size_t cost_ws_bytes(mm_batch_t h, int64_t N, bool bigv, size_t off[4]) {
+    const size_t rows = align_up(size_t(h->total_s1p) * size_t(N + 1) * 4, 256);
+    off[0] = rows;
+    off[1] = off[0] + ws_c_bytes(h, N);
+    off[2] = off[1] + rows;
+    off[3] = off[2] + ws_c_bytes(h, N);
+    return off[3] + (bigv ? align_up(size_t(h->B) * 8 * size_t(h->max_S1p) * 4, 256) : 0);
+}
+// an output laid out by three strides holds every element once: sorted by stride, each reaches past the extent of the one before
+static bool strides_hold(int64_t sb, int64_t B, int64_t sn, int64_t N, int64_t sp, int64_t P) {
+    std::pair<int64_t, int64_t> d[3] = {{sb, B}, {sn, N}, {sp, P}};
+    std::sort(d, d + 3);
+    int64_t need = 1;
+    for (const auto &e : d) {
+        if (e.second <= 1) continue;
+        if (e.first < need) return false;
+        need = e.first * e.second;
+    }
+    return true;
+}
+
+int mm_expectedcost_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, const float *cost,
+                        int64_t csb, int64_t csn, float *risk, float *grad, float *gamma, int64_t gsb, int64_t gsn, int64_t gsp, float *ttl,
+                        void *stream) {
+    if (h && h->semiring != MM_LOG)
+        return fail(MM_ERR_UNSUPPORTED, "mm_expectedcost_f32: log-semiring batches only (this batch is " +
+                                            std::string(h->semiring == MM_TROPICAL ? "tropical" : "ProbSemiring") + ")");
+    int rc = check_run(h, "mm_expectedcost_f32", V, N, MM_LOG);
+    if (rc) return rc;
+    if (!cost || !risk || !grad) return fail(MM_ERR_INVALID, "mm_expectedcost_f32: cost / risk / grad is NULL");
+    const int64_t P = h->max_P1 - 1;
+    if (csn < P) return fail(MM_ERR_DIM, "mm_expectedcost_f32: c_stride_n " + std::to_string(csn) + " < " + std::to_string(P) + " pdfs");
+    if (!strides_hold(gsb, h->B, gsn, N, gsp, P))
+        return fail(MM_ERR_DIM, "mm_expectedcost_f32: g strides (" + std::to_string(gsb) + ", " + std::to_string(gsn) + ", " + std::to_string(gsp) +
+                                    ") cannot hold " + std::to_string(h->B) + " x " + std::to_string(N) + " x " + std::to_string(P) + " elements");
+    // (the item forms first, as mm_arcposteriors_f32: pick_geometry sizes the workgroups by them)
+    rc = ensure_item_forms(h, stream);
+    if (rc) return rc;
+    const Geometry g = pick_geometry(h);
+    const int NW = std::min(g.NW, 8);  // (both kernels are compiled for 8 waves per CU: 8 items and the pair arithmetic per wave)
+    const int P1p = (h->max_P1 + 3) & ~3;
+    const bool bigv = cost_bigv(h);
+    const size_t lds = mm_cost_lds_bytes(bigv ? 0 : h->max_S1p, P1p);
+    if (lds > 160 * 1024) return fail(MM_ERR_UNSUPPORTED, "too many pdfs for the LDS: " + std::to_string(h->max_P1));
+    size_t off[4];
+    const size_t total = cost_ws_bytes(h, N, bigv, off);
+    rc = ensure_ws(h, std::max(mm_batch_workspace_bytes(h, N), total), stream);
+    if (rc) return rc;
+    char *ws = static_cast<char *>(h->ws);
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    p.ws_alpha = reinterpret_cast<float *>(ws);
+    p.ws_c = reinterpret_cast<double *>(ws + off[0]);
+    CostParams cp{};
+    cp.cost = cost;
+    cp.csb = csb;
+    cp.csn = csn;
+    cp.risk = risk;
+    cp.grad = grad;
+    cp.gamma = gamma;
+    cp.gsb = gsb;
+    cp.gsn = gsn;
+    cp.gsp = gsp;
+    cp.ttl = ttl;
+    cp.ws_r = reinterpret_cast<float *>(ws + off[1]);
+    cp.ws_o = reinterpret_cast<double *>(ws + off[2]);
+    if (bigv) {
+        cp.ws_big = reinterpret_cast<float *>(ws + off[3]);
+        cp.big_stride = 8ll * h->max_S1p;
+    }
+    return mm_launch_cost(h->B, NW, g.NI, bigv, lds, p, cp, static_cast<hipStream_t>(stream));
 }
 
 // ---- posterior path sampling (mm_kernel_sample.hip)

@@ -201,4 +201,22 @@ struct SampleParams {
 int mm_launch_sample(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, bool stage, int max_S1p, int n_cus, const RunParams &p,
                      const SampleParams &sp, hipStream_t stream);
 
+// ---- expected path cost and its gradient (mm_cost_tu.hip: mm_cost_fwd_kernel, mm_cost_bwd_kernel on the item form)
+struct CostParams {
+    const float *cost;  // [b * csb + n * csn + p], frames below len_b only
+    long long csb, csn;
+    float *risk;   // [B]
+    float *grad;   // strides as gamma's
+    float *gamma;  // NULL: not asked for
+    long long gsb, gsn, gsp;
+    float *ttl;    // NULL: not asked for
+    float *ws_r;   // [sum_b S1p_b][N+1] the centred r rows, laid out like RunParams::ws_alpha
+    double *ws_o;  // [B][N+2] per-frame offsets O_n of the r rows; [0]: risk
+    float *ws_big; // global-memory vectors: [B][big_stride] floats (8 * max S1p)
+    long long big_stride;
+};
+// lds_bytes: cost_lds_plan(...).total * 4 of the geometry (state vectors in LDS, or bigv: in CostParams::ws_big)
+int mm_launch_cost(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, const RunParams &p, const CostParams &cp, hipStream_t stream);
+size_t mm_cost_lds_bytes(int S1p, int P1p);
+
 }  // namespace mm

@@ -428,6 +428,33 @@ class BatchedFSM:
         out = (paths, ttl) + ((lp,) if want_logprob else ())
         return tuple(t.cpu().numpy() for t in out) if as_numpy else out
 
+    def expectedcost(self, V, cost, lens=None, want_gamma=False):
+        """Expected path cost under the path posterior and its gradient (mm_expectedcost_f32): ``(risk[B], grad[B, N, P],
+        ttl[B])``, plus ``gamma[B, N, P]`` when ``want_gamma``.  ``cost[b, n, p]`` is what utterance b pays for being in a state
+        of pdf p at frame n (finite for n < len_b, not read beyond); ``risk[b]`` the posterior expectation of a path's summed
+        cost, ``grad`` its derivative with respect to ``V``, ``gamma`` (the pdf posteriors) its derivative with respect to
+        ``cost``; ``ttl`` = log Z, as ``pdfposteriors`` returns it.  With ``cost = -onehot(reference pdfs)`` on the denominator
+        graph this is lattice-free sMBR (``mbr.smbr_loss``).  Log batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        Ct = torch.as_tensor(np.ascontiguousarray(cost, dtype=np.float32)).cuda() if not isinstance(cost, torch.Tensor) else cost
+        if Ct.dtype != torch.float32 or Ct.device != Vt.device:
+            raise TypeError("cost must be a float32 tensor on V's device")
+        if tuple(Ct.shape) != (B, N, P):
+            raise _lib.DimensionMismatch(-2, f"cost must be [B={B}, N={N}, P={P}], got {tuple(Ct.shape)}")
+        if Ct.stride(2) != 1:
+            Ct = Ct.contiguous()
+        risk = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        grad = torch.empty((B, N, P), dtype=torch.float32, device=Vt.device)
+        gamma = torch.empty((B, N, P), dtype=torch.float32, device=Vt.device) if want_gamma else None
+        check(lib.mm_expectedcost_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
+                                      lt.data_ptr() if lt is not None else None, N, Ct.data_ptr(), Ct.stride(0), Ct.stride(1),
+                                      risk.data_ptr(), grad.data_ptr(), gamma.data_ptr() if gamma is not None else None,
+                                      grad.stride(0), grad.stride(1), grad.stride(2), ttl.data_ptr(), self._stream(torch)))
+        out = (risk, grad, ttl) + ((gamma,) if want_gamma else ())
+        return tuple(t.cpu().numpy() for t in out) if as_numpy else out
+
     def maxstateposteriors(self, V, lens=None):
         """Max-marginals of the tropical semiring, (sum S1) x (N+1), computed on the device."""
         return self._export(lib.mm_maxstateposteriors_f32, V, lens)
@@ -510,11 +537,11 @@ class BatchedFSM:
 
     def kernels(self, semiring: str = "log") -> str:
         """The kernels the engine launches for this batch (informational): "log" = pdfposteriors, "tropical" = bestpath, "export" =
-        alpharecursion / betarecursion, "arcs" = arcposteriors, "sample" = samplepaths."""
+        alpharecursion / betarecursion, "arcs" = arcposteriors, "sample" = samplepaths, "cost" = expectedcost."""
         import ctypes
 
         buf = ctypes.create_string_buffer(512)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5}[semiring], buf, 512))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6}[semiring], buf, 512))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -818,6 +845,28 @@ def arcposteriors(fsm, Vhats, Chats=None, want_init=False):
     bf = _as_batch(fsm, Chats)
     V, lens = _need_expanded(Vhats, bf.semiring)
     return bf.arcposteriors(V, lens, want_init=want_init)
+
+
+def expectedcost(fsm, Vhats, costs, Chats=None):
+    """Expected path cost of every utterance under its path posterior, and the gradient: ``(risk[B], grad[B, P, N], ttl[B])`` --
+    see ``BatchedFSM.expectedcost``.  ``fsm`` and the arguments as for ``pdfposteriors``: the rawunion of the batch with its state
+    maps, or a BatchedFSM / CompiledFSM; V_hats must be what ``expand`` makes; ``costs[b]`` is a P x N_b matrix, N_b at least
+    the utterance's length (the cost of pdf p at frame n, laid out like the real rows of a V_hat; columns beyond the length are
+    ignored).  ``grad`` comes back in ``pdfposteriors``' layout.  NumPy arrays out."""
+    bf = _as_batch(fsm, Chats)
+    V, lens = _need_expanded(Vhats, bf.semiring)
+    B, N, P = V.shape
+    cost = np.zeros((B, N, P), dtype=np.float32)
+    costs = list(costs)
+    if len(costs) != B:
+        raise _lib.DimensionMismatch(-2, f"{len(costs)} cost matrices for a batch of {B} FSMs")
+    for b, c in enumerate(costs):
+        c = np.asarray(c.cpu() if hasattr(c, "cpu") else c, dtype=np.float32)
+        if c.ndim != 2 or c.shape[0] != P or c.shape[1] < lens[b]:
+            raise _lib.DimensionMismatch(-2, f"cost {b} must be P={P} x (at least {int(lens[b])} frames), got {c.shape}")
+        cost[b, : lens[b]] = c[:, : lens[b]].T
+    risk, grad, ttl = bf.expectedcost(V, cost, lens)
+    return risk, np.ascontiguousarray(grad.transpose(0, 2, 1)), ttl
 
 
 def samplepaths(fsm, Vhats, Chats=None, nsamples=1, seed=0):
