@@ -425,6 +425,18 @@ static Geometry pick_geometry(mm_batch_t h) {
     return g;
 }
 
+// Whether an item-form kernel of this batch keeps its state vectors in global memory (BIGV): its LDS plan (with or without the
+// stage rows, and `extra` bytes a kernel adds behind the plan) does not fit 160 KB, or MM_BIGV asks for it.
+static bool vectors_global(mm_batch_t h, bool with_stage, size_t extra = 0) {
+    return size_t(lds_plan(h->max_S1p, (h->max_P1 + 3) & ~3, with_stage).total) * 4 + extra > 160 * 1024 || h->dbg.bigv;
+}
+// the arc, sampling and cost entries have no streamed-only instance with the vectors in LDS: NI = 0 runs <0, BIGV>.
+// (mm_batch_create asks these before the item forms are up: pick_geometry's NI must never depend on max_items, which
+// ensure_item_forms raises later -- only NW does.)
+static bool arcs_global(mm_batch_t h) { return vectors_global(h, true, 2 * MM_MAX_WAVES * sizeof(float)) || pick_geometry(h).NI == 0; }  // (mm_launch_arcs: + the posterior sums)
+static bool sample_global(mm_batch_t h) { return vectors_global(h, true) || pick_geometry(h).NI == 0; }
+static const char *where_of(bool global) { return global ? "global" : "lds"; }
+
 // item / tropical kernels: `kernel` keeps the state vectors in LDS; `big` is the same kernel with the vectors in global
 // memory, for FSMs beyond the LDS (the reference has no size limit: src/linalg.jl:170-181)
 static int fsm_to_device(mm_fsm_t f);
@@ -463,7 +475,7 @@ static int launch(K kernel, K big, mm_batch_t h, const RunParams &p0, bool with_
     RunParams p = p0;
     p.deterministic = h->deterministic ? 1 : 0;
     LdsPlan L = lds_plan(h->max_S1p, P1p, with_stage);
-    if (size_t(L.total) * 4 > 160 * 1024 || h->dbg.bigv) {
+    if (vectors_global(h, with_stage)) {
         if (!h->ws_big) return fail(MM_ERR_UNSUPPORTED, "FSM too large for the LDS and no global-memory vectors were allocated");
         L = lds_plan(0, P1p, with_stage);
         if (size_t(L.total) * 4 > 160 * 1024) return fail(MM_ERR_UNSUPPORTED, "too many pdfs for the LDS: " + std::to_string(h->max_P1));
@@ -2237,9 +2249,10 @@ static int batch_create_impl(const mm_fsm_t *fsms, int64_t B, mm_batch_t *out) {
         return fail(MM_ERR_HIP, "mm_batch_create: device allocation failed");
     }
     h->utts_host = std::move(utts);
-    {   // FSMs whose state vectors do not fit the LDS: the item / tropical kernels keep them in global memory
-        const int P1p = (h->max_P1 + 3) & ~3;
-        if (size_t(lds_plan(h->max_S1p, P1p, true).total) * 4 > 160 * 1024 || h->dbg.bigv) {
+    {   // FSMs whose state vectors do not fit the LDS: the item / tropical kernels keep them in global memory.  The arc kernel's
+        // plan is the largest (32 floats behind the item kernel's), and the streamed-only instances of the arc and sampling
+        // entries have the vectors there whatever the size (MM_NITEMS=0 on a small graph)
+        if (arcs_global(h)) {
             if (hipMalloc(&h->ws_big, size_t(B) * 4 * size_t(h->max_S1p) * sizeof(float)) != hipSuccess) {
                 h->ws_big = nullptr;
                 return fail(MM_ERR_HIP, "mm_batch_create: device allocation failed");
@@ -2429,10 +2442,27 @@ int mm_batch_team_xcd_stats(mm_batch_t h, int out[2]) {
 }
 
 // (mm_batch_kernels, entry 0) what mm_pdfposteriors_f32 launches on a log batch
+// the item kernel by instance: <MODE, NI, where the state vectors live> (FB: <MODE_FB, NI, pass, where>)
+static std::string item_fb_kernels(mm_batch_t h, bool one_launch) {
+    const std::string w = where_of(vectors_global(h, true));
+    if (one_launch || pick_geometry(h).NI == 0)  // (redo_on_items always, launch_log without resident items)
+        return "mm_log_kernel<MODE_FB,0,0," + w + "> (forward and backward in one launch, every item streamed)";
+    return "mm_log_kernel<MODE_FB,8,1," + w + "> (forward) + mm_log_kernel<MODE_FB,8,2," + w + "> (backward)";
+}
+static std::string item_export_kernel(mm_batch_t h, const char *mode, bool trop) {
+    return std::string("mm_log_kernel<") + mode + "," + std::to_string(pick_geometry(h).NI) + "," + where_of(vectors_global(h, false)) + (trop ? ",TROP>" : ">");
+}
+static std::string tropical_kernel(mm_batch_t h) {  // (launch_tropical)
+    const bool resident = pick_geometry(h).NI == 8 && h->max_items <= 8 * MM_MAX_WAVES;
+    return std::string("mm_tropical_kernel<") + (resident ? "8," : "0,") + where_of(vectors_global(h, true)) + ">";
+}
+
 static std::string fb_kernels(mm_batch_t h) {
-    const std::string exact = h->quad_ok ? "mm_fbq_kernel<" + std::to_string(h->geo_kq[0]) + ",*,0> + mm_fbq_kernel<" +
-                                               std::to_string(h->geo_kq[1]) + ",*,1>"
-                                         : std::string("mm_log_kernel<MODE_FB> (forward, backward)");
+    // what fb_exact runs, and (`redo`) what the families that hand their marked utterances to redo_on_items run
+    const std::string quad = "mm_fbq_kernel<" + std::to_string(h->geo_kq[0]) + ",*,0> + mm_fbq_kernel<" + std::to_string(h->geo_kq[1]) + ",*,1>";
+    const std::string exact = h->quad_ok ? quad : item_fb_kernels(h, false);
+    const std::string redo = item_fb_kernels(h, true);
+    const std::string pair_tail = h->dpair_ok && !h->quad_ok ? redo : exact;
     switch (h->fb) {
     case Fb::Lane:
         return "mm_lane_kernel<" + std::to_string(h->lane_S <= 8 ? 8 : h->lane_S <= 16 ? 16 : h->lane_S <= 32 ? 32 : 64) +
@@ -2444,7 +2474,7 @@ static std::string fb_kernels(mm_batch_t h) {
         return "mm_stream_kernel (forward and backward recursions as workgroups of one grid" +
             (h->stream_H > 1 ? ", teams of " + std::to_string(h->stream_H) + " workgroups per utterance and direction" : std::string()) +
             "; arcs streamed from L2, the vector in LDS as wide-exponent "
-            "32-bit values), mm_stream_combine_kernel, mm_stream_finish_kernel, then for marked utterances only " + exact;
+            "32-bit values), mm_stream_combine_kernel, mm_stream_finish_kernel, then for marked utterances only " + redo;
     case Fb::Split: {
         const std::string k = std::to_string(mm_pair_nj(h->max_P1, h->pair_H)), H = std::to_string(h->pair_H);
         return "mm_fbs_kernel<" + k + ",A," + H + ">, then <" + k + ",B," + H + "> (forward and backward agents in one grid, teams of " + H +
@@ -2455,7 +2485,7 @@ static std::string fb_kernels(mm_batch_t h) {
                                             : std::string("; FIRST and alone while the inputs are hard)")) +
                                ", mm_dpair_finish_kernel, then for what those mark "
                          : std::string()) +
-            exact;
+            pair_tail;
     }
     case Fb::Pairs: {
         const std::string k = std::to_string(mm_pair_nj(h->max_P1));
@@ -2467,7 +2497,7 @@ static std::string fb_kernels(mm_batch_t h) {
                                             : std::string("; FIRST and alone while the inputs are hard)")) +
                                ", mm_dpair_finish_kernel, then for what those mark "
                          : std::string()) +
-            exact;
+            pair_tail;
     }
     case Fb::Rows: {
         auto ka = [&](int d) {
@@ -2497,20 +2527,23 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
     if (entry == 0) {  // mm_pdfposteriors_f32
         s = fb_kernels(h);
     } else if (entry == 1) {  // mm_viterbi_f32
-        s = h->vit_ok ? "mm_vit_kernel + mm_vit_backtrace_kernel (mm_tropical_kernel + mm_backtrace_kernel when the int32 back-pointers are asked for)"
-                      : "mm_tropical_kernel + mm_backtrace_kernel";
+        const std::string t = tropical_kernel(h);
+        s = h->vit_ok ? "mm_vit_kernel + mm_vit_backtrace_kernel (" + t + " + mm_backtrace_kernel when the int32 back-pointers are asked for)"
+                      : t + " + mm_backtrace_kernel";
     } else if (entry == 3) {  // mm_alpharecursion_f32 / mm_betarecursion_f32
         const bool xa = export_on_pairs(h, 0), xb = export_on_pairs(h, 1);
         const std::string fast = (h->pair_H > 1 ? "mm_fbsx_kernel<2," + std::to_string(h->pair_H) + "> (phase A of one direction over all frames, teams of " + std::to_string(h->pair_H) + " workgroups) + "
                                                 : "mm_fbx_kernel<" + std::to_string(mm_pair_nj(h->max_P1)) + "> (phase A of one direction over all frames, two utterances per workgroup) + ") +
-                                 "mm_pair_export_kernel, then for marked utterances only the item kernel";
-        s = h->semiring == MM_TROPICAL ? std::string("mm_tropical_kernel / mm_log_kernel<MODE_BETA, TROP>")
-            : "alpha: " + (xa ? fast : std::string("mm_log_kernel<MODE_ALPHA>")) + "; beta: " + (xb ? fast : std::string("mm_log_kernel<MODE_BETA>"));
+                                 "mm_pair_export_kernel, then for marked utterances only the item kernel, ";
+        const std::string ia = item_export_kernel(h, "MODE_ALPHA", false), ib = item_export_kernel(h, "MODE_BETA", false);
+        s = h->semiring == MM_TROPICAL ? tropical_kernel(h) + " / " + item_export_kernel(h, "MODE_BETA", true)
+            : "alpha: " + (xa ? fast + ia : ia) + "; beta: " + (xb ? fast + ib : ib);
     } else if (entry == 4) {  // mm_arcposteriors_f32
         if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_arcposteriors_f32 runs on log-semiring batches only");
         const Geometry g = pick_geometry(h);
         s = "mm_log_kernel<MODE_FB," + std::to_string(g.NI) + ",1> (forward) + mm_arc_kernel<" + std::to_string(g.NI) +
-            "> (backward, the arcs' sums by their owning lanes) + mm_arc_scatter_kernel";
+            "> (backward, the arcs' sums by their owning lanes) + mm_arc_scatter_kernel; state vectors " +
+            (arcs_global(h) ? "in global memory" : "in LDS");
     } else if (entry == 5) {  // mm_samplepaths_f32
         if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_samplepaths_f32 runs on log-semiring batches only");
         const Geometry g = pick_geometry(h);
@@ -3013,7 +3046,7 @@ int mm_arcposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
     const int NW = std::min(g.NW, 8);  // (mm_arc_kernel holds 8 items' arcs and their sums per wave: 8 waves per CU)
     const int P1p = (h->max_P1 + 3) & ~3;
     LdsPlan L = lds_plan(h->max_S1p, P1p, true);
-    const bool bigv = size_t(L.total) * 4 + 2 * MM_MAX_WAVES * 4 > 160 * 1024 || h->dbg.bigv || g.NI == 0;  // (mm_launch_arcs: + the posterior sums)
+    const bool bigv = arcs_global(h);
     if (bigv) {
         if (!h->ws_big) return fail(MM_ERR_UNSUPPORTED, "FSM too large for the LDS and no global-memory vectors were allocated");
         L = lds_plan(0, P1p, true);
@@ -3123,10 +3156,7 @@ int mm_expectedcost_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, 
 // ---- posterior path sampling (mm_kernel_sample.hip)
 // mm_sample_kernel keeps two alpha~ rows in LDS where they fit (and the item kernel's vectors do: BIGV batches gather from global memory)
 static bool sample_stages(mm_batch_t h) {
-    const Geometry g = pick_geometry(h);
-    const LdsPlan L = lds_plan(h->max_S1p, (h->max_P1 + 3) & ~3, true);
-    const bool bigv = size_t(L.total) * 4 > 160 * 1024 || h->dbg.bigv || g.NI == 0;
-    return !bigv && !h->dbg.sample_nostage && size_t(h->max_S1p) * 8 <= 160 * 1024;
+    return !sample_global(h) && !h->dbg.sample_nostage && size_t(h->max_S1p) * 8 <= 160 * 1024;
 }
 // The sampling forms of a batch: per FSM, T_hat' by destination over the real states plus the omega column as lists of SampleRec
 // (source, log2 weight, the source's own list), parallel entries of one (source, destination) merged by log-add -- the draw and
@@ -3207,7 +3237,7 @@ int mm_samplepaths_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, c
     const Geometry g = pick_geometry(h);
     const int P1p = (h->max_P1 + 3) & ~3;
     LdsPlan L = lds_plan(h->max_S1p, P1p, true);
-    const bool bigv = size_t(L.total) * 4 > 160 * 1024 || h->dbg.bigv || g.NI == 0;
+    const bool bigv = sample_global(h);
     if (bigv) {
         if (!h->ws_big) return fail(MM_ERR_UNSUPPORTED, "FSM too large for the LDS and no global-memory vectors were allocated");
         L = lds_plan(0, P1p, true);

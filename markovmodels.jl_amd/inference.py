@@ -540,16 +540,16 @@ class BatchedFSM:
         alpharecursion / betarecursion, "arcs" = arcposteriors, "sample" = samplepaths, "cost" = expectedcost."""
         import ctypes
 
-        buf = ctypes.create_string_buffer(512)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6}[semiring], buf, 512))
+        buf = ctypes.create_string_buffer(1024)
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6}[semiring], buf, 1024))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
         """What the last call of the generic entry (mm_pdfposteriors_ex) launched for this batch (informational)."""
         import ctypes
 
-        buf = ctypes.create_string_buffer(512)
-        check(lib.mm_batch_kernels(self._h, 2, buf, 512))
+        buf = ctypes.create_string_buffer(1024)
+        check(lib.mm_batch_kernels(self._h, 2, buf, 1024))
         return buf.value.decode()
 
     def viterbi(self, V, lens=None, return_backpointers=False):

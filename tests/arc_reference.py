@@ -85,18 +85,21 @@ def enumerate_paths(g, f, V, L, N):
 
 
 def check(c, init, ttl, c_ref, init_ref, logz_ref, L, N):
-    """The accuracy bar of the arc posteriors against a float64 reference (one utterance)."""
+    """The accuracy bar of the arc posteriors against a float64 reference (one utterance).  Returns the measured worst
+    per-arc error over its bar."""
     c = np.asarray(c, dtype=np.float64)
     if not np.isfinite(logz_ref):
         assert (c == 0).all() and np.isneginf(ttl)
         if init is not None:
             assert (np.asarray(init) == 0).all()
-        return
+        return 0.0
     err = np.abs(c - c_ref)
     assert (err <= 1e-4 * c_ref + 1e-6 * max(L, 1)).all(), (err.max(), int(np.argmax(err - 1e-4 * c_ref)))
+    worst = float(np.max(err / (1e-4 * c_ref + 1e-6 * max(L, 1))))
     assert abs(c.sum() - N) <= 1e-4 * N, (c.sum(), N)
     assert np.isclose(ttl, logz_ref, rtol=1e-5, atol=1e-5 * max(1.0, abs(logz_ref)) + 1e-4), (ttl, logz_ref)
     if init is not None:
         init = np.asarray(init, dtype=np.float64)
         assert abs(init.sum() - 1.0) <= 1e-5, init.sum()
         assert (np.abs(init - init_ref) <= 1e-4 * init_ref + 1e-6).all()
+    return worst

@@ -17,6 +17,7 @@ import graphs
 #   config 3 graph, T = 500, log_softmax(10 x)        2.1e-6
 #   WSJ denominator / numerator, T = 700              6.7e-7 / 3.0e-6
 #   four distinct graphs / 12 500 states, T = 40      1.6e-6 / 1.2e-6
+#   the cases of tests/test_gpu_itemform.py (70 000 states, the boundaries, wide rows), T <= 60   <= 3.0e-7
 # a = 10 x the worst (the factor is for what the NumPy run does not have: the hardware's exp2 / log2 approximations in alpha~ and
 # beta~, the kernel's reduction order, float32 partial sums per pdf), capped at the project's own 1e-4.
 GRAD_F32_FLOOR = 3.01e-6

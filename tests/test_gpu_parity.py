@@ -23,6 +23,8 @@ def torch():
 
 
 def check_gamma(g, g_ref, lens):
+    """The accuracy bar of pdf posteriors against a float64 reference.  Returns the measured worst log-posterior error over
+    its bar."""
     g = np.asarray(g, dtype=np.float64)
     assert np.isfinite(g).all()
     for b, L in enumerate(lens):
@@ -34,6 +36,7 @@ def check_gamma(g, g_ref, lens):
     assert (np.abs(lg - lr) <= RTOL_LOGPOST * np.maximum(np.abs(lr), 1.0)).all(), np.abs(lg - lr).max()
     for b, L in enumerate(lens):
         assert np.allclose(g[b, :L].sum(-1), 1.0, atol=1e-5)
+    return float(np.max(np.abs(lg - lr) / (RTOL_LOGPOST * np.maximum(np.abs(lr), 1.0)))) if m.any() else 0.0
 
 
 def run_shared(mm, wl, oracle, torch, g, B, N, lens, seed=0, scale=1.0):

@@ -56,6 +56,11 @@ def _exact_check(gr, support, logp, paths, lp, L, tag):
 # ---- 1. the exact distribution
 @pytest.mark.parametrize("case", range(len(sr.TINY_CASES)))
 def test_exact_distribution_on_tiny_graphs(mm, wl, torch, case):
+    _exact_tiny_run(mm, wl, case)
+
+
+def _exact_tiny_run(mm, wl, case):
+    """The case above; returns the batch it ran."""
     S, seed, N, L = sr.TINY_CASES[case]
     g, f64, V = sr.tiny_case(mm, wl, S, seed, N)
     gr = sr.Graph(g, f64)
@@ -68,6 +73,7 @@ def test_exact_distribution_on_tiny_graphs(mm, wl, torch, case):
     for b in range(2):
         _exact_check(gr, support, logp, paths[b], lp[b], L, f"case {case} utterance {b}")
     assert not np.array_equal(paths[0], paths[1])  # (independent streams: the key is the position in the batch)
+    return bf
 
 
 # ---- 2. / 3. marginals, validity and logprob at real sizes

@@ -1,5 +1,5 @@
 """The float32 floor of the expected-cost recursion, on the CPU: tests/cost_reference.py's float32 mode (r and s carried centred in
-float32, the offsets in float64) against its float64 mode, on the very inputs of tests/test_gpu_expectedcost.py.  The worst
+float32, the offsets in float64) against its float64 mode, on the very inputs of tests/test_gpu_expectedcost.py and tests/test_gpu_itemform.py.  The worst
 |grad_f32 - grad_f64| / G_b it prints is cost_reference.GRAD_F32_FLOOR; 10 x that (capped at 1e-4) is the absolute part of the
 gradient's bar.  No GPU involved: the kernel is never the source of its own tolerance.
 
@@ -33,6 +33,16 @@ def main():
              ("config3 T=500 log_softmax(10x)", lambda: t.case_config3(wl, True)), ("wsj den T=700", lambda: t.case_wsj(wl, "den_fsm_wsj")),
              ("wsj num T=700", lambda: t.case_wsj(wl, "num_fsm_wsj")), ("four distinct graphs", lambda: t.case_distinct(wl)),
              ("12500 states", lambda: t.case_bigv(wl))]
+    import test_gpu_itemform as ti
+
+    # the item-form cases (tests/test_gpu_itemform.py): streamed-only instances, beyond 16-bit state indices, boundaries, wide rows
+    cases += [("lfmmi600", lambda: ti.case_lfmmi600(wl)), ("70000 states", lambda: ti.case_random_big(wl)),
+              ("70000 + 40 states", lambda: ti.case_mixed(wl, True)), ("40 + 70000 states", lambda: ti.case_mixed(wl, False)),
+              ("65530 states", lambda: ti.case_random_big(wl, 65530)), ("65531 states", lambda: ti.case_random_big(wl, 65531)),
+              ("5062 states", lambda: ti.case_random_big(wl, ti.PREDICTED_LDS_BOUNDARY["cost"])),
+              ("5063 states", lambda: ti.case_random_big(wl, ti.PREDICTED_LDS_BOUNDARY["cost"] + 1)),
+              ("wide rows", lambda: ti.case_wide(wl, "wide")), ("ergodic300", lambda: ti.case_wide(wl, "ergodic300")),
+              ("lexicon3000", lambda: ti.case_wide(wl, "lexicon"))]
     rows, worst = [], 0.0
     for name, make in cases:
         gs, V, cost, lens, idx = make()
