@@ -13,8 +13,7 @@ static int launch_arcs_ni(int64_t B, int NW, size_t lds, const RunParams &p, con
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fwd), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
     hipLaunchKernelGGL(fwd, dim3(unsigned(B)), dim3(64 * NW), lds, stream, p);
     HIP_TRY(hipGetLastError());
-    // (mm_arc_kernel: the per-wave posterior sums of two frames behind the item kernel's LDS plan)
-    const size_t lds_b = lds + 2 * MM_MAX_WAVES * sizeof(float);
+    const size_t lds_b = lds + MM_ARC_LDS_EXTRA;
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bwd), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_b)));
     hipLaunchKernelGGL(bwd, dim3(unsigned(B)), dim3(64 * NW), lds_b, stream, p, ap);
     HIP_TRY(hipGetLastError());

@@ -340,10 +340,10 @@ struct mm_batch_s {
     size_t prob_logv_bytes = 0;
     // arc posteriors (mm_arcposteriors_f32): the utterances' ArcDev descriptors on the device (made on the first call), the float64
     // sums of all their backward slots, the most caller entries / initial states of one FSM
-    ArcDev *d_arcs = nullptr;
+    DevMem d_arcs;
     int64_t arc_slots = 0, arc_max_nnz = 0, arc_max_init = 0;
     // path sampling (mm_samplepaths_f32): the utterances' SampleDev descriptors on the device (made on the first call)
-    SampleDev *d_samp = nullptr;
+    DevMem d_samp;
 };
 
 static bool on_pairs(mm_batch_t h) { return h->fb == Fb::Pairs || h->fb == Fb::Split; }
@@ -425,16 +425,54 @@ static Geometry pick_geometry(mm_batch_t h) {
     return g;
 }
 
-// Whether an item-form kernel of this batch keeps its state vectors in global memory (BIGV): its LDS plan (with or without the
-// stage rows, and `extra` bytes a kernel adds behind the plan) does not fit 160 KB, or MM_BIGV asks for it.
-static bool vectors_global(mm_batch_t h, bool with_stage, size_t extra = 0) {
-    return size_t(lds_plan(h->max_S1p, (h->max_P1 + 3) & ~3, with_stage).total) * 4 + extra > 160 * 1024 || h->dbg.bigv;
+// ---- one plan per entry that runs on the item form: its launch geometry and where its state vectors live
+enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost };
+struct ItemPlan {
+    ItemEntry e;
+    int NW, NI;        // waves per workgroup, register-resident items per wave of the instance (8 or 0)
+    bool global;       // the state vectors in global memory (BIGV), else in LDS
+    bool stage;        // (Sample) mm_sample_kernel keeps two alpha~ rows in LDS, else it gathers them from global memory
+    size_t lds_bytes;  // dynamic LDS of the chosen placement (Arcs: of the forward kernel; mm_arc_kernel adds MM_ARC_LDS_EXTRA)
+};
+// The only source of the above.  The vectors are global when the entry's LDS plan (the item kernel's, with the stage rows for
+// all but the export modes, + the arc kernel's extra; Cost: cost_lds_plan) does not fit 160 KB, when MM_BIGV asks for it, or for
+// the arc, sampling and cost kernels when NI = 0: they have no streamed-only instance with the vectors in LDS.
+// `global` never depends on max_items, nor does NI except Tropical's (8: the whole graph is register-resident): mm_batch_create
+// asks before the item forms are up, and ensure_item_forms raises max_items later -- only NW follows it.
+static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
+    const size_t lds_max = 160 * 1024;
+    const Geometry g = pick_geometry(h);
+    const int P1p = (h->max_P1 + 3) & ~3;
+    auto bytes = [&](int S1p) {
+        return e == ItemEntry::Cost ? mm_cost_lds_bytes(S1p, P1p) : size_t(lds_plan(S1p, P1p, e != ItemEntry::Export).total) * 4;
+    };
+    const bool derived = e == ItemEntry::Arcs || e == ItemEntry::Sample || e == ItemEntry::Cost;
+    ItemPlan pl{e, g.NW, g.NI, false, false, 0};
+    pl.global = bytes(h->max_S1p) + (e == ItemEntry::Arcs ? MM_ARC_LDS_EXTRA : 0) > lds_max || h->dbg.bigv || (derived && g.NI == 0);
+    pl.lds_bytes = bytes(pl.global ? 0 : h->max_S1p);
+    if (e == ItemEntry::Arcs || e == ItemEntry::Cost) pl.NW = std::min(g.NW, 8);  // (8 items' arcs and their sums / the pair arithmetic per wave: compiled for 8 waves per CU)
+    if (e == ItemEntry::Sample) pl.stage = !pl.global && !h->dbg.sample_nostage && size_t(h->max_S1p) * 8 <= lds_max;
+    if (e == ItemEntry::Tropical) {
+        // register-resident items when the whole graph fits 8 items per wave -- as many waves as there is work for (latency), at most
+        // 8 items each --, else streamed
+        pl.NI = g.NI == 8 && h->max_items <= 8 * MM_MAX_WAVES ? 8 : 0;
+        pl.NW = pl.NI ? std::min(MM_MAX_WAVES, std::max(g.NW, (h->max_items + 3) / 4)) : 16;
+        if (pl.NI && h->dbg.nwaves >= g.NW && h->dbg.nwaves <= MM_MAX_WAVES) pl.NW = h->dbg.nwaves;
+    }
+    return pl;
 }
-// the arc, sampling and cost entries have no streamed-only instance with the vectors in LDS: NI = 0 runs <0, BIGV>.
-// (mm_batch_create asks these before the item forms are up: pick_geometry's NI must never depend on max_items, which
-// ensure_item_forms raises later -- only NW does.)
-static bool arcs_global(mm_batch_t h) { return vectors_global(h, true, 2 * MM_MAX_WAVES * sizeof(float)) || pick_geometry(h).NI == 0; }  // (mm_launch_arcs: + the posterior sums)
-static bool sample_global(mm_batch_t h) { return vectors_global(h, true) || pick_geometry(h).NI == 0; }
+// ... for an entry about to launch: refuses what the plan cannot run.  (Cost keeps its global vectors in the workspace at
+// 8 floats per state, the others in h->ws_big at 4: bind_big, ItemWs)
+static int item_plan_check(mm_batch_t h, const ItemPlan &pl) {
+    if (pl.global && pl.e != ItemEntry::Cost && !h->ws_big)
+        return fail(MM_ERR_UNSUPPORTED, "FSM too large for the LDS and no global-memory vectors were allocated");
+    return pl.lds_bytes > 160 * 1024 ? fail(MM_ERR_UNSUPPORTED, "too many pdfs for the LDS: " + std::to_string(h->max_P1)) : int(MM_OK);
+}
+static void bind_big(mm_batch_t h, const ItemPlan &pl, RunParams &p) {
+    if (!pl.global || pl.e == ItemEntry::Cost) return;
+    p.ws_big = h->ws_big;
+    p.big_stride = 4ll * h->max_S1p;
+}
 static const char *where_of(bool global) { return global ? "global" : "lds"; }
 
 // item / tropical kernels: `kernel` keeps the state vectors in LDS; `big` is the same kernel with the vectors in global
@@ -465,44 +503,37 @@ static int ensure_item_forms(mm_batch_t h, void *stream) {
     return MM_OK;
 }
 
+// (NW is the caller's: launch_log and launch_tropical read their plan BEFORE the item forms of a batch created without them are
+// up, so the first call on such a batch runs with fewer waves than the later ones)
 template <typename K>
-static int launch(K kernel, K big, mm_batch_t h, const RunParams &p0, bool with_stage, int NW, void *stream) {
-    {
-        const int rc = ensure_item_forms(h, stream);
-        if (rc) return rc;
-    }
-    const int P1p = (h->max_P1 + 3) & ~3;
+static int launch(K kernel, K big, mm_batch_t h, const RunParams &p0, ItemEntry e, int NW, void *stream) {
+    int rc = ensure_item_forms(h, stream);
+    if (rc) return rc;
+    const ItemPlan pl = item_plan(h, e);
+    rc = item_plan_check(h, pl);
+    if (rc) return rc;
     RunParams p = p0;
     p.deterministic = h->deterministic ? 1 : 0;
-    LdsPlan L = lds_plan(h->max_S1p, P1p, with_stage);
-    if (vectors_global(h, with_stage)) {
-        if (!h->ws_big) return fail(MM_ERR_UNSUPPORTED, "FSM too large for the LDS and no global-memory vectors were allocated");
-        L = lds_plan(0, P1p, with_stage);
-        if (size_t(L.total) * 4 > 160 * 1024) return fail(MM_ERR_UNSUPPORTED, "too many pdfs for the LDS: " + std::to_string(h->max_P1));
-        kernel = big;
-        p.ws_big = h->ws_big;
-        p.big_stride = 4ll * h->max_S1p;
-    }
-    const size_t lds = size_t(L.total) * 4;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                int(lds)));
-    hipLaunchKernelGGL(kernel, dim3(unsigned(h->B)), dim3(64 * NW), lds, static_cast<hipStream_t>(stream), p);
+    if (pl.global) kernel = big;
+    bind_big(h, pl, p);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(pl.lds_bytes)));
+    hipLaunchKernelGGL(kernel, dim3(unsigned(h->B)), dim3(64 * NW), pl.lds_bytes, static_cast<hipStream_t>(stream), p);
     HIP_TRY(hipGetLastError());
     return MM_OK;
 }
 
 template <int MODE, bool TROP = false>
 static int launch_log(mm_batch_t h, const RunParams &p, void *stream) {
-    const Geometry g = pick_geometry(h);
-    const bool st = MODE == MODE_FB;
+    const ItemEntry e = MODE == MODE_FB ? ItemEntry::Fb : ItemEntry::Export;
+    const ItemPlan g = item_plan(h, e);
     if (MODE == MODE_FB && g.NI != 0) {  // forward kernel, then backward kernel on the same stream
-        int rc = launch(mm_log_kernel<MODE, 8, 1, TROP, false>, mm_log_kernel<MODE, 8, 1, TROP, true>, h, p, st, g.NW, stream);
+        int rc = launch(mm_log_kernel<MODE, 8, 1, TROP, false>, mm_log_kernel<MODE, 8, 1, TROP, true>, h, p, e, g.NW, stream);
         if (rc) return rc;
-        return launch(mm_log_kernel<MODE, 8, 2, TROP, false>, mm_log_kernel<MODE, 8, 2, TROP, true>, h, p, st, g.NW, stream);
+        return launch(mm_log_kernel<MODE, 8, 2, TROP, false>, mm_log_kernel<MODE, 8, 2, TROP, true>, h, p, e, g.NW, stream);
     }
     switch (g.NI) {
-        case 0: return launch(mm_log_kernel<MODE, 0, 0, TROP, false>, mm_log_kernel<MODE, 0, 0, TROP, true>, h, p, st, g.NW, stream);
-        default: return launch(mm_log_kernel<MODE, 8, 0, TROP, false>, mm_log_kernel<MODE, 8, 0, TROP, true>, h, p, st, g.NW, stream);
+        case 0: return launch(mm_log_kernel<MODE, 0, 0, TROP, false>, mm_log_kernel<MODE, 0, 0, TROP, true>, h, p, e, g.NW, stream);
+        default: return launch(mm_log_kernel<MODE, 8, 0, TROP, false>, mm_log_kernel<MODE, 8, 0, TROP, true>, h, p, e, g.NW, stream);
     }
 }
 
@@ -544,14 +575,9 @@ static int launch_quad(mm_batch_t h, const RunParams &p, void *stream) {
 }
 
 static int launch_tropical(mm_batch_t h, const RunParams &p, void *stream) {
-    // register-resident items when the whole graph fits 8 items per wave, else streamed
-    const Geometry g = pick_geometry(h);
-    if (g.NI == 8 && h->max_items <= 8 * MM_MAX_WAVES) {  // as many waves as there is work for (latency), at most 8 items each
-        int NW = std::min(MM_MAX_WAVES, std::max(g.NW, (h->max_items + 3) / 4));
-        if (h->dbg.nwaves >= g.NW && h->dbg.nwaves <= MM_MAX_WAVES) NW = h->dbg.nwaves;
-        return launch(mm_tropical_kernel<8, false>, mm_tropical_kernel<8, true>, h, p, true, NW, stream);
-    }
-    return launch(mm_tropical_kernel<0, false>, mm_tropical_kernel<0, true>, h, p, true, 16, stream);
+    const ItemPlan pl = item_plan(h, ItemEntry::Tropical);
+    if (pl.NI == 8) return launch(mm_tropical_kernel<8, false>, mm_tropical_kernel<8, true>, h, p, pl.e, pl.NW, stream);
+    return launch(mm_tropical_kernel<0, false>, mm_tropical_kernel<0, true>, h, p, pl.e, pl.NW, stream);
 }
 
 // The row kernels (mm_kernel_rows.hip): KA register-resident arcs per lane, NWC compute waves + 1 service wave.
@@ -2249,15 +2275,14 @@ static int batch_create_impl(const mm_fsm_t *fsms, int64_t B, mm_batch_t *out) {
         return fail(MM_ERR_HIP, "mm_batch_create: device allocation failed");
     }
     h->utts_host = std::move(utts);
-    {   // FSMs whose state vectors do not fit the LDS: the item / tropical kernels keep them in global memory.  The arc kernel's
-        // plan is the largest (32 floats behind the item kernel's), and the streamed-only instances of the arc and sampling
-        // entries have the vectors there whatever the size (MM_NITEMS=0 on a small graph)
-        if (arcs_global(h)) {
-            if (hipMalloc(&h->ws_big, size_t(B) * 4 * size_t(h->max_S1p) * sizeof(float)) != hipSuccess) {
-                h->ws_big = nullptr;
-                return fail(MM_ERR_HIP, "mm_batch_create: device allocation failed");
-            }
-        }
+    // FSMs whose state vectors do not fit the LDS of some entry that keeps them in h->ws_big (every one but Cost): the arc kernel's
+    // plan is the largest, and the streamed-only instances of the arc and sampling entries have the vectors there whatever the
+    // size (MM_NITEMS=0 on a small graph)
+    bool big = false;
+    for (ItemEntry e : {ItemEntry::Fb, ItemEntry::Export, ItemEntry::Tropical, ItemEntry::Arcs, ItemEntry::Sample}) big |= item_plan(h, e).global;
+    if (big && hipMalloc(&h->ws_big, size_t(B) * 4 * size_t(h->max_S1p) * sizeof(float)) != hipSuccess) {
+        h->ws_big = nullptr;
+        return fail(MM_ERR_HIP, "mm_batch_create: device allocation failed");
     }
     if (on_pairs(h) && !h->dbg.no_dpair) {
         void *hp = nullptr;
@@ -2302,8 +2327,6 @@ int mm_batch_destroy(mm_batch_t h) {
     if (h->stat_host) (void)hipHostFree(const_cast<int *>(h->stat_host));
     if (h->gen.ws) (void)hipFree(h->gen.ws);
     if (h->gen.d_utts) (void)hipFree(h->gen.d_utts);
-    if (h->d_arcs) (void)hipFree(h->d_arcs);
-    if (h->d_samp) (void)hipFree(h->d_samp);
     delete h;
     return MM_OK;
 }
@@ -2444,17 +2467,19 @@ int mm_batch_team_xcd_stats(mm_batch_t h, int out[2]) {
 // (mm_batch_kernels, entry 0) what mm_pdfposteriors_f32 launches on a log batch
 // the item kernel by instance: <MODE, NI, where the state vectors live> (FB: <MODE_FB, NI, pass, where>)
 static std::string item_fb_kernels(mm_batch_t h, bool one_launch) {
-    const std::string w = where_of(vectors_global(h, true));
-    if (one_launch || pick_geometry(h).NI == 0)  // (redo_on_items always, launch_log without resident items)
+    const ItemPlan pl = item_plan(h, ItemEntry::Fb);
+    const std::string w = where_of(pl.global);
+    if (one_launch || pl.NI == 0)  // (redo_on_items always, launch_log without resident items)
         return "mm_log_kernel<MODE_FB,0,0," + w + "> (forward and backward in one launch, every item streamed)";
     return "mm_log_kernel<MODE_FB,8,1," + w + "> (forward) + mm_log_kernel<MODE_FB,8,2," + w + "> (backward)";
 }
 static std::string item_export_kernel(mm_batch_t h, const char *mode, bool trop) {
-    return std::string("mm_log_kernel<") + mode + "," + std::to_string(pick_geometry(h).NI) + "," + where_of(vectors_global(h, false)) + (trop ? ",TROP>" : ">");
+    const ItemPlan pl = item_plan(h, ItemEntry::Export);
+    return std::string("mm_log_kernel<") + mode + "," + std::to_string(pl.NI) + "," + where_of(pl.global) + (trop ? ",TROP>" : ">");
 }
 static std::string tropical_kernel(mm_batch_t h) {  // (launch_tropical)
-    const bool resident = pick_geometry(h).NI == 8 && h->max_items <= 8 * MM_MAX_WAVES;
-    return std::string("mm_tropical_kernel<") + (resident ? "8," : "0,") + where_of(vectors_global(h, true)) + ">";
+    const ItemPlan pl = item_plan(h, ItemEntry::Tropical);
+    return "mm_tropical_kernel<" + std::to_string(pl.NI) + "," + where_of(pl.global) + ">";
 }
 
 static std::string fb_kernels(mm_batch_t h) {
@@ -2516,8 +2541,6 @@ static std::string fb_kernels(mm_batch_t h) {
 }
 
 static bool export_on_pairs(mm_batch_t h, int dir);
-static bool sample_stages(mm_batch_t h);
-static bool cost_bigv(mm_batch_t h);
 int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
     if (!h || !buf || n < 2) return fail(MM_ERR_INVALID, "mm_batch_kernels: bad argument");
     if (entry == 0) h = twin_of(h);  // (ProbSemiring: the fast entry runs the log twins' kernels)
@@ -2538,23 +2561,21 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
         const std::string ia = item_export_kernel(h, "MODE_ALPHA", false), ib = item_export_kernel(h, "MODE_BETA", false);
         s = h->semiring == MM_TROPICAL ? tropical_kernel(h) + " / " + item_export_kernel(h, "MODE_BETA", true)
             : "alpha: " + (xa ? fast + ia : ia) + "; beta: " + (xb ? fast + ib : ib);
-    } else if (entry == 4) {  // mm_arcposteriors_f32
-        if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_arcposteriors_f32 runs on log-semiring batches only");
-        const Geometry g = pick_geometry(h);
-        s = "mm_log_kernel<MODE_FB," + std::to_string(g.NI) + ",1> (forward) + mm_arc_kernel<" + std::to_string(g.NI) +
-            "> (backward, the arcs' sums by their owning lanes) + mm_arc_scatter_kernel; state vectors " +
-            (arcs_global(h) ? "in global memory" : "in LDS");
-    } else if (entry == 5) {  // mm_samplepaths_f32
-        if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_samplepaths_f32 runs on log-semiring batches only");
-        const Geometry g = pick_geometry(h);
-        s = "mm_log_kernel<MODE_FB," + std::to_string(g.NI) + ",1> (forward) + mm_sample_kernel<" + (sample_stages(h) ? "lds" : "global") +
-            "> (backward sampling, one wave per chain; alpha~ rows " + (sample_stages(h) ? "staged in LDS by DMA" : "gathered from global memory") + ")";
-    } else if (entry == 6) {  // mm_expectedcost_f32
-        if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_expectedcost_f32 runs on log-semiring batches only");
-        const Geometry g = pick_geometry(h);
-        const std::string inst = "<" + std::to_string(g.NI) + "," + (cost_bigv(h) ? "global" : "lds") + ">";
-        s = "mm_cost_fwd_kernel" + inst + " (forward: alpha~ and r) + mm_cost_bwd_kernel" + inst + " (backward: beta~ and s, gamma and grad per pdf); state vectors " +
-            (cost_bigv(h) ? "in global memory" : "in LDS");
+    } else if (entry >= 4 && entry <= 6) {  // mm_arcposteriors_f32, mm_samplepaths_f32, mm_expectedcost_f32
+        static const char *const who[] = {"mm_arcposteriors_f32", "mm_samplepaths_f32", "mm_expectedcost_f32"};
+        if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, std::string("mm_batch_kernels: ") + who[entry - 4] + " runs on log-semiring batches only");
+        const ItemPlan pl = item_plan(h, entry == 4 ? ItemEntry::Arcs : entry == 5 ? ItemEntry::Sample : ItemEntry::Cost);
+        const std::string ni = std::to_string(pl.NI), vectors = pl.global ? "in global memory" : "in LDS";
+        if (entry == 4) {
+            s = "mm_log_kernel<MODE_FB," + ni + ",1> (forward) + mm_arc_kernel<" + ni +
+                "> (backward, the arcs' sums by their owning lanes) + mm_arc_scatter_kernel; state vectors " + vectors;
+        } else if (entry == 5) {
+            s = "mm_log_kernel<MODE_FB," + ni + ",1> (forward) + mm_sample_kernel<" + where_of(!pl.stage) +
+                "> (backward sampling, one wave per chain; alpha~ rows " + (pl.stage ? "staged in LDS by DMA" : "gathered from global memory") + ")";
+        } else {
+            const std::string inst = "<" + ni + "," + where_of(pl.global) + ">";
+            s = "mm_cost_fwd_kernel" + inst + " (forward: alpha~ and r) + mm_cost_bwd_kernel" + inst + " (backward: beta~ and s, gamma and grad per pdf); state vectors " + vectors;
+        }
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -2736,7 +2757,7 @@ static int prob_pdfposteriors(mm_batch_t h, const float *V, int64_t vsb, int64_t
 // the item kernel for what the kernels before it marked (p.redo), both passes in ONE launch whose workgroups of the other utterances
 // leave at once (streamed items: its speed does not matter, the empty launch's does)
 static int redo_on_items(mm_batch_t h, const RunParams &p, void *stream) {
-    return launch(mm_log_kernel<MODE_FB, 0, 0, false, false>, mm_log_kernel<MODE_FB, 0, 0, false, true>, h, p, true, pick_geometry(h).NW, stream);
+    return launch(mm_log_kernel<MODE_FB, 0, 0, false, false>, mm_log_kernel<MODE_FB, 0, 0, false, true>, h, p, ItemEntry::Fb, item_plan(h, ItemEntry::Fb).NW, stream);
 }
 
 // the library's own zeroing kernel over `bytes` (a multiple of 16) at d
@@ -2959,82 +2980,138 @@ int mm_pdfposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
     return fb_exact(h, p, ws, L, stream);
 }
 
-// The arc forms of a batch (mm_kernel_arcs.hip): per FSM, the slot of the backward item form that holds each caller entry and the
-// initial states in init_idx order (uploaded once per FSM); per utterance, an ArcDev with its first slot in the float64 sums.
-// Made on the first mm_arcposteriors_f32 call, like the item forms: never during a stream capture.
-static int ensure_arc_forms(mm_batch_t h, void *stream) {
-    if (h->d_arcs) return MM_OK;
-    if (capturing(stream))
-        return fail(MM_ERR_INVALID, "the arc forms of this batch are not on the device yet: run mm_arcposteriors_f32 once outside a stream capture");
-    std::vector<ArcDev> arcs(size_t(h->B));
-    int64_t slots = 0;
-    for (int64_t b = 0; b < h->B; ++b) {
-        mm_fsm_t f = h->fsms[size_t(b)];
-        if (f->nnz > INT32_MAX) return fail(MM_ERR_UNSUPPORTED, "mm_arcposteriors_f32: more than 2^31 - 1 arcs in one FSM");
-        const Packed &pk = f->packed[1];  // (ensure_item_forms packed it)
-        if (!f->arc_blob) {
-            std::vector<int32_t> k2slot(size_t(f->nnz), -1);
-            const std::vector<int64_t> &rowptr = f->mat[1].rowptr;
-            for (size_t it = 0; it < pk.items.size(); ++it) {
-                const ItemMeta &im = pk.items[it];
-                const int g = 1 << im.log2g;
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int32_t row = pk.rowinfo[it * 64 + size_t(lane)].row;
-                    if (row < 0) continue;
-                    // (pack_rows: lane `sub` of the row's group holds arcs sub, sub + g, ... in slots k = 0, 1, ...)
-                    int64_t k = 0;
-                    for (int64_t a = rowptr[size_t(row)] + (lane & (g - 1)); a < rowptr[size_t(row) + 1]; a += g, ++k)
-                        k2slot[size_t(f->bwd_caller[size_t(a)])] = int32_t((int64_t(im.slot_row) + k) * 64 + lane);
-                }
-            }
-            Blob bl;
-            (void)bl.add(k2slot);  // (at 0)
-            (void)bl.add(f->init_order);
-            const int rc = upload(bl, f->arc_blob);
-            if (rc) return rc;
-        }
-        ArcDev &a = arcs[size_t(b)];
-        const size_t o_i = align_up(size_t(f->nnz) * 4, 256);  // (where Blob::add put init_order, behind k2slot)
-        a.k2slot = static_cast<const int *>(f->arc_blob.get());
-        a.init_states = reinterpret_cast<const int *>(static_cast<const char *>(f->arc_blob.get()) + o_i);
-        a.slot_off = slots;
-        a.nnz = int(f->nnz);
-        a.n_init = int(f->init_order.size());
-        a.kphony = int(f->kphony);
-        a.pad = 0;
-        slots += pk.n_slot_rows * 64;
-        h->arc_max_nnz = std::max<int64_t>(h->arc_max_nnz, f->nnz);
-        h->arc_max_init = std::max<int64_t>(h->arc_max_init, int64_t(f->init_order.size()));
+}  // extern "C"
+// ---- the entries on the item form beside pdfposteriors: arc posteriors, path sampling, expected cost (log batches only)
+
+// What the three start with: the semiring refusal, check_run, the entry's own argument checks (`args`), the item forms -- ahead
+// of the plan: a batch created without them has max_items = 0 until they are up, and the plan would size the workgroups for no
+// items --, then the plan.  Its refusals come with the workspace (item_ws_bind), behind what the entry checks on its derived forms.
+template <class Args>
+static int item_entry_begin(mm_batch_t h, const char *who, ItemEntry e, const float *V, int64_t N, void *stream, Args args, ItemPlan *pl) {
+    if (h && h->semiring != MM_LOG)
+        return fail(MM_ERR_UNSUPPORTED, std::string(who) + ": log-semiring batches only (this batch is " +
+                                            std::string(h->semiring == MM_TROPICAL ? "tropical" : "ProbSemiring") + ")");
+    int rc = check_run(h, who, V, N, MM_LOG);
+    if (!rc) rc = args();
+    if (!rc) rc = ensure_item_forms(h, stream);
+    if (!rc) *pl = item_plan(h, e);
+    return rc;
+}
+
+// Where the three keep what they keep in h->ws for N frames: byte offsets, each aligned to 256 bytes.  The alpha~ store (at 0) and
+// the per-frame offsets as the item kernel keeps them; Arcs: the float64 sums of all backward slots, the state posteriors of
+// frame 1; Cost: the r store and its offsets, and for FSMs beyond the LDS the state vectors of both kernels ([B][8 * max S1p]
+// floats).  total: no less than what mm_pdfposteriors_f32 needs for as many frames.  (mm_batch_reserve does not cover it.)
+struct ItemWs { size_t c = 0, acc = 0, post1 = 0, r = 0, o = 0, big = 0, total = 0; };
+static ItemWs item_ws_layout(mm_batch_t h, const ItemPlan &pl, int64_t N) {
+    ItemWs W;
+    const size_t rows = align_up(size_t(h->total_s1p) * size_t(N + 1) * 4, 256);
+    W.c = rows;
+    W.total = W.c + ws_c_bytes(h, N);
+    if (pl.e == ItemEntry::Arcs) {
+        W.acc = W.total;
+        W.post1 = W.acc + align_up(size_t(h->arc_slots) * 8, 256);
+        W.total = W.post1 + align_up(size_t(h->total_s1p) * 4, 256);
+    } else if (pl.e == ItemEntry::Cost) {
+        W.r = W.total;
+        W.o = W.r + rows;
+        W.big = W.o + ws_c_bytes(h, N);
+        W.total = W.big + (pl.global ? align_up(size_t(h->B) * 8 * size_t(h->max_S1p) * 4, 256) : 0);
     }
-    void *d = nullptr;
-    HIP_TRY(hipMalloc(&d, sizeof(ArcDev) * size_t(h->B)));
-    if (hipMemcpy(d, arcs.data(), sizeof(ArcDev) * size_t(h->B), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(d);
-        return fail(MM_ERR_HIP, "mm_arcposteriors_f32: upload of the arc descriptors failed");
-    }
-    h->d_arcs = static_cast<ArcDev *>(d);
-    h->arc_slots = slots;
+    W.total = std::max(W.total, mm_batch_workspace_bytes(h, N));
+    return W;
+}
+// refuses what the plan cannot run, grows the workspace to the layout and binds the call to it
+static int item_ws_bind(mm_batch_t h, const ItemPlan &pl, const ItemWs &W, RunParams &p, void *stream) {
+    int rc = item_plan_check(h, pl);
+    if (!rc) rc = ensure_ws(h, W.total, stream);
+    if (rc) return rc;
+    p.ws_alpha = static_cast<float *>(h->ws);
+    p.ws_c = reinterpret_cast<double *>(static_cast<char *>(h->ws) + W.c);
+    bind_big(h, pl, p);
     return MM_OK;
 }
-// workspace of mm_arcposteriors_f32: the item kernel's alpha~ store and offsets, the float64 slot sums, the frame-1 posteriors
-static size_t arc_ws_bytes(mm_batch_t h, int64_t N, size_t off[3]) {
-    off[0] = align_up(size_t(h->total_s1p) * size_t(N + 1) * 4, 256);
-    off[1] = off[0] + ws_c_bytes(h, N);
-    off[2] = off[1] + align_up(size_t(h->arc_slots) * 8, 256);
-    return off[2] + align_up(size_t(h->total_s1p) * 4, 256);
+
+// The derived forms of a batch (arc forms, sampling forms): per FSM one blob that `pack` fills on the host, uploaded once per FSM
+// (f->*blob); per utterance one Dev that `describe` fills, uploaded once per batch (`descs`).  Made on the first call of the entry
+// that needs them, like the item forms: never during a stream capture.  A failed upload leaves nothing behind: the next call tries again.
+template <class Dev, class Pack, class Describe>
+static int ensure_derived_forms(mm_batch_t h, void *stream, const char *what, const char *who, DevMem &descs, DevMem mm_fsm_s::*blob, Pack pack,
+                                Describe describe) {
+    if (descs) return MM_OK;
+    if (capturing(stream))
+        return fail(MM_ERR_INVALID, std::string("the ") + what + " forms of this batch are not on the device yet: run " + who + " once outside a stream capture");
+    std::vector<Dev> host(size_t(h->B));
+    for (int64_t b = 0; b < h->B; ++b) {
+        mm_fsm_t f = h->fsms[size_t(b)];
+        if (f->nnz > INT32_MAX) return fail(MM_ERR_UNSUPPORTED, std::string(who) + ": more than 2^31 - 1 arcs in one FSM");
+        if (!(f->*blob)) {
+            Blob bl;
+            pack(f, bl);
+            const int rc = upload(bl, f->*blob);
+            if (rc) return rc;
+        }
+        host[size_t(b)] = describe(f);
+    }
+    void *d = nullptr;
+    HIP_TRY(hipMalloc(&d, sizeof(Dev) * host.size()));
+    DevMem own(d);
+    if (hipMemcpy(d, host.data(), sizeof(Dev) * host.size(), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(MM_ERR_HIP, std::string(who) + ": upload of the " + what + " descriptors failed");
+    descs = std::move(own);
+    return MM_OK;
+}
+extern "C" {
+
+// ---- arc posteriors (mm_kernel_arcs.hip)
+// the slot (slot row * 64 + lane) of the backward item form that holds each caller entry; -1: none
+static std::vector<int32_t> pack_k2slot(const mm_fsm_s &f) {
+    const Packed &pk = f.packed[1];  // (ensure_item_forms packed it)
+    std::vector<int32_t> k2slot(size_t(f.nnz), -1);
+    const std::vector<int64_t> &rowptr = f.mat[1].rowptr;
+    for (size_t it = 0; it < pk.items.size(); ++it) {
+        const ItemMeta &im = pk.items[it];
+        const int g = 1 << im.log2g;
+        for (int lane = 0; lane < 64; ++lane) {
+            const int32_t row = pk.rowinfo[it * 64 + size_t(lane)].row;
+            if (row < 0) continue;
+            // (pack_rows: lane `sub` of the row's group holds arcs sub, sub + g, ... in slots k = 0, 1, ...)
+            int64_t k = 0;
+            for (int64_t a = rowptr[size_t(row)] + (lane & (g - 1)); a < rowptr[size_t(row) + 1]; a += g, ++k)
+                k2slot[size_t(f.bwd_caller[size_t(a)])] = int32_t((int64_t(im.slot_row) + k) * 64 + lane);
+        }
+    }
+    return k2slot;
+}
+// The arc forms: per FSM k2slot and the initial states in init_idx order; per utterance an ArcDev with its first slot in the
+// float64 sums.
+static int ensure_arc_forms(mm_batch_t h, void *stream) {
+    int64_t slots = 0;
+    const int rc = ensure_derived_forms<ArcDev>(
+        h, stream, "arc", "mm_arcposteriors_f32", h->d_arcs, &mm_fsm_s::arc_blob,
+        [](mm_fsm_t f, Blob &bl) {
+            (void)bl.add(pack_k2slot(*f));  // (at 0)
+            (void)bl.add(f->init_order);
+        },
+        [&](mm_fsm_t f) {
+            const char *base = static_cast<const char *>(f->arc_blob.get());
+            const size_t o_i = align_up(size_t(f->nnz) * 4, 256);  // (where Blob::add put init_order, behind k2slot)
+            const ArcDev a{reinterpret_cast<const int *>(base), reinterpret_cast<const int *>(base + o_i), slots, int(f->nnz), int(f->init_order.size()),
+                           int(f->kphony), 0};
+            slots += f->packed[1].n_slot_rows * 64;
+            h->arc_max_nnz = std::max<int64_t>(h->arc_max_nnz, f->nnz);
+            h->arc_max_init = std::max<int64_t>(h->arc_max_init, int64_t(f->init_order.size()));
+            return a;
+        });
+    if (!rc && slots) h->arc_slots = slots;  // (0: they were up already)
+    return rc;
 }
 
 int mm_arcposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, float *counts,
                          int64_t csb, float *init_counts, int64_t isb, float *ttl, void *stream) {
-    if (h && h->semiring != MM_LOG)
-        return fail(MM_ERR_UNSUPPORTED, "mm_arcposteriors_f32: log-semiring batches only (this batch is " +
-                                            std::string(h->semiring == MM_TROPICAL ? "tropical" : "ProbSemiring") + ")");
-    int rc = check_run(h, "mm_arcposteriors_f32", V, N, MM_LOG);
-    if (rc) return rc;
-    if (!counts) return fail(MM_ERR_INVALID, "mm_arcposteriors_f32: counts is NULL");
-    // (the item forms first: a batch created without them has max_items = 0 until they are up, and pick_geometry would size the
-    // workgroups for no items)
-    rc = ensure_item_forms(h, stream);
+    ItemPlan pl;
+    int rc = item_entry_begin(h, "mm_arcposteriors_f32", ItemEntry::Arcs, V, N, stream,
+                              [&]() { return counts ? int(MM_OK) : fail(MM_ERR_INVALID, "mm_arcposteriors_f32: counts is NULL"); }, &pl);
     if (rc) return rc;
     rc = ensure_arc_forms(h, stream);
     if (rc) return rc;
@@ -3042,53 +3119,24 @@ int mm_arcposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
         return fail(MM_ERR_DIM, "mm_arcposteriors_f32: c_stride_b " + std::to_string(csb) + " < " + std::to_string(h->arc_max_nnz) + " entries of the largest FSM");
     if (init_counts && isb < h->arc_max_init)
         return fail(MM_ERR_DIM, "mm_arcposteriors_f32: i_stride_b " + std::to_string(isb) + " < " + std::to_string(h->arc_max_init) + " initial states of the largest FSM");
-    const Geometry g = pick_geometry(h);
-    const int NW = std::min(g.NW, 8);  // (mm_arc_kernel holds 8 items' arcs and their sums per wave: 8 waves per CU)
-    const int P1p = (h->max_P1 + 3) & ~3;
-    LdsPlan L = lds_plan(h->max_S1p, P1p, true);
-    const bool bigv = arcs_global(h);
-    if (bigv) {
-        if (!h->ws_big) return fail(MM_ERR_UNSUPPORTED, "FSM too large for the LDS and no global-memory vectors were allocated");
-        L = lds_plan(0, P1p, true);
-        if (size_t(L.total) * 4 > 160 * 1024) return fail(MM_ERR_UNSUPPORTED, "too many pdfs for the LDS: " + std::to_string(h->max_P1));
-    }
-    size_t off[3];
-    rc = ensure_ws(h, std::max(mm_batch_workspace_bytes(h, N), arc_ws_bytes(h, N, off)), stream);
+    const ItemWs W = item_ws_layout(h, pl, N);
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    rc = item_ws_bind(h, pl, W, p, stream);
     if (rc) return rc;
     char *ws = static_cast<char *>(h->ws);
-    RunParams p = run_params(h, V, vsb, vsn, lens, N);
-    p.ws_alpha = reinterpret_cast<float *>(ws);
-    p.ws_c = reinterpret_cast<double *>(ws + off[0]);
-    if (bigv) {
-        p.ws_big = h->ws_big;
-        p.big_stride = 4ll * h->max_S1p;
-    }
     ArcParams ap{};
-    ap.arcs = h->d_arcs;
-    ap.acc = reinterpret_cast<double *>(ws + off[1]);
-    ap.post1 = reinterpret_cast<float *>(ws + off[2]);
+    ap.arcs = static_cast<const ArcDev *>(h->d_arcs.get());
+    ap.acc = reinterpret_cast<double *>(ws + W.acc);
+    ap.post1 = reinterpret_cast<float *>(ws + W.post1);
     ap.counts = counts;
     ap.csb = csb;
     ap.init_counts = init_counts;
     ap.isb = isb;
     ap.ttl = ttl;
-    return mm_launch_arcs(h->B, NW, g.NI, bigv, size_t(L.total) * 4, p, ap, static_cast<hipStream_t>(stream));
+    return mm_launch_arcs(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, p, ap, static_cast<hipStream_t>(stream));
 }
 
 // ---- expected path cost and its gradient (mm_kernel_cost.hip)
-static bool cost_bigv(mm_batch_t h) {
-    return mm_cost_lds_bytes(h->max_S1p, (h->max_P1 + 3) & ~3) > 160 * 1024 || h->dbg.bigv || pick_geometry(h).NI == 0;
-}
-// workspace of mm_expectedcost_f32: the alpha~ store and its offsets as the item kernel keeps them, the r store and its offsets,
-// and for FSMs beyond the LDS the state vectors of both kernels ([B][8 * max S1p] floats)
-static size_t cost_ws_bytes(mm_batch_t h, int64_t N, bool bigv, size_t off[4]) {
-    const size_t rows = align_up(size_t(h->total_s1p) * size_t(N + 1) * 4, 256);
-    off[0] = rows;
-    off[1] = off[0] + ws_c_bytes(h, N);
-    off[2] = off[1] + rows;
-    off[3] = off[2] + ws_c_bytes(h, N);
-    return off[3] + (bigv ? align_up(size_t(h->B) * 8 * size_t(h->max_S1p) * 4, 256) : 0);
-}
 // an output laid out by three strides holds every element once: sorted by stride, each reaches past the extent of the one before
 static bool strides_hold(int64_t sb, int64_t B, int64_t sn, int64_t N, int64_t sp, int64_t P) {
     std::pair<int64_t, int64_t> d[3] = {{sb, B}, {sn, N}, {sp, P}};
@@ -3105,34 +3153,22 @@ static bool strides_hold(int64_t sb, int64_t B, int64_t sn, int64_t N, int64_t s
 int mm_expectedcost_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, const float *cost,
                         int64_t csb, int64_t csn, float *risk, float *grad, float *gamma, int64_t gsb, int64_t gsn, int64_t gsp, float *ttl,
                         void *stream) {
-    if (h && h->semiring != MM_LOG)
-        return fail(MM_ERR_UNSUPPORTED, "mm_expectedcost_f32: log-semiring batches only (this batch is " +
-                                            std::string(h->semiring == MM_TROPICAL ? "tropical" : "ProbSemiring") + ")");
-    int rc = check_run(h, "mm_expectedcost_f32", V, N, MM_LOG);
+    ItemPlan pl;
+    int rc = item_entry_begin(h, "mm_expectedcost_f32", ItemEntry::Cost, V, N, stream, [&]() {
+        if (!cost || !risk || !grad) return fail(MM_ERR_INVALID, "mm_expectedcost_f32: cost / risk / grad is NULL");
+        const int64_t P = h->max_P1 - 1;
+        if (csn < P) return fail(MM_ERR_DIM, "mm_expectedcost_f32: c_stride_n " + std::to_string(csn) + " < " + std::to_string(P) + " pdfs");
+        if (!strides_hold(gsb, h->B, gsn, N, gsp, P))
+            return fail(MM_ERR_DIM, "mm_expectedcost_f32: g strides (" + std::to_string(gsb) + ", " + std::to_string(gsn) + ", " + std::to_string(gsp) +
+                                        ") cannot hold " + std::to_string(h->B) + " x " + std::to_string(N) + " x " + std::to_string(P) + " elements");
+        return int(MM_OK);
+    }, &pl);
     if (rc) return rc;
-    if (!cost || !risk || !grad) return fail(MM_ERR_INVALID, "mm_expectedcost_f32: cost / risk / grad is NULL");
-    const int64_t P = h->max_P1 - 1;
-    if (csn < P) return fail(MM_ERR_DIM, "mm_expectedcost_f32: c_stride_n " + std::to_string(csn) + " < " + std::to_string(P) + " pdfs");
-    if (!strides_hold(gsb, h->B, gsn, N, gsp, P))
-        return fail(MM_ERR_DIM, "mm_expectedcost_f32: g strides (" + std::to_string(gsb) + ", " + std::to_string(gsn) + ", " + std::to_string(gsp) +
-                                    ") cannot hold " + std::to_string(h->B) + " x " + std::to_string(N) + " x " + std::to_string(P) + " elements");
-    // (the item forms first, as mm_arcposteriors_f32: pick_geometry sizes the workgroups by them)
-    rc = ensure_item_forms(h, stream);
-    if (rc) return rc;
-    const Geometry g = pick_geometry(h);
-    const int NW = std::min(g.NW, 8);  // (both kernels are compiled for 8 waves per CU: 8 items and the pair arithmetic per wave)
-    const int P1p = (h->max_P1 + 3) & ~3;
-    const bool bigv = cost_bigv(h);
-    const size_t lds = mm_cost_lds_bytes(bigv ? 0 : h->max_S1p, P1p);
-    if (lds > 160 * 1024) return fail(MM_ERR_UNSUPPORTED, "too many pdfs for the LDS: " + std::to_string(h->max_P1));
-    size_t off[4];
-    const size_t total = cost_ws_bytes(h, N, bigv, off);
-    rc = ensure_ws(h, std::max(mm_batch_workspace_bytes(h, N), total), stream);
+    const ItemWs W = item_ws_layout(h, pl, N);
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    rc = item_ws_bind(h, pl, W, p, stream);
     if (rc) return rc;
     char *ws = static_cast<char *>(h->ws);
-    RunParams p = run_params(h, V, vsb, vsn, lens, N);
-    p.ws_alpha = reinterpret_cast<float *>(ws);
-    p.ws_c = reinterpret_cast<double *>(ws + off[0]);
     CostParams cp{};
     cp.cost = cost;
     cp.csb = csb;
@@ -3144,119 +3180,78 @@ int mm_expectedcost_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, 
     cp.gsn = gsn;
     cp.gsp = gsp;
     cp.ttl = ttl;
-    cp.ws_r = reinterpret_cast<float *>(ws + off[1]);
-    cp.ws_o = reinterpret_cast<double *>(ws + off[2]);
-    if (bigv) {
-        cp.ws_big = reinterpret_cast<float *>(ws + off[3]);
+    cp.ws_r = reinterpret_cast<float *>(ws + W.r);
+    cp.ws_o = reinterpret_cast<double *>(ws + W.o);
+    if (pl.global) {
+        cp.ws_big = reinterpret_cast<float *>(ws + W.big);
         cp.big_stride = 8ll * h->max_S1p;
     }
-    return mm_launch_cost(h->B, NW, g.NI, bigv, lds, p, cp, static_cast<hipStream_t>(stream));
+    return mm_launch_cost(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, p, cp, static_cast<hipStream_t>(stream));
 }
 
 // ---- posterior path sampling (mm_kernel_sample.hip)
-// mm_sample_kernel keeps two alpha~ rows in LDS where they fit (and the item kernel's vectors do: BIGV batches gather from global memory)
-static bool sample_stages(mm_batch_t h) {
-    return !sample_global(h) && !h->dbg.sample_nostage && size_t(h->max_S1p) * 8 <= 160 * 1024;
-}
-// The sampling forms of a batch: per FSM, T_hat' by destination over the real states plus the omega column as lists of SampleRec
-// (source, log2 weight, the source's own list), parallel entries of one (source, destination) merged by log-add -- the draw and
-// the reported probability are over STATE sequences -- uploaded once per FSM; per utterance a SampleDev.  Made on the first
-// mm_samplepaths_f32 call, like the item and arc forms: never during a stream capture.
-static int ensure_sample_forms(mm_batch_t h, void *stream) {
-    if (h->d_samp) return MM_OK;
-    if (capturing(stream))
-        return fail(MM_ERR_INVALID, "the sampling forms of this batch are not on the device yet: run mm_samplepaths_f32 once outside a stream capture");
-    std::vector<SampleDev> forms(size_t(h->B));
-    for (int64_t b = 0; b < h->B; ++b) {
-        mm_fsm_t f = h->fsms[size_t(b)];
-        if (!f->samp_blob) {
-            if (f->nnz > INT32_MAX) return fail(MM_ERR_UNSUPPORTED, "mm_samplepaths_f32: more than 2^31 - 1 arcs in one FSM");
-            const Csr &m = f->mat[0];  // row j: the arcs into j, sources ascending
-            const int64_t S1 = f->S1, fin = S1 - 1;
-            const float NINF = -std::numeric_limits<float>::infinity();
-            std::vector<int32_t> start(size_t(S1) + 1, 0);
-            std::vector<SampleRec> recs;
-            recs.reserve(size_t(f->nnz));
-            for (int64_t j = 0; j < S1; ++j) {
-                start[size_t(j)] = int32_t(recs.size());
-                for (int64_t k = m.rowptr[size_t(j)]; k < m.rowptr[size_t(j) + 1];) {
-                    const int32_t i = m.col[size_t(k)];
-                    double mx = -std::numeric_limits<double>::infinity(), sum = 0.0;
-                    int64_t e = k;
-                    for (; e < m.rowptr[size_t(j) + 1] && m.col[size_t(e)] == i; ++e) mx = std::max(mx, double(m.val[size_t(e)]));
-                    for (int64_t q = k; q < e; ++q)
-                        if (m.val[size_t(q)] > NINF) sum += std::exp2(double(m.val[size_t(q)]) - mx);
-                    // (the phony final state is never a source: its self-loop is not part of any path of len_b frames)
-                    if (sum > 0.0 && i != fin) recs.push_back(SampleRec{i, float(mx + std::log2(sum)), 0, 0});
-                    k = e;
-                }
-            }
-            start[size_t(S1)] = int32_t(recs.size());
-            for (SampleRec &r : recs) {
-                r.start = start[size_t(r.src)];
-                r.deg = start[size_t(r.src) + 1] - r.start;
-            }
-            f->samp_fin_start = start[size_t(fin)];
-            f->samp_fin_deg = start[size_t(S1)] - start[size_t(fin)];
-            Blob bl;
-            (void)bl.add(recs);  // (at 0)
-            const int rc = upload(bl, f->samp_blob);
-            if (rc) return rc;
+// T_hat' by destination over the real states plus the omega column as lists of SampleRec (source, log2 weight, the source's own
+// list), parallel entries of one (source, destination) merged by log-add -- the draw and the reported probability are over STATE
+// sequences; *fin_start, *fin_deg: the list of the phony final state
+static std::vector<SampleRec> pack_sample_recs(const mm_fsm_s &f, int *fin_start, int *fin_deg) {
+    const Csr &m = f.mat[0];  // row j: the arcs into j, sources ascending
+    const int64_t S1 = f.S1, fin = S1 - 1;
+    const float NINF = -std::numeric_limits<float>::infinity();
+    std::vector<int32_t> start(size_t(S1) + 1, 0);
+    std::vector<SampleRec> recs;
+    recs.reserve(size_t(f.nnz));
+    for (int64_t j = 0; j < S1; ++j) {
+        start[size_t(j)] = int32_t(recs.size());
+        for (int64_t k = m.rowptr[size_t(j)]; k < m.rowptr[size_t(j) + 1];) {
+            const int32_t i = m.col[size_t(k)];
+            double mx = -std::numeric_limits<double>::infinity(), sum = 0.0;
+            int64_t e = k;
+            for (; e < m.rowptr[size_t(j) + 1] && m.col[size_t(e)] == i; ++e) mx = std::max(mx, double(m.val[size_t(e)]));
+            for (int64_t q = k; q < e; ++q)
+                if (m.val[size_t(q)] > NINF) sum += std::exp2(double(m.val[size_t(q)]) - mx);
+            // (the phony final state is never a source: its self-loop is not part of any path of len_b frames)
+            if (sum > 0.0 && i != fin) recs.push_back(SampleRec{i, float(mx + std::log2(sum)), 0, 0});
+            k = e;
         }
-        forms[size_t(b)] = SampleDev{static_cast<const SampleRec *>(f->samp_blob.get()), f->samp_fin_start, f->samp_fin_deg};
     }
-    void *d = nullptr;
-    HIP_TRY(hipMalloc(&d, sizeof(SampleDev) * size_t(h->B)));
-    if (hipMemcpy(d, forms.data(), sizeof(SampleDev) * size_t(h->B), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(d);
-        return fail(MM_ERR_HIP, "mm_samplepaths_f32: upload of the sampling descriptors failed");
+    start[size_t(S1)] = int32_t(recs.size());
+    for (SampleRec &r : recs) {
+        r.start = start[size_t(r.src)];
+        r.deg = start[size_t(r.src) + 1] - r.start;
     }
-    h->d_samp = static_cast<SampleDev *>(d);
-    return MM_OK;
+    *fin_start = start[size_t(fin)];
+    *fin_deg = start[size_t(S1)] - start[size_t(fin)];
+    return recs;
+}
+// The sampling forms: per FSM its SampleRec lists, per utterance a SampleDev.
+static int ensure_sample_forms(mm_batch_t h, void *stream) {
+    return ensure_derived_forms<SampleDev>(
+        h, stream, "sampling", "mm_samplepaths_f32", h->d_samp, &mm_fsm_s::samp_blob,
+        [](mm_fsm_t f, Blob &bl) { (void)bl.add(pack_sample_recs(*f, &f->samp_fin_start, &f->samp_fin_deg)); },  // (at 0)
+        [](mm_fsm_t f) { return SampleDev{static_cast<const SampleRec *>(f->samp_blob.get()), f->samp_fin_start, f->samp_fin_deg}; });
 }
 
 int mm_samplepaths_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, int64_t nsamples, int64_t seed,
                        int32_t *paths, int64_t psb, int64_t psk, float *logprob, int64_t lsb, float *ttl, void *stream) {
-    if (h && h->semiring != MM_LOG)
-        return fail(MM_ERR_UNSUPPORTED, "mm_samplepaths_f32: log-semiring batches only (this batch is " +
-                                            std::string(h->semiring == MM_TROPICAL ? "tropical" : "ProbSemiring") + ")");
-    int rc = check_run(h, "mm_samplepaths_f32", V, N, MM_LOG);
-    if (rc) return rc;
-    if (!paths) return fail(MM_ERR_INVALID, "mm_samplepaths_f32: paths is NULL");
-    if (nsamples < 1) return fail(MM_ERR_INVALID, "mm_samplepaths_f32: nsamples " + std::to_string(nsamples) + " < 1");
-    if (nsamples > INT32_MAX) return fail(MM_ERR_UNSUPPORTED, "mm_samplepaths_f32: more than 2^31 - 1 samples");
-    if (psk < N) return fail(MM_ERR_DIM, "mm_samplepaths_f32: path_stride_k " + std::to_string(psk) + " < N = " + std::to_string(N));
-    if (psb / nsamples < psk)
-        return fail(MM_ERR_DIM, "mm_samplepaths_f32: path_stride_b " + std::to_string(psb) + " < nsamples * path_stride_k");
-    if (logprob && lsb < nsamples) return fail(MM_ERR_DIM, "mm_samplepaths_f32: lp_stride_b " + std::to_string(lsb) + " < nsamples = " + std::to_string(nsamples));
-    // (the item forms first, as mm_arcposteriors_f32: pick_geometry sizes the workgroups by them)
-    rc = ensure_item_forms(h, stream);
+    ItemPlan pl;
+    int rc = item_entry_begin(h, "mm_samplepaths_f32", ItemEntry::Sample, V, N, stream, [&]() {
+        if (!paths) return fail(MM_ERR_INVALID, "mm_samplepaths_f32: paths is NULL");
+        if (nsamples < 1) return fail(MM_ERR_INVALID, "mm_samplepaths_f32: nsamples " + std::to_string(nsamples) + " < 1");
+        if (nsamples > INT32_MAX) return fail(MM_ERR_UNSUPPORTED, "mm_samplepaths_f32: more than 2^31 - 1 samples");
+        if (psk < N) return fail(MM_ERR_DIM, "mm_samplepaths_f32: path_stride_k " + std::to_string(psk) + " < N = " + std::to_string(N));
+        if (psb / nsamples < psk)
+            return fail(MM_ERR_DIM, "mm_samplepaths_f32: path_stride_b " + std::to_string(psb) + " < nsamples * path_stride_k");
+        if (logprob && lsb < nsamples) return fail(MM_ERR_DIM, "mm_samplepaths_f32: lp_stride_b " + std::to_string(lsb) + " < nsamples = " + std::to_string(nsamples));
+        return int(MM_OK);
+    }, &pl);
     if (rc) return rc;
     rc = ensure_sample_forms(h, stream);
     if (rc) return rc;
-    const Geometry g = pick_geometry(h);
-    const int P1p = (h->max_P1 + 3) & ~3;
-    LdsPlan L = lds_plan(h->max_S1p, P1p, true);
-    const bool bigv = sample_global(h);
-    if (bigv) {
-        if (!h->ws_big) return fail(MM_ERR_UNSUPPORTED, "FSM too large for the LDS and no global-memory vectors were allocated");
-        L = lds_plan(0, P1p, true);
-        if (size_t(L.total) * 4 > 160 * 1024) return fail(MM_ERR_UNSUPPORTED, "too many pdfs for the LDS: " + std::to_string(h->max_P1));
-    }
-    // workspace: the item kernel's alpha~ store and offsets
-    const size_t off_c = align_up(size_t(h->total_s1p) * size_t(N + 1) * 4, 256);
-    rc = ensure_ws(h, std::max(mm_batch_workspace_bytes(h, N), off_c + ws_c_bytes(h, N)), stream);
-    if (rc) return rc;
-    char *ws = static_cast<char *>(h->ws);
     RunParams p = run_params(h, V, vsb, vsn, lens, N);
-    p.ws_alpha = reinterpret_cast<float *>(ws);
-    p.ws_c = reinterpret_cast<double *>(ws + off_c);
-    if (bigv) {
-        p.ws_big = h->ws_big;
-        p.big_stride = 4ll * h->max_S1p;
-    }
+    rc = item_ws_bind(h, pl, item_ws_layout(h, pl, N), p, stream);
+    if (rc) return rc;
     SampleParams sp{};
-    sp.forms = h->d_samp;
+    sp.forms = static_cast<const SampleDev *>(h->d_samp.get());
     sp.paths = paths;
     sp.psb = psb;
     sp.psk = psk;
@@ -3266,7 +3261,7 @@ int mm_samplepaths_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, c
     sp.K = int(nsamples);
     sp.key0 = unsigned(uint64_t(seed));
     sp.key1 = unsigned(uint64_t(seed) >> 32);
-    return mm_launch_sample(h->B, g.NW, g.NI, bigv, size_t(L.total) * 4, sample_stages(h), h->max_S1p, h->n_cus, p, sp, static_cast<hipStream_t>(stream));
+    return mm_launch_sample(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, pl.stage, h->max_S1p, h->n_cus, p, sp, static_cast<hipStream_t>(stream));
 }
 
 // alpha / beta export on the pair kernels (mm_pairs_tu.hip: mm_fbx_kernel + mm_pair_export_kernel): one shared graph in the pair
@@ -3342,9 +3337,9 @@ static int run_export(mm_batch_t h, int mode, const float *V, int64_t vsb, int64
     }
     if (h->semiring == MM_TROPICAL) {
         if (mode == MODE_ALPHA) return launch_tropical(h, p, stream);
-        const Geometry g = pick_geometry(h);
-        if (g.NI == 0) return launch(mm_log_kernel<MODE_BETA, 0, 0, true, false>, mm_log_kernel<MODE_BETA, 0, 0, true, true>, h, p, false, g.NW, stream);
-        return launch(mm_log_kernel<MODE_BETA, 8, 0, true, false>, mm_log_kernel<MODE_BETA, 8, 0, true, true>, h, p, false, g.NW, stream);
+        const ItemPlan g = item_plan(h, ItemEntry::Export);
+        if (g.NI == 0) return launch(mm_log_kernel<MODE_BETA, 0, 0, true, false>, mm_log_kernel<MODE_BETA, 0, 0, true, true>, h, p, g.e, g.NW, stream);
+        return launch(mm_log_kernel<MODE_BETA, 8, 0, true, false>, mm_log_kernel<MODE_BETA, 8, 0, true, true>, h, p, g.e, g.NW, stream);
     }
     if (mode == MODE_ALPHA) return launch_log<MODE_ALPHA>(h, p, stream);
     return launch_log<MODE_BETA>(h, p, stream);

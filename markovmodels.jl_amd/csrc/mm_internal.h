@@ -152,7 +152,7 @@ struct QuadLaunch {
 int mm_launch_quad_pass(int pass, const QuadLaunch &ql, const RunParams &p, hipStream_t stream);
 
 // ---- arc posteriors (mm_arcs_tu.hip: mm_log_kernel's forward half, then mm_arc_kernel and mm_arc_scatter_kernel on the item form)
-struct ArcDev {  // one FSM's arc form (mm_engine.hip ensure_arc_forms)
+struct ArcDev {  // one utterance's arc form (mm_engine.hip ensure_arc_forms)
     const int *k2slot;       // [nnz] caller entry -> slot (slot row * 64 + lane) of the backward item form; -1: none
     const int *init_states;  // [n_init] the states of alpha_hat in the caller's init_idx order
     long long slot_off;      // this utterance's first slot in ArcParams::acc
@@ -170,6 +170,8 @@ struct ArcParams {
     long long isb;
     float *ttl;          // NULL: not asked for
 };
+// LDS bytes of mm_arc_kernel behind the item kernel's plan: the per-wave posterior sums of two frames
+#define MM_ARC_LDS_EXTRA (2 * MM_MAX_WAVES * sizeof(float))
 // NI: register-resident items per wave (8, or 0 for FSMs of more than 65534 states); bigv: the state vectors in global memory
 int mm_launch_arcs(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, const RunParams &p, const ArcParams &ap, hipStream_t stream);
 
