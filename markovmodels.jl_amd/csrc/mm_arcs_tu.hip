@@ -8,16 +8,8 @@ namespace mm {
 
 template <int NI, bool BIGV>
 static int launch_arcs_ni(int64_t B, int NW, size_t lds, const RunParams &p, const ArcParams &ap, hipStream_t stream) {
-    auto fwd = mm_log_kernel<MODE_FB, NI, 1, false, BIGV>;
-    auto bwd = mm_arc_kernel<NI, BIGV>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fwd), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-    hipLaunchKernelGGL(fwd, dim3(unsigned(B)), dim3(64 * NW), lds, stream, p);
-    HIP_TRY(hipGetLastError());
-    const size_t lds_b = lds + MM_ARC_LDS_EXTRA;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bwd), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_b)));
-    hipLaunchKernelGGL(bwd, dim3(unsigned(B)), dim3(64 * NW), lds_b, stream, p, ap);
-    HIP_TRY(hipGetLastError());
-    return MM_OK;
+    const int rc = mm_launch(mm_log_kernel<MODE_FB, NI, 1, false, BIGV>, dim3(unsigned(B)), dim3(64 * NW), lds, stream, p);
+    return rc ? rc : mm_launch(mm_arc_kernel<NI, BIGV>, dim3(unsigned(B)), dim3(64 * NW), lds + MM_ARC_LDS_EXTRA, stream, p, ap);
 }
 
 int mm_launch_arcs(int64_t B, int NW, int NI, bool bigv, size_t lds, const RunParams &p, const ArcParams &ap, hipStream_t stream) {
@@ -25,10 +17,7 @@ int mm_launch_arcs(int64_t B, int NW, int NI, bool bigv, size_t lds, const RunPa
     if (NI == 8) rc = bigv ? launch_arcs_ni<8, true>(B, NW, lds, p, ap, stream) : launch_arcs_ni<8, false>(B, NW, lds, p, ap, stream);
     else if (NI == 0 && bigv) rc = launch_arcs_ni<0, true>(B, NW, lds, p, ap, stream);
     else return mm_fail(MM_ERR_UNSUPPORTED, "arc posteriors: no instance for this geometry");
-    if (rc) return rc;
-    hipLaunchKernelGGL(mm_arc_scatter_kernel, dim3(unsigned(B), 4), dim3(256), 0, stream, p, ap);
-    HIP_TRY(hipGetLastError());
-    return MM_OK;
+    return rc ? rc : mm_launch(mm_arc_scatter_kernel, dim3(unsigned(B), 4), dim3(256), 0, stream, p, ap);
 }
 
 }  // namespace mm

@@ -10,15 +10,8 @@ size_t mm_cost_lds_bytes(int S1p, int P1p) { return size_t(cost_lds_plan(S1p, P1
 
 template <int NI, bool BIGV>
 static int launch_cost_ni(int64_t B, int NW, size_t lds, const RunParams &p, const CostParams &cp, hipStream_t stream) {
-    auto fwd = mm_cost_fwd_kernel<NI, BIGV>;
-    auto bwd = mm_cost_bwd_kernel<NI, BIGV>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fwd), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-    hipLaunchKernelGGL(fwd, dim3(unsigned(B)), dim3(64 * NW), lds, stream, p, cp);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(bwd), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-    hipLaunchKernelGGL(bwd, dim3(unsigned(B)), dim3(64 * NW), lds, stream, p, cp);
-    HIP_TRY(hipGetLastError());
-    return MM_OK;
+    const int rc = mm_launch(mm_cost_fwd_kernel<NI, BIGV>, dim3(unsigned(B)), dim3(64 * NW), lds, stream, p, cp);
+    return rc ? rc : mm_launch(mm_cost_bwd_kernel<NI, BIGV>, dim3(unsigned(B)), dim3(64 * NW), lds, stream, p, cp);
 }
 
 int mm_launch_cost(int64_t B, int NW, int NI, bool bigv, size_t lds, const RunParams &p, const CostParams &cp, hipStream_t stream) {

@@ -440,7 +440,7 @@ struct ItemPlan {
 // `global` never depends on max_items, nor does NI except Tropical's (8: the whole graph is register-resident): mm_batch_create
 // asks before the item forms are up, and ensure_item_forms raises max_items later -- only NW follows it.
 static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
-    const size_t lds_max = 160 * 1024;
+    const size_t lds_max = MM_LDS_MAX;
     const Geometry g = pick_geometry(h);
     const int P1p = (h->max_P1 + 3) & ~3;
     auto bytes = [&](int S1p) {
@@ -466,7 +466,7 @@ static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
 static int item_plan_check(mm_batch_t h, const ItemPlan &pl) {
     if (pl.global && pl.e != ItemEntry::Cost && !h->ws_big)
         return fail(MM_ERR_UNSUPPORTED, "FSM too large for the LDS and no global-memory vectors were allocated");
-    return pl.lds_bytes > 160 * 1024 ? fail(MM_ERR_UNSUPPORTED, "too many pdfs for the LDS: " + std::to_string(h->max_P1)) : int(MM_OK);
+    return pl.lds_bytes > MM_LDS_MAX ? fail(MM_ERR_UNSUPPORTED, "too many pdfs for the LDS: " + std::to_string(h->max_P1)) : int(MM_OK);
 }
 static void bind_big(mm_batch_t h, const ItemPlan &pl, RunParams &p) {
     if (!pl.global || pl.e == ItemEntry::Cost) return;
@@ -516,10 +516,7 @@ static int launch(K kernel, K big, mm_batch_t h, const RunParams &p0, ItemEntry 
     p.deterministic = h->deterministic ? 1 : 0;
     if (pl.global) kernel = big;
     bind_big(h, pl, p);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(pl.lds_bytes)));
-    hipLaunchKernelGGL(kernel, dim3(unsigned(h->B)), dim3(64 * NW), pl.lds_bytes, static_cast<hipStream_t>(stream), p);
-    HIP_TRY(hipGetLastError());
-    return MM_OK;
+    return mm_launch(kernel, dim3(unsigned(h->B)), dim3(64 * NW), pl.lds_bytes, static_cast<hipStream_t>(stream), p);
 }
 
 template <int MODE, bool TROP = false>
@@ -551,7 +548,7 @@ static bool quad_kernel_usable(mm_batch_t h) {
     // small deep graphs (numerators): measured on the reference's WSJ numerator graph (depth 165),
     // item kernel 2.3 ms against 2.7 ms; shallow graphs of the same size are 1.6x faster on the quad kernels
     if (h->max_depth >= 64 && h->geo_kq[0] <= 3 && h->geo_kq[1] <= 3 && h->dbg.kernel == DebugOpts::K_AUTO) return false;
-    return quad_lds_bytes(h, 0) <= 160 * 1024 && quad_lds_bytes(h, 1) <= 160 * 1024;
+    return quad_lds_bytes(h, 0) <= MM_LDS_MAX && quad_lds_bytes(h, 1) <= MM_LDS_MAX;
 }
 
 // (the quad kernels' instances live in mm_quad_tu.hip)
@@ -586,12 +583,8 @@ static const int kRowKA[] = {24, 40, 42, 44};  // instantiated register windows 
 template <int KA, int PASS>
 static int launch_row_ka(mm_batch_t h, const RunParams &p, void *stream) {
     const size_t lds = row_lds_bytes(MM_ROW_RS, PASS, h->row_slotrows[PASS]);
-    if (lds > 160 * 1024) return fail(MM_ERR_UNSUPPORTED, "row kernel: LDS");
-    auto kernel = mm_fbr_kernel<KA, MM_ROW_RS, PASS>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-    hipLaunchKernelGGL(kernel, dim3(unsigned(h->B)), dim3(64 * (h->row_nwc[PASS] + 1)), lds, static_cast<hipStream_t>(stream), p);
-    HIP_TRY(hipGetLastError());
-    return MM_OK;
+    if (lds > MM_LDS_MAX) return fail(MM_ERR_UNSUPPORTED, "row kernel: LDS");
+    return mm_launch(mm_fbr_kernel<KA, MM_ROW_RS, PASS>, dim3(unsigned(h->B)), dim3(64 * (h->row_nwc[PASS] + 1)), lds, static_cast<hipStream_t>(stream), p);
 }
 template <int PASS>
 static int launch_row_pass(mm_batch_t h, const RunParams &p, void *stream) {
@@ -2051,7 +2044,7 @@ static int pick_family(mm_batch_t h, const mm_fsm_t *fsms, const int64_t nq_max[
             h->pair_ka = std::max(fsms[0]->prows.form[0].g.KA, fsms[0]->prows.form[1].g.KA);
             h->pair_nwc = std::max(fsms[0]->prows.form[0].g.NWC, fsms[0]->prows.form[1].g.NWC);
             h->pair_slotrows = std::max(fsms[0]->prows.form[0].g.nslotrows, fsms[0]->prows.form[1].g.nslotrows);
-            pairs = h->pair_ka <= MM_PAIR_KA && mm_pair_lds_bytes(1, h->pair_slotrows, h->max_P1) <= 160 * 1024;
+            pairs = h->pair_ka <= MM_PAIR_KA && mm_pair_lds_bytes(1, h->pair_slotrows, h->max_P1) <= MM_LDS_MAX;
         }
     }
     // split pair kernels: one shared FSM that is too large for the pair kernels proper (more arcs than the registers of a
@@ -2078,7 +2071,7 @@ static int pick_family(mm_batch_t h, const mm_fsm_t *fsms, const int64_t nq_max[
                 }
             h->split_s1p = (f0->split.total + 2 + 3) & ~3;
             const size_t lds = mm_split_lds_bytes(h->pair_H, 1, h->pair_slotrows, h->max_P1);
-            pairs = h->pair_ka <= mm_split_ka(h->pair_H) && h->pair_nwc <= MM_SPLIT_NWC && lds > 0 && lds <= 160 * 1024;
+            pairs = h->pair_ka <= mm_split_ka(h->pair_H) && h->pair_nwc <= MM_SPLIT_NWC && lds > 0 && lds <= MM_LDS_MAX;
             if (h->dbg.verbose) fprintf(stderr, "[mm] teams of %d: LDS %zu bytes in phase B\n", h->pair_H, lds);
             if (!pairs) h->pair_H = 1;
         }

@@ -1,6 +1,8 @@
 // mm_internal.h -- what the translation units of the engine share on the host side (not part of the C ABI).
 // mm_engine.hip holds the C ABI, the handles and the item / quad / row kernels; kernel families with many template
 // instances live in translation units of their own (compiled in parallel, see Makefile) behind plain launch functions.
+// Every launch with dynamic LDS, in all of them, goes through mm_launch below and asks MM_LDS_MAX what fits; the four
+// translation units of the pair family share their geometry, team placement and launch sequence (end of mm_kernel_pairs.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,6 +27,18 @@ int mm_fail(int code, const std::string &msg);
             return ::mm::mm_fail(MM_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
     } while (0)
 
+#define MM_LDS_MAX (size_t(160 * 1024))  // LDS bytes of a compute unit: what one workgroup can ask for
+// The one launch: raises the kernel's dynamic-LDS limit to lds_bytes (on every launch: nothing is remembered), launches, and
+// returns MM_OK or the mm_fail of the HIP error.  (lds_bytes 0: a kernel without dynamic LDS has no limit to raise)
+// (static: an instance per translation unit, none among the library's dynamic symbols)
+template <typename... P, typename... A>
+static int mm_launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const A &...args) {
+    if (lds_bytes) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds_bytes)));
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
+    HIP_TRY(hipGetLastError());
+    return MM_OK;
+}
+
 #define MM_ROW_RS 8192  // LDS bytes of one copy of the linear vector (row kernels) / half a pair vector (pair kernels)
 #define MM_PAIR_KA 44   // arc slots per lane of the pair kernels
 // pdfs (+ 1) of the pair / split pair / float64 pair kernels: passes of 64 lanes of their service waves (the NJ of the instances),
@@ -46,10 +60,10 @@ inline int mm_pair_xps(int P1, int H = 1) { const int nj = mm_pair_nj(P1, H); re
 // what the LDS of a compute unit holds next to two such vectors
 #define MM_SPLIT8_RS 24320
 #define MM_SPLIT8_RSH 6144
-inline int mm_split_rs(int H) { return H == 8 ? MM_SPLIT8_RS : (H == 4 ? MM_SPLIT4_RS : MM_SPLIT_RS); }
-inline int mm_split_ka(int H) { return H == 8 ? 36 : 36; }  // arc slots per lane (teams of 8: fewer arcs per workgroup, and more registers to the exchange)
-inline int mm_split_rsh(int H) { return H == 8 ? MM_SPLIT8_RSH : (H == 4 ? MM_SPLIT4_RSH : MM_SPLIT_RSH); }
-#define MM_SPLIT_KA 36
+// (the geometry of a team of H: template arguments of the team kernels of mm_split_tu.hip, mm_dpair_tu.hip and mm_wpair_tu.hip)
+constexpr int mm_split_rs(int H) { return H == 8 ? MM_SPLIT8_RS : (H == 4 ? MM_SPLIT4_RS : MM_SPLIT_RS); }
+constexpr int mm_split_ka(int) { return 36; }  // arc slots per lane, whatever the team
+constexpr int mm_split_rsh(int H) { return H == 8 ? MM_SPLIT8_RSH : (H == 4 ? MM_SPLIT4_RSH : MM_SPLIT_RSH); }
 #define MM_SPLIT_NWC 14
 
 // ---- generic path (mm_generic.hip): any semiring, float32 or float64, any C_hat / V_hat

@@ -25,6 +25,8 @@
 // reference (:157-158), and log Z of a frame = log2(sum) + the two agents' cumulative offsets (double), ttl = the
 // minimum over the frames (:159).
 #pragma once
+#include <algorithm>
+#include "mm_internal.h"
 #include "mm_kernel_rows.hip"
 
 namespace mm {
@@ -1870,6 +1872,43 @@ static __global__ void __launch_bounds__(1024) mm_pair_export_kernel(RunParams p
             }
         __syncthreads();
     }
+}
+
+// ---- what the translation units of the pair family share (mm_pairs_tu.hip, mm_split_tu.hip, mm_dpair_tu.hip, mm_wpair_tu.hip):
+// where a team's workgroups sit in a grid, one phase, the sequence of a call, the export's layout pass.
+// Workgroup blk of one direction's part of a grid -> (pair or utterance, set of the team), and the workgroups that takes for n
+// pairs or utterances.  Workgroups b and b + 8 have been seen to share an XCD (its L2): the workgroups of a team are 8 apart, so
+// their exchange stays inside one L2 where that holds (speed only; any placement is correct).  A direction's part is a multiple
+// of 8 H workgroups: the block -> XCD pattern is the same in both.
+struct TeamPos { int idx, hset; };
+template <int H>
+__device__ __forceinline__ TeamPos team_pos(int blk) { return {(blk / (8 * H)) * 8 + (blk & 7), (blk >> 3) % H}; }
+static inline unsigned team_grid(unsigned n, int H) { return (n + 7) / 8 * 8 * unsigned(H); }
+static inline unsigned pair_count(const PairLaunch &pl) { return unsigned((pl.B + 1) / 2); }
+// One phase (or the export's one direction): `lds` bytes of dynamic LDS, `waves` waves per workgroup; `what` names the kernels in
+// the refusal.
+template <typename K, typename... A>
+static int pair_launch_phase(K kernel, const char *what, size_t lds, unsigned grid, int waves, hipStream_t st, const A &...args) {
+    if (lds > MM_LDS_MAX) return mm_fail(MM_ERR_UNSUPPORTED, std::string(what) + ": LDS");
+    return mm_launch(kernel, dim3(grid), dim3(64 * waves), lds, st, args...);
+}
+// A call: phase A, phase B, the finish kernel.  (phase B of either direction needs phase A of both: stream order)
+typedef int (*PairPhaseFn)(const PairLaunch &, const RunParams &, hipStream_t);
+static int pair_launch_phases(PairPhaseFn phase_a, PairPhaseFn phase_b, void (*finish)(RunParams), const PairLaunch &pl, const RunParams &p,
+                              hipStream_t s0) {
+    int rc = phase_a(pl, p, s0);
+    if (!rc) rc = phase_b(pl, p, s0);
+    if (rc) return rc;
+    return mm_launch(finish, dim3(unsigned(pl.B)), dim3(256), 0, s0, p);
+}
+// The export's second launch: the stored rows -> the reference's layout, by (pairs, chunks of frames) workgroups, enough of them
+// to keep the memory system busy
+static int pair_launch_export_layout(const PairLaunch &pl, const RunParams &p, int dir, hipStream_t st) {
+    const unsigned npairs = pair_count(pl);
+    const int chunks = std::max(1, std::min(p.N + 1, int(4096 / std::max(1u, npairs))));
+    const int fpb = (p.N + 1 + chunks - 1) / chunks;
+    return mm_launch(mm_pair_export_kernel, dim3(npairs, unsigned((p.N + 1 + fpb - 1) / fpb)), dim3(1024), size_t(3) * size_t(p.pair_s1p) * 4, st, p,
+                     dir, fpb, pl.H);
 }
 
 }  // namespace mm

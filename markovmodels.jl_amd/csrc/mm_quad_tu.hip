@@ -7,13 +7,7 @@ namespace mm {
 
 template <int KQ, int RPT, int PASS>
 static int launch_quad_kq_rpt(const QuadLaunch *h, const RunParams &p, hipStream_t stream) {
-    const size_t lds = h->lds;
-    auto kernel = mm_fbq_kernel<KQ, RPT, PASS>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                int(lds)));
-    hipLaunchKernelGGL(kernel, dim3(unsigned(h->B)), dim3(64 * h->nw), lds, stream, p);
-    HIP_TRY(hipGetLastError());
-    return MM_OK;
+    return mm_launch(mm_fbq_kernel<KQ, RPT, PASS>, dim3(unsigned(h->B)), dim3(64 * h->nw), h->lds, stream, p);
 }
 
 template <int KQ, int PASS>

@@ -8,23 +8,15 @@ namespace mm {
 
 template <int NI, bool BIGV>
 static int launch_sample_fwd(int64_t B, int NW, size_t lds, const RunParams &p, hipStream_t stream) {
-    auto fwd = mm_log_kernel<MODE_FB, NI, 1, false, BIGV>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(fwd), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-    hipLaunchKernelGGL(fwd, dim3(unsigned(B)), dim3(64 * NW), lds, stream, p);
-    HIP_TRY(hipGetLastError());
-    return MM_OK;
+    return mm_launch(mm_log_kernel<MODE_FB, NI, 1, false, BIGV>, dim3(unsigned(B)), dim3(64 * NW), lds, stream, p);
 }
 
 template <bool STAGE, int CW>
 static int launch_sample_walk(int64_t B, int max_S1p, const RunParams &p, const SampleParams &sp, hipStream_t stream) {
-    auto walk = mm_sample_kernel<STAGE, CW>;
     const size_t lds = STAGE ? size_t(2) * size_t(max_S1p) * sizeof(float) : 0;
     const unsigned groups = unsigned((sp.K + MM_SAMPLE_NW * CW - 1) / (MM_SAMPLE_NW * CW));
     if (groups > 65535u) return mm_fail(MM_ERR_UNSUPPORTED, "mm_samplepaths_f32: more than " + std::to_string(65535 * MM_SAMPLE_NW * CW) + " samples in one call");
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(walk), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-    hipLaunchKernelGGL(walk, dim3(unsigned(B), groups), dim3(64 * (MM_SAMPLE_NW + 1)), lds, stream, p, sp);
-    HIP_TRY(hipGetLastError());
-    return MM_OK;
+    return mm_launch(mm_sample_kernel<STAGE, CW>, dim3(unsigned(B), groups), dim3(64 * (MM_SAMPLE_NW + 1)), lds, stream, p, sp);
 }
 
 // chains per wave: the fewest for which every workgroup of the call is resident at once (two workgroups per compute unit)

@@ -192,7 +192,7 @@ int mm_stream_build(int64_t S1, int32_t P1, const int64_t *const rowptr[2], cons
     *out = nullptr;
     if (H != 1 && H != 2 && H != 4) return MM_OK;
     // (16-bit LDS byte offsets in the records: 4 * position <= 65 532, positions include up to 12 of padding)
-    if (S1 < 2 || S1 > 16370 || P1 > 1024 || mm_stream_lds_bytes(int(S1), P1) > 160 * 1024) return MM_OK;
+    if (S1 < 2 || S1 > 16370 || P1 > 1024 || mm_stream_lds_bytes(int(S1), P1) > MM_LDS_MAX) return MM_OK;
     auto f = std::make_unique<StreamForm>();
     f->S1 = int(S1);
     f->P1 = P1;
@@ -825,23 +825,17 @@ static __global__ void __launch_bounds__(256) mm_stream_finish_kernel(RunParams 
 // both recursions in ONE grid when the chip holds them (2 B H workgroups of one per compute unit), else one grid per direction
 template <int NJ, int H>
 static int launch_stream_nj(int64_t B, int n_cus, size_t lds, const RunParams &p, hipStream_t st) {
-    auto k = mm_stream_kernel<NJ, H>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-    auto grid = [&](int64_t teams) { return dim3(unsigned(H > 1 ? (teams + 7) / 8 * 8 * H : teams)); };  // (teams: groups of 8, their workgroups 8 apart)
+    // (teams: groups of 8, their workgroups 8 apart -- team_grid, mm_kernel_pairs.hip)
+    auto run = [&](int64_t teams, int dir) { return mm_launch(mm_stream_kernel<NJ, H>, dim3(H > 1 ? team_grid(unsigned(teams), H) : unsigned(teams)), dim3(1024), lds, st, p, dir); };
+    int rc;
     if (2 * B * H <= int64_t(n_cus) || H > 1) {  // (a team's workgroups must run together: H > 1 is chosen only when everything fits, mm_stream_pick_h)
-        hipLaunchKernelGGL(k, grid(2 * B), dim3(1024), lds, st, p, -1);
-        HIP_TRY(hipGetLastError());
+        rc = run(2 * B, -1);
     } else {
-        hipLaunchKernelGGL(k, grid(B), dim3(1024), lds, st, p, 0);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k, grid(B), dim3(1024), lds, st, p, 1);
-        HIP_TRY(hipGetLastError());
+        rc = run(B, 0);
+        if (!rc) rc = run(B, 1);
     }
-    hipLaunchKernelGGL(mm_stream_combine_kernel, dim3(unsigned(B), unsigned((p.N + kStreamCombineFrames - 1) / kStreamCombineFrames)), dim3(1024), 0, st, p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(mm_stream_finish_kernel, dim3(unsigned(B)), dim3(256), 0, st, p);
-    HIP_TRY(hipGetLastError());
-    return MM_OK;
+    if (!rc) rc = mm_launch(mm_stream_combine_kernel, dim3(unsigned(B), unsigned((p.N + kStreamCombineFrames - 1) / kStreamCombineFrames)), dim3(1024), 0, st, p);
+    return rc ? rc : mm_launch(mm_stream_finish_kernel, dim3(unsigned(B)), dim3(256), 0, st, p);
 }
 // workgroups per team for a batch of B utterances on n_cus compute units: as many as leave every workgroup of both directions its own
 // compute unit (B = 64 on 256: 2; B <= 32: 4)
@@ -860,7 +854,7 @@ size_t mm_stream_slot(int max_S1) { return (size_t(max_S1) + 16 + 63) & ~size_t(
 size_t mm_stream_exchange_bytes(int64_t B, int H, int max_S1) { return H > 1 ? ((size_t(B) * 4 * mm_stream_slot(max_S1) * 4 + 255) & ~size_t(255)) : 0; }
 int mm_launch_stream(int64_t B, int n_cus, int max_S1, int max_P1, int H, const RunParams &p, hipStream_t st) {
     const size_t lds = mm_stream_lds_bytes(max_S1, max_P1);
-    if (lds > 160 * 1024 || max_P1 > 1024) return mm_fail(MM_ERR_UNSUPPORTED, "stream kernel: LDS");
+    if (lds > MM_LDS_MAX || max_P1 > 1024) return mm_fail(MM_ERR_UNSUPPORTED, "stream kernel: LDS");
     if ((p.N + kStreamCombineFrames - 1) / kStreamCombineFrames > 65535) return mm_fail(MM_ERR_UNSUPPORTED, "stream kernel: more than 524 280 frames");
 #define MM_STREAM_CASE(NJ_)                                                          \
     case NJ_:                                                                        \

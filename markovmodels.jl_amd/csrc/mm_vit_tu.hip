@@ -8,11 +8,7 @@ namespace mm {
 template <int N4, int N2, int NJ, int VSZ>
 static int launch_vit(const VitLaunch &vl, const RunParams &p, hipStream_t stream) {
     const size_t lds = 2 * size_t(VSZ) + 2 * size_t(MM_VIT_ESZ) + 4 * size_t(NJ) * 256;
-    auto kernel = mm_vit_kernel<N4, N2, NJ, VSZ>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-    hipLaunchKernelGGL(kernel, dim3(unsigned(vl.B)), dim3(1024), lds, stream, p);
-    HIP_TRY(hipGetLastError());
-    return MM_OK;
+    return mm_launch(mm_vit_kernel<N4, N2, NJ, VSZ>, dim3(unsigned(vl.B)), dim3(1024), lds, stream, p);
 }
 template <int N4, int N2>
 static int launch_vit_shape(const VitLaunch &vl, const RunParams &p, hipStream_t stream) {
@@ -33,22 +29,14 @@ int mm_launch_viterbi(const VitLaunch &vl, const RunParams &p, hipStream_t strea
     // 2 x 4 rows, the graph's row pointers and sources
     const int RSB = vl.bp_row;  // (the row stride the forward kernel wrote with)
     const size_t csr = (size_t(vl.max_S1p + 1) * 4 + size_t(vl.max_arcs) * 2 + 15) & ~size_t(15);
-    const size_t budget = 160 * 1024;
+    const size_t budget = MM_LDS_MAX;
     const bool csrl = csr + 2 * (4 * size_t(RSB) + 1024) <= budget;
     const size_t room = budget - (csrl ? csr : 0) - 2 * 1024;  // (every buffer of the ring has a spare KB: mm_vit_backtrace_kernel)
     int R = int(room / (2 * size_t(RSB)));
     R = R > 64 ? 64 : R;
     if (R < 1) return mm_fail(MM_ERR_UNSUPPORTED, "Viterbi back-trace: a row of back-pointers does not fit the LDS");
     const size_t lds = (csrl ? csr : 0) + 2 * (size_t(R) * size_t(RSB) + 1024);
-    if (csrl) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(mm_vit_backtrace_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-        hipLaunchKernelGGL(mm_vit_backtrace_kernel<true>, dim3(unsigned(vl.B)), dim3(512), lds, stream, p, R, RSB);
-    } else {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(mm_vit_backtrace_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-        hipLaunchKernelGGL(mm_vit_backtrace_kernel<false>, dim3(unsigned(vl.B)), dim3(512), lds, stream, p, R, RSB);
-    }
-    HIP_TRY(hipGetLastError());
-    return MM_OK;
+    return mm_launch(csrl ? mm_vit_backtrace_kernel<true> : mm_vit_backtrace_kernel<false>, dim3(unsigned(vl.B)), dim3(512), lds, stream, p, R, RSB);
 }
 
 }  // namespace mm

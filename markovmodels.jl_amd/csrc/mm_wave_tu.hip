@@ -8,12 +8,7 @@ namespace mm {
 template <int NSEG, int NJ, bool TWO = false>
 static int launch_wave_one(const WaveLaunch &wl, const RunParams &p, hipStream_t stream) {
     static_assert(MM_WAVE_RS == MM_WAVE_VSZ && MM_WAVE_WAVES == MM_WAVE_NWD, "packer and kernel disagree");
-    const size_t lds = 2 * size_t(MM_WAVE_SLICE);
-    auto kernel = mm_wave_kernel<NSEG, NJ, TWO>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-    hipLaunchKernelGGL(kernel, dim3(unsigned(wl.B)), dim3(128 * (MM_WAVE_NWD + 3)), lds, stream, p);
-    HIP_TRY(hipGetLastError());
-    return MM_OK;
+    return mm_launch(mm_wave_kernel<NSEG, NJ, TWO>, dim3(unsigned(wl.B)), dim3(128 * (MM_WAVE_NWD + 3)), 2 * size_t(MM_WAVE_SLICE), stream, p);
 }
 int mm_launch_wave(const WaveLaunch &wl, const RunParams &p, hipStream_t stream) {
     // (wl.nseg: the most segments ONE wave of an agent holds)
