@@ -114,7 +114,8 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * shapes): entry 0 = mm_pdfposteriors_f32, 1 = mm_viterbi_f32, 2 = what the last mm_pdfposteriors_ex call on the batch launched
  * (the recursion kernel; for ProbSemiring FSMs in float32 with general state maps, the emission GEMM C_hat * V_hat on the matrix
  * cores before it), 3 = mm_alpharecursion_f32 / mm_betarecursion_f32, 4 = mm_arcposteriors_f32 (log batches only),
- * 5 = mm_samplepaths_f32 (log batches only), 6 = mm_expectedcost_f32 (log batches only).
+ * 5 = mm_samplepaths_f32 (log batches only), 6 = mm_expectedcost_f32 (log batches only), 7 = mm_leakyposteriors_f32 (log batches
+ * only).
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -256,6 +257,46 @@ int mm_expectedcost_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, in
                         const float *cost, int64_t c_stride_b, int64_t c_stride_n,
                         float *risk, float *grad, float *gamma, int64_t g_stride_b, int64_t g_stride_n, int64_t g_stride_p,
                         float *ttl, void *stream);
+
+/* Pdf posteriors of the LEAKY HMM: the denominator forward-backward of LF-MMI training as the chain-model trainers run it (the
+ * alpha_dash / beta_dash recursion of Kaldi's chain denominator computation, the `leaky` mode of PyChain), written for state
+ * emissions.  After every frame a fraction eps of the total forward mass is re-injected into the initial states in the proportions
+ * of the initial distribution, so a chunk that does not start or stay on a path from the graph's initial states keeps a finite
+ * log Z and a gradient.  For one FSM in the extended system of src/fsm.jl:19-28 (S real states plus the phony final state, initial
+ * vector alpha_hat, T_hat = [T omega; 0 1]), with pi(k) = alpha_hat(k) as the caller gave it (not renormalised, zero on the phony
+ * state), u the indicator of the real states and eps >= 0 the leak coefficient, T_hat is replaced by
+ *
+ *   T_eps = (I + eps * u * pi') * T_hat        (semiring sums and products; log semiring: (+) = logaddexp, (*) = +)
+ *
+ * and everything else is mm_pdfposteriors_f32 unchanged: expand() semantics, lengths, gamma as probabilities normalised per frame,
+ * ttl the minimum over the frames of the per-frame log normaliser.  In words: a path may, after any frame and from any real state,
+ * jump with weight eps * pi(k) to initial state k; it then takes an ordinary arc of k, the final arc included.  The phony final state
+ * never leaks.  eps = 0 is mm_pdfposteriors_f32 itself; log Z is non-decreasing in eps; d log Z_eps / d V(n,p) = gamma_eps(n,p), so
+ * the LF-MMI gradient stays a difference of posteriors.  No S x S matrix is formed: with rho(j) = (+)_k pi(k) (*) T_hat(k,j) (one
+ * constant per row, the phony final column included) and tot_n = (+)_{i real} alpha_n(i),
+ *   alpha_1 = alpha_hat (*) lhs_1
+ *   alpha_n(j) = lhs_n(j) (*) [ (+)_i alpha_{n-1}(i) T_hat(i,j)  (+)  eps (*) tot_{n-1} (*) rho(j) ]
+ *   z_n(i) = (+)_j T_hat(i,j) lhs_{n+1}(j) beta_{n+1}(j)        c_n = (+)_k pi(k) z_n(k)
+ *   beta_n(i) = z_n(i) (+) eps (*) c_n  for real i,   beta_n(final) = z_n(final)        gamma_n(j) ~ alpha_n(j) beta_n(j)
+ *   V, lens, N, gamma, strides, ttl   exactly as mm_pdfposteriors_f32: frames n >= len_b are exact zeros; an utterance with no
+ *                path even with the leak (len_b = 0, or a frame whose emissions are all -inf) gets gamma = 0 and ttl = -inf.
+ *                gamma or ttl NULL: MM_ERR_INVALID; strides that cannot hold B x N x P distinct elements: MM_ERR_DIM
+ *   leak         the linear coefficient eps (coefficients in use range from 1e-5 to 0.1); 0 is allowed; negative or non-finite:
+ *                MM_ERR_INVALID
+ * MM_LOG batches only: Tropical and ProbSemiring batches return MM_ERR_UNSUPPORTED.  Runs on the item form of every FSM of every log
+ * batch (any size, shared or distinct graphs, each with its own pi and rho), one workgroup per utterance, whatever kernels
+ * mm_pdfposteriors_f32 picks for the batch: a forward kernel with the leak term in the row epilogue, a backward kernel that forms
+ * beta = z (+) eps c between its two barriers and adds the per-pdf sums over fixed lists -- no atomics, so a repeated call returns
+ * the same bits.  Like mm_pdfposteriors_f32 the result does not depend on the level of V (a constant added to every emission of a
+ * frame changes gamma not at all and ttl by that constant): the float32 sums behind tot and c are taken relative to the frame's
+ * largest emission.  A frame in which every live state's own emission lies more than 110 nats below the frame's largest loses its
+ * leak (the unleaked result there, never a NaN).  The exact, mark and gamma policies and the posterior floor do not apply.  Workspace: the alpha~ store of the item
+ * kernel, grown by the call.  Stream contract of mm_arcposteriors_f32: launches on `stream` only, no host synchronisation; it can be
+ * captured in a hipGraph once a first call has put the batch's item forms and leak rows (rho) on the device and sized the workspace
+ * (a capture before that returns MM_ERR_INVALID). */
+int mm_leakyposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                           float leak, float *gamma, int64_t g_stride_b, int64_t g_stride_n, int64_t g_stride_p, float *ttl,
+                           void *stream);
 
 /* alpha-recursion(alpha_hat, T_hat', C_hat*V_hat) (src/inference.jl:62-74) as
  * called from pdfposteriors (:150-152): out is the reference's state_A, a

@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, samplepaths, expectedcost, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, samplepaths, expectedcost, leakyposteriors, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -292,6 +292,28 @@ function expectedcost(b::ROCBatch, V::ROCArray{Float32,3}, cost::ROCArray{Float3
         pointer(risk), pointer(grad), pointer(γ), 1, B * P, B, pointer(ttl),
         AMDGPU.stream().stream))
     risk, grad, γ, ttl
+end
+
+"""
+    leakyposteriors(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing; leak = 1f-5) -> (γ, ttl)
+
+Pdf posteriors of the leaky HMM (mm_leakyposteriors_f32 in the header) of a log-semiring batch: `pdfposteriors` with T̂ replaced by
+(I + leak · u πᵀ) · T̂ -- after any frame, from any real state, a path may jump with weight leak · π(k) to initial state k.  The
+denominator forward-backward of LF-MMI training on chunks.  `V` and `lens` as for `pdfposteriors`; γ is B × P × N, ttl = log Z.
+"""
+function leakyposteriors(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing; leak = 1f-5)
+    P, N, B = size(V)
+    P == b.P || throw(DimensionMismatch("V has $P pdfs, the FSMs $(b.P)"))
+    γ = ROCArray{Float32}(undef, B, P, N)
+    ttl = ROCArray{Float32}(undef, B)
+    lp = lens === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(lens))
+    check(ccall((:mm_leakyposteriors_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Cfloat,
+         Ptr{Float32}, Int64, Int64, Int64, Ptr{Float32}, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, lp, N, Float32(leak),
+        pointer(γ), 1, B * P, B, pointer(ttl),
+        AMDGPU.stream().stream))
+    γ, ttl
 end
 
 """

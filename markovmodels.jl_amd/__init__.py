@@ -2,7 +2,7 @@
 
 Host-side mirror of the reference's hot-path interface (src/MarkovModels.jl:14-45:
 FSM, nstates, rawunion, CompiledFSM, batch, compile, expand, alpha-recursion,
-beta-recursion, pdfposteriors, arcposteriors, samplepaths, expectedcost, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
+beta-recursion, pdfposteriors, leakyposteriors, arcposteriors, samplepaths, expectedcost, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
 The directory name contains a dot, so load it with
 ``__graft_entry__.load_package()`` (importlib) rather than a plain import.
 """
@@ -22,6 +22,7 @@ from .inference import (  # noqa: F401
     compiled_cache_stats,
     expand,
     expectedcost,
+    leakyposteriors,
     maxstateposteriors,
     pdfposteriors,
     samplepaths,

@@ -51,6 +51,7 @@ SYMBOLS = [
     "mm_arcposteriors_f32",
     "mm_samplepaths_f32",
     "mm_expectedcost_f32",
+    "mm_leakyposteriors_f32",
     "mm_pdfposteriors_ex",
     "mm_statemap_create",
     "mm_statemap_destroy",
@@ -163,6 +164,8 @@ def _load():
     lib.mm_samplepaths_f32.argtypes = [vp, fp, i64, i64, vp, i64, i64, i64, vp, i64, i64, fp, i64, fp, vp]
     lib.mm_expectedcost_f32.restype = C.c_int
     lib.mm_expectedcost_f32.argtypes = [vp, fp, i64, i64, vp, i64, fp, i64, i64, fp, fp, fp, i64, i64, i64, fp, vp]
+    lib.mm_leakyposteriors_f32.restype = C.c_int
+    lib.mm_leakyposteriors_f32.argtypes = [vp, fp, i64, i64, vp, i64, C.c_float, fp, i64, i64, i64, fp, vp]
     for name in ("mm_alpharecursion_f32", "mm_betarecursion_f32", "mm_maxstateposteriors_f32"):
         fn = getattr(lib, name)
         fn.restype = C.c_int

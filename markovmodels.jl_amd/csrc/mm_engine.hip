@@ -209,6 +209,9 @@ struct mm_fsm_s {
     // first mm_samplepaths_f32 call that needs it; the list of the phony final state (the omega column)
     DevMem samp_blob;
     int samp_fin_start = 0, samp_fin_deg = 0;
+    // leaky posteriors (MM_LOG): the leak rows -- rho(j) = (+)_k alpha_hat(k) T_hat(k, j), log2 domain, [S1] -- made on the first
+    // mm_leakyposteriors_f32 call that needs them
+    DevMem leak_blob;
 };
 
 // Test/diagnostic switches.  Read from the environment at mm_batch_create (and once per process for the entries that have no
@@ -344,6 +347,8 @@ struct mm_batch_s {
     int64_t arc_slots = 0, arc_max_nnz = 0, arc_max_init = 0;
     // path sampling (mm_samplepaths_f32): the utterances' SampleDev descriptors on the device (made on the first call)
     DevMem d_samp;
+    // leaky posteriors (mm_leakyposteriors_f32): the utterances' LeakDev descriptors on the device (made on the first call)
+    DevMem d_leak;
 };
 
 static bool on_pairs(mm_batch_t h) { return h->fb == Fb::Pairs || h->fb == Fb::Split; }
@@ -426,7 +431,7 @@ static Geometry pick_geometry(mm_batch_t h) {
 }
 
 // ---- one plan per entry that runs on the item form: its launch geometry and where its state vectors live
-enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost };
+enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky };
 struct ItemPlan {
     ItemEntry e;
     int NW, NI;        // waves per workgroup, register-resident items per wave of the instance (8 or 0)
@@ -435,8 +440,8 @@ struct ItemPlan {
     size_t lds_bytes;  // dynamic LDS of the chosen placement (Arcs: of the forward kernel; mm_arc_kernel adds MM_ARC_LDS_EXTRA)
 };
 // The only source of the above.  The vectors are global when the entry's LDS plan (the item kernel's, with the stage rows for
-// all but the export modes, + the arc kernel's extra; Cost: cost_lds_plan) does not fit 160 KB, when MM_BIGV asks for it, or for
-// the arc, sampling and cost kernels when NI = 0: they have no streamed-only instance with the vectors in LDS.
+// all but the export modes, + the arc kernel's extra; Cost: cost_lds_plan; Leaky: leaky_lds_plan) does not fit 160 KB, when MM_BIGV
+// asks for it, or for the arc, sampling, cost and leaky kernels when NI = 0: they have no streamed-only instance with the vectors in LDS.
 // `global` never depends on max_items, nor does NI except Tropical's (8: the whole graph is register-resident): mm_batch_create
 // asks before the item forms are up, and ensure_item_forms raises max_items later -- only NW follows it.
 static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
@@ -444,13 +449,15 @@ static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
     const Geometry g = pick_geometry(h);
     const int P1p = (h->max_P1 + 3) & ~3;
     auto bytes = [&](int S1p) {
+        if (e == ItemEntry::Leaky) return mm_leaky_lds_bytes(S1p, P1p);
         return e == ItemEntry::Cost ? mm_cost_lds_bytes(S1p, P1p) : size_t(lds_plan(S1p, P1p, e != ItemEntry::Export).total) * 4;
     };
-    const bool derived = e == ItemEntry::Arcs || e == ItemEntry::Sample || e == ItemEntry::Cost;
+    const bool derived = e == ItemEntry::Arcs || e == ItemEntry::Sample || e == ItemEntry::Cost || e == ItemEntry::Leaky;
     ItemPlan pl{e, g.NW, g.NI, false, false, 0};
     pl.global = bytes(h->max_S1p) + (e == ItemEntry::Arcs ? MM_ARC_LDS_EXTRA : 0) > lds_max || h->dbg.bigv || (derived && g.NI == 0);
     pl.lds_bytes = bytes(pl.global ? 0 : h->max_S1p);
-    if (e == ItemEntry::Arcs || e == ItemEntry::Cost) pl.NW = std::min(g.NW, 8);  // (8 items' arcs and their sums / the pair arithmetic per wave: compiled for 8 waves per CU)
+    // (8 items' arcs and their sums / the pair arithmetic / the leak term and its sums per wave: compiled for 8 waves per CU)
+    if (e == ItemEntry::Arcs || e == ItemEntry::Cost || e == ItemEntry::Leaky) pl.NW = std::min(g.NW, 8);
     if (e == ItemEntry::Sample) pl.stage = !pl.global && !h->dbg.sample_nostage && size_t(h->max_S1p) * 8 <= lds_max;
     if (e == ItemEntry::Tropical) {
         // register-resident items when the whole graph fits 8 items per wave -- as many waves as there is work for (latency), at most
@@ -2569,6 +2576,12 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
             const std::string inst = "<" + ni + "," + where_of(pl.global) + ">";
             s = "mm_cost_fwd_kernel" + inst + " (forward: alpha~ and r) + mm_cost_bwd_kernel" + inst + " (backward: beta~ and s, gamma and grad per pdf); state vectors " + vectors;
         }
+    } else if (entry == 7) {  // mm_leakyposteriors_f32
+        if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_leakyposteriors_f32 runs on log-semiring batches only");
+        const ItemPlan pl = item_plan(h, ItemEntry::Leaky);
+        const std::string inst = "<" + std::to_string(pl.NI) + "," + where_of(pl.global) + ">";
+        s = "mm_leaky_fwd_kernel" + inst + " (forward: alpha~ with the leak term in the row epilogue) + mm_leaky_bwd_kernel" + inst +
+            " (backward: z, then beta = z (+) eps c, gamma per pdf); state vectors " + (pl.global ? "in global memory" : "in LDS");
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -2974,9 +2987,9 @@ int mm_pdfposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
 }
 
 }  // extern "C"
-// ---- the entries on the item form beside pdfposteriors: arc posteriors, path sampling, expected cost (log batches only)
+// ---- the entries on the item form beside pdfposteriors: arc posteriors, path sampling, expected cost, leaky posteriors (log batches only)
 
-// What the three start with: the semiring refusal, check_run, the entry's own argument checks (`args`), the item forms -- ahead
+// What they start with: the semiring refusal, check_run, the entry's own argument checks (`args`), the item forms -- ahead
 // of the plan: a batch created without them has max_items = 0 until they are up, and the plan would size the workgroups for no
 // items --, then the plan.  Its refusals come with the workspace (item_ws_bind), behind what the entry checks on its derived forms.
 template <class Args>
@@ -2991,7 +3004,7 @@ static int item_entry_begin(mm_batch_t h, const char *who, ItemEntry e, const fl
     return rc;
 }
 
-// Where the three keep what they keep in h->ws for N frames: byte offsets, each aligned to 256 bytes.  The alpha~ store (at 0) and
+// Where they keep what they keep in h->ws for N frames: byte offsets, each aligned to 256 bytes.  The alpha~ store (at 0) and
 // the per-frame offsets as the item kernel keeps them; Arcs: the float64 sums of all backward slots, the state posteriors of
 // frame 1; Cost: the r store and its offsets, and for FSMs beyond the LDS the state vectors of both kernels ([B][8 * max S1p]
 // floats).  total: no less than what mm_pdfposteriors_f32 needs for as many frames.  (mm_batch_reserve does not cover it.)
@@ -3180,6 +3193,71 @@ int mm_expectedcost_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, 
         cp.big_stride = 8ll * h->max_S1p;
     }
     return mm_launch_cost(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, p, cp, static_cast<hipStream_t>(stream));
+}
+
+// ---- pdf posteriors of the leaky HMM (mm_kernel_leaky.hip)
+// rho(j) = (+)_k alpha_hat(k) T_hat(k, j) over the rows of T_hat' (the phony final column included), summed in double
+static std::vector<float> pack_leak_rows(const mm_fsm_s &f) {
+    const Csr &m = f.mat[0];  // row j: the arcs into j
+    const float NINF = -std::numeric_limits<float>::infinity();
+    std::vector<float> rho(size_t(f.S1), NINF);
+    for (int64_t j = 0; j < f.S1; ++j) {
+        double mx = -std::numeric_limits<double>::infinity();
+        for (int64_t k = m.rowptr[size_t(j)]; k < m.rowptr[size_t(j) + 1]; ++k)
+            mx = std::max(mx, double(m.val[size_t(k)]) + double(f.init[size_t(m.col[size_t(k)])]));
+        if (!(mx > -std::numeric_limits<double>::infinity())) continue;
+        double sum = 0.0;
+        for (int64_t k = m.rowptr[size_t(j)]; k < m.rowptr[size_t(j) + 1]; ++k)
+            sum += std::exp2(double(m.val[size_t(k)]) + double(f.init[size_t(m.col[size_t(k)])]) - mx);
+        rho[size_t(j)] = float(mx + std::log2(sum));
+    }
+    return rho;
+}
+// ... and, with them, the batch's global vectors where only this entry's LDS plan (5 floats per state against the item kernel's 4)
+// asks for them: mm_batch_create allocates h->ws_big for the other entries' plans alone, so a batch that never calls this entry
+// holds what it held
+static int ensure_leak_rows(mm_batch_t h, const ItemPlan &pl, void *stream) {
+    if (pl.global && !h->ws_big) {
+        if (capturing(stream))
+            return fail(MM_ERR_INVALID, "the global vectors of this batch are not on the device yet: run mm_leakyposteriors_f32 once outside a stream capture");
+        if (hipMalloc(&h->ws_big, size_t(h->B) * 4 * size_t(h->max_S1p) * sizeof(float)) != hipSuccess) {
+            h->ws_big = nullptr;
+            return fail(MM_ERR_HIP, "mm_leakyposteriors_f32: device allocation failed");
+        }
+    }
+    return ensure_derived_forms<LeakDev>(
+        h, stream, "leak", "mm_leakyposteriors_f32", h->d_leak, &mm_fsm_s::leak_blob, [](mm_fsm_t f, Blob &bl) { (void)bl.add(pack_leak_rows(*f)); },
+        [](mm_fsm_t f) { return LeakDev{static_cast<const float *>(f->leak_blob.get())}; });
+}
+
+int mm_leakyposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, float leak, float *gamma,
+                           int64_t gsb, int64_t gsn, int64_t gsp, float *ttl, void *stream) {
+    ItemPlan pl;
+    int rc = item_entry_begin(h, "mm_leakyposteriors_f32", ItemEntry::Leaky, V, N, stream, [&]() {
+        if (!gamma || !ttl) return fail(MM_ERR_INVALID, "mm_leakyposteriors_f32: gamma / ttl is NULL");
+        if (!(leak >= 0.f) || !std::isfinite(leak)) return fail(MM_ERR_INVALID, "mm_leakyposteriors_f32: the leak coefficient must be finite and >= 0");
+        const int64_t P = h->max_P1 - 1;
+        if (!strides_hold(gsb, h->B, gsn, N, gsp, P))
+            return fail(MM_ERR_DIM, "mm_leakyposteriors_f32: g strides (" + std::to_string(gsb) + ", " + std::to_string(gsn) + ", " + std::to_string(gsp) +
+                                        ") cannot hold " + std::to_string(h->B) + " x " + std::to_string(N) + " x " + std::to_string(P) + " elements");
+        return int(MM_OK);
+    }, &pl);
+    if (rc) return rc;
+    rc = ensure_leak_rows(h, pl, stream);
+    if (rc) return rc;
+    const ItemWs W = item_ws_layout(h, pl, N);
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    rc = item_ws_bind(h, pl, W, p, stream);
+    if (rc) return rc;
+    p.gamma = gamma;
+    p.gsb = gsb;
+    p.gsn = gsn;
+    p.gsp = gsp;
+    p.ttl = ttl;
+    LeakParams lp{};
+    lp.rows = static_cast<const LeakDev *>(h->d_leak.get());
+    lp.leps2 = leak > 0.f ? std::log2(leak) : -std::numeric_limits<float>::infinity();
+    return mm_launch_leaky(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, p, lp, static_cast<hipStream_t>(stream));
 }
 
 // ---- posterior path sampling (mm_kernel_sample.hip)

@@ -235,4 +235,17 @@ struct CostParams {
 int mm_launch_cost(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, const RunParams &p, const CostParams &cp, hipStream_t stream);
 size_t mm_cost_lds_bytes(int S1p, int P1p);
 
+// ---- pdf posteriors of the leaky HMM (mm_leaky_tu.hip: mm_leaky_fwd_kernel, mm_leaky_bwd_kernel on the item form)
+struct LeakDev {  // one utterance's leak rows (mm_engine.hip ensure_leak_rows)
+    const float *rho;  // [S1] log2 (+)_k pi(k) T_hat(k, j): what a leak into the initial states brings to row j
+};
+struct LeakParams {
+    const LeakDev *rows;  // [B]
+    float leps2;          // log2 of the leak coefficient (-inf: no leak)
+};
+// lds_bytes: leaky_lds_plan(...).total * 4 of the geometry (state vectors in LDS, or bigv: in RunParams::ws_big); gamma and ttl
+// go where RunParams says
+int mm_launch_leaky(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, const RunParams &p, const LeakParams &lp, hipStream_t stream);
+size_t mm_leaky_lds_bytes(int S1p, int P1p);
+
 }  // namespace mm

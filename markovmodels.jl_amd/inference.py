@@ -455,6 +455,30 @@ class BatchedFSM:
         out = (risk, grad, ttl) + ((gamma,) if want_gamma else ())
         return tuple(t.cpu().numpy() for t in out) if as_numpy else out
 
+    def leakyposteriors(self, V, lens=None, leak=1e-5, out=None):
+        """Pdf posteriors of the leaky HMM (mm_leakyposteriors_f32): ``(gamma[B, N, P], ttl[B])`` as ``pdfposteriors`` returns
+        them, with the transition matrix replaced by ``(I + leak * u * pi') * T_hat``: after any frame, from any real state, a
+        path may jump with weight ``leak * pi(k)`` to initial state k (``pi`` = the FSM's initial vector as given).  The
+        denominator forward-backward of LF-MMI training on chunks: log Z stays finite for an utterance that loses every path
+        mid-chunk.  ``leak`` is the linear coefficient (1e-5 .. 0.1 in use; 0 = ``pdfposteriors``); ``out`` as for
+        ``pdfposteriors``.  Log batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        if out is not None:
+            # the kernels write through raw pointers and strides: a wrong buffer is memory corruption, not an exception
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != Vt.device:
+                raise TypeError("out must be a float32 tensor on V's device")
+            if out.dim() != 3 or tuple(out.shape) != (B, N, P):
+                raise _lib.DimensionMismatch(-2, f"out must be [B={B}, N={N}, P={P}], got {tuple(out.shape)}")
+        gamma = out if out is not None else torch.empty((B, N, P), dtype=torch.float32, device=Vt.device)
+        ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        check(lib.mm_leakyposteriors_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
+                                         lt.data_ptr() if lt is not None else None, N, float(leak), gamma.data_ptr(),
+                                         gamma.stride(0), gamma.stride(1), gamma.stride(2), ttl.data_ptr(), self._stream(torch)))
+        if as_numpy:
+            return gamma.cpu().numpy(), ttl.cpu().numpy()
+        return gamma, ttl
+
     def maxstateposteriors(self, V, lens=None):
         """Max-marginals of the tropical semiring, (sum S1) x (N+1), computed on the device."""
         return self._export(lib.mm_maxstateposteriors_f32, V, lens)
@@ -537,11 +561,12 @@ class BatchedFSM:
 
     def kernels(self, semiring: str = "log") -> str:
         """The kernels the engine launches for this batch (informational): "log" = pdfposteriors, "tropical" = bestpath, "export" =
-        alpharecursion / betarecursion, "arcs" = arcposteriors, "sample" = samplepaths, "cost" = expectedcost."""
+        alpharecursion / betarecursion, "arcs" = arcposteriors, "sample" = samplepaths, "cost" = expectedcost, "leaky" =
+        leakyposteriors."""
         import ctypes
 
         buf = ctypes.create_string_buffer(1024)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6}[semiring], buf, 1024))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7}[semiring], buf, 1024))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -834,6 +859,30 @@ def pdfposteriors(fsm, Vhats, Chats=None, seqlengths=None):
         return bf.pdfposteriors_generic(Vh, Chats if general_c else None)
     V, lens = un
     g, ttl = bf.pdfposteriors(V, lens)
+    return np.ascontiguousarray(g.transpose(0, 2, 1)), ttl
+
+
+def leakyposteriors(fsm, Vhats, Chats=None, leak=1e-5, seqlengths=None):
+    """Pdf posteriors of the leaky HMM -- see ``BatchedFSM.leakyposteriors`` -- in ``pdfposteriors``' call shape: ``fsm`` the
+    rawunion of the batch with its state maps, or a BatchedFSM / CompiledFSM (log semiring, Float32); V_hats what ``expand``
+    makes.  Returns (gamma[B, P, N] probabilities, ttl[B]): NumPy arrays for host inputs, device tensors for float32 V_hats on
+    the HIP device given with their ``seqlengths``."""
+    if not hasattr(Vhats, "dim"):  # (a generator is read once)
+        Vhats = list(Vhats)
+    bf = _as_batch(fsm, Chats)
+    Vd = _device_vhats(Vhats)
+    if Vd is not None and seqlengths is not None:
+        torch = _torch()
+        B, P1, N1 = Vd.shape
+        if B != bf.B:
+            raise _lib.DimensionMismatch(-2, f"{B} matrices V_hat for a batch of {bf.B} FSMs")
+        lens = torch.as_tensor(seqlengths, dtype=torch.int32, device=Vd.device)
+        g, ttl = bf.leakyposteriors(Vd[:, : P1 - 1, : N1 - 1].transpose(1, 2).contiguous(), lens, leak=leak)
+        return g.transpose(1, 2), ttl
+    # (device V_hats without their lengths: to the host, as pdfposteriors moves them, where the phony row gives the lengths)
+    Vh = [np.asarray(v.cpu() if hasattr(v, "cpu") else v) for v in Vhats]
+    V, lens = _need_expanded(Vh, bf.semiring)
+    g, ttl = bf.leakyposteriors(V, lens, leak=leak)
     return np.ascontiguousarray(g.transpose(0, 2, 1)), ttl
 
 

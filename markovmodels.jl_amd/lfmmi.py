@@ -5,7 +5,9 @@ graphs (one per utterance) and the shared denominator graph -- and
     loss      = - sum_b (log Z_num[b] - log Z_den[b])
     d loss / d V[b, n, p] = gamma_den[b, n, p] - gamma_num[b, n, p]
 
-(the derivative of log Z w.r.t. a log-likelihood is the pdf posterior).  `lfmmi_loss` is a
+(the derivative of log Z w.r.t. a log-likelihood is the pdf posterior; with `leak`, the denominator is the leaky HMM of the
+chain-model trainers -- `BatchedFSM.leakyposteriors` -- whose log Z has the leaky posterior as its derivative, so the gradient
+stays this difference).  `lfmmi_loss` is a
 torch.autograd.Function over the device-resident log-likelihoods; in a data-parallel job the
 per-rank losses are summed with `dist.allreduce_logz` (one scalar over RCCL).
 
@@ -34,9 +36,10 @@ def _side_stream(torch, device):
     return s
 
 
-def posteriors_difference(V, num_batch, den_batch, lens=None, mode: str = "auto", out=None):
+def posteriors_difference(V, num_batch, den_batch, lens=None, mode: str = "auto", out=None, leak=None):
     """(gamma_den - gamma_num)[B, N, P], ttl_num[B], ttl_den[B] for device-resident V: the two engine calls of an LF-MMI step and
-    the gradient they give, without autograd."""
+    the gradient they give, without autograd.  ``leak``: None -- the plain denominator -- or the coefficient of the leaky one
+    (``den_batch.leakyposteriors``); the numerator call is the same either way."""
     import torch
 
     from ._lib import MarkovModelsAMDError
@@ -45,6 +48,11 @@ def posteriors_difference(V, num_batch, den_batch, lens=None, mode: str = "auto"
         raise ValueError(f"mode {mode!r}")
     B, N, P = V.shape
     grad = out if out is not None else torch.empty((B, N, P), dtype=torch.float32, device=V.device)
+    if leak is None:
+        den = den_batch.pdfposteriors
+    else:
+        def den(V, lens, out):
+            return den_batch.leakyposteriors(V, lens, leak=leak, out=out)
     fused = mode in ("auto", "fused")
     if fused:
         try:
@@ -55,7 +63,7 @@ def posteriors_difference(V, num_batch, den_batch, lens=None, mode: str = "auto"
             fused = False
     if fused:
         try:
-            _, t_den = den_batch.pdfposteriors(V, lens, out=grad)
+            _, t_den = den(V, lens, out=grad)
             _, t_num = num_batch.pdfposteriors(V, lens, out=grad)  # grad += -1 * gamma_num
         finally:
             num_batch.set_gamma_mode(False, 1.0)
@@ -66,14 +74,14 @@ def posteriors_difference(V, num_batch, den_batch, lens=None, mode: str = "auto"
         side.wait_stream(cur)  # (V is produced on the caller's stream)
         with torch.cuda.stream(side):
             g_num, t_num = num_batch.pdfposteriors(V, lens)
-        _, t_den = den_batch.pdfposteriors(V, lens, out=grad)
+        _, t_den = den(V, lens, out=grad)
         cur.wait_stream(side)
         g_num.record_stream(cur)
         t_num.record_stream(cur)
         grad.sub_(g_num)
         return grad, t_num, t_den
     g_num, t_num = num_batch.pdfposteriors(V, lens)
-    _, t_den = den_batch.pdfposteriors(V, lens, out=grad)
+    _, t_den = den(V, lens, out=grad)
     grad.sub_(g_num)
     return grad, t_num, t_den
 
@@ -83,8 +91,8 @@ def _function():
 
     class _LFMMI(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, V, num, den, lens, mode):
-            grad, t_num, t_den = posteriors_difference(V.detach(), num, den, lens, mode)
+        def forward(ctx, V, num, den, lens, mode, leak=None):
+            grad, t_num, t_den = posteriors_difference(V.detach(), num, den, lens, mode, leak=leak)
             ctx.save_for_backward(grad)
             ctx.mark_non_differentiable(t_num, t_den)
             loss = -(t_num.double() - t_den.double()).sum()
@@ -93,16 +101,18 @@ def _function():
         @staticmethod
         def backward(ctx, gl, _gn, _gd):
             (grad,) = ctx.saved_tensors
-            return grad * gl, None, None, None, None
+            return grad * gl, None, None, None, None, None
 
     return _LFMMI
 
 
-def lfmmi_loss(V, num_batch, den_batch, lens: Optional["torch.Tensor"] = None, mode: str = "auto"):
+def lfmmi_loss(V, num_batch, den_batch, lens: Optional["torch.Tensor"] = None, mode: str = "auto", leak: Optional[float] = None):
     """V: [B, N, P] float32 log-likelihoods on the HIP device (requires_grad as needed);
     num_batch / den_batch: BatchedFSM of B utterances each (log semiring).
     Returns (loss, ttl_num[B], ttl_den[B]); utterances without an accepting numerator or
-    denominator path have ttl = -inf and must be filtered by the caller.
+    denominator path have ttl = -inf and must be filtered by the caller.  ``leak`` (None: off; 1e-5 .. 0.1 in use): the
+    denominator runs as a leaky HMM (``BatchedFSM.leakyposteriors``), whose log Z is finite for every utterance whose frames
+    can be emitted at all -- chunked training needs it.
 
     The gradient is a difference of posteriors: one below 1e-12 changes nothing.  A training loop says so once --
     `den_batch.set_posterior_floor(1e-12)` -- and the denominator stays on the float32 kernels when the model's outputs get
@@ -113,4 +123,4 @@ def lfmmi_loss(V, num_batch, den_batch, lens: Optional["torch.Tensor"] = None, m
     (`compile_many`: packed on the host's cores, one allocation, one copy; profiles/r04_host_cost.json), the numerator call
     itself 0.44 ms at T = 700: keep the CompiledFSM of an utterance across epochs -- a batch of known FSMs only assembles
     descriptors (0.1 ms).  Measured step: `bench.py --workload lfmmi_step` (profiles/r06_bench_lfmmi_step*.json)."""
-    return _function().apply(V, num_batch, den_batch, lens, mode)
+    return _function().apply(V, num_batch, den_batch, lens, mode, leak)
