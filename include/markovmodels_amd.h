@@ -115,7 +115,8 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * (the recursion kernel; for ProbSemiring FSMs in float32 with general state maps, the emission GEMM C_hat * V_hat on the matrix
  * cores before it), 3 = mm_alpharecursion_f32 / mm_betarecursion_f32, 4 = mm_arcposteriors_f32 (log batches only),
  * 5 = mm_samplepaths_f32 (log batches only), 6 = mm_expectedcost_f32 (log batches only), 7 = mm_leakyposteriors_f32 (log batches
- * only).
+ * only),
+ * 8 = mm_pathentropy_f32 (log batches only): mm_entropy_fwd_kernel<NI,lds|global> + mm_entropy_bwd_kernel<...>.
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -297,6 +298,48 @@ int mm_expectedcost_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, in
 int mm_leakyposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
                            float leak, float *gamma, int64_t g_stride_b, int64_t g_stride_n, int64_t g_stride_p, float *ttl,
                            void *stream);
+
+/* Entropy of the posterior over complete paths and its gradient in the emissions: the objective of semi-supervised sequence
+ * training (negative conditional entropy over the denominator graph, for untranscribed audio), the entropy regulariser of LF-MMI /
+ * CTC-style losses, a per-utterance confidence figure.  For utterance b the extended system is that of src/fsm.jl:19-28 with
+ * lhs = C_hat * expand(V_b), frames 1..N+1 and length len_b -- exactly mm_pdfposteriors_f32's semantics; a path is a complete
+ * state sequence pi = s_1 .. s_{N+1} and P(pi) = w(pi) / Z_b its posterior:
+ *
+ *   H_b          = - sum_pi P(pi) ln P(pi)                                                                   (nats; >= 0)
+ *   Hf_1(j) = 0     Hf_n(j) = sum_i P(i | j) (Hf_{n-1}(i) - ln P(i | j)),  P(i | j) ~ alpha_{n-1}(i) T_hat_ij     (the entropy of the prefix given s_n = j)
+ *   Hb_{N+1}(.) = 0 Hb_n(i) = sum_j P(j | i) (Hb_{n+1}(j) - ln P(j | i)),  P(j | i) ~ T_hat_ij lhs_{n+1}(j) beta_{n+1}(j)  (... of the suffix given s_n = i)
+ *   H_b          = Hf_{N+1}(final)
+ *   grad_b(n,p)  = d H_b / d V_b(n,p) = sum_{j : pdf(j) = p} q_n(j) * (Hf_n(j) + Hb_n(j) - ln q_n(j) - H_b),   q_n(j) the state posterior
+ *
+ * (the entropy semiring: Hernando et al. 2005, Li & Eisner 2009).  0 * ln 0 := 0; a state no path reaches carries Hf = Hb = 0.
+ * It follows that sum_p grad_b(n,p) = 0 for every frame, that a constant added to all emissions of a frame changes neither H nor
+ * grad, that a graph with a single path of positive weight gives H = 0 and grad = 0, and that paths of equal weight give
+ * H = ln(number of paths).  The paths are sequences of stored entries of T_hat: parallel entries between the same two states,
+ * which the reference's sparse() combines and its FSMs therefore never hold, would count as distinct transitions.
+ *   V, lens, N   as mm_pdfposteriors_f32
+ *   entropy      device float[B], out: H_b.  NULL: MM_ERR_INVALID
+ *   grad         device, out (NULL: not written): element (b, n, p) at grad[b*g_stride_b + n*g_stride_n + p*g_stride_p], the three
+ *                strides as mm_expectedcost_f32's; frames n >= len_b are exact zeros.  Strides that cannot hold B x N x P distinct
+ *                elements: MM_ERR_DIM (not looked at when grad and gamma are both NULL)
+ *   gamma        device, out with grad's strides (NULL: not written): the pdf posterior, as mm_pdfposteriors_f32 returns it
+ *   ttl          device float[B], out (NULL: not written): log Z_b, the value mm_pdfposteriors_f32 returns
+ * grad == NULL and gamma == NULL is allowed and runs the forward kernel alone: entropy and ttl, bit for bit those of the full
+ * call, with no frame kept in the workspace (confidence scoring).
+ * An utterance without an accepting path (len_b = 0 included) gets entropy 0, grad 0, gamma 0, ttl = -inf; len_b = 1 gives the
+ * entropy of the choice of the single state.
+ * MM_LOG batches only: Tropical and ProbSemiring batches return MM_ERR_UNSUPPORTED.  Runs on the item form of every FSM (any size),
+ * one workgroup per utterance: a forward kernel that carries Hf beside alpha~ (one 8-byte gather per arc; the conditional
+ * probabilities are the terms of the row's log-sum-exp), a backward kernel that carries Hb beside beta~ and adds the per-pdf sums
+ * over fixed lists -- no atomics, so a repeated call returns the same bits.  Hf and Hb are carried centred by per-frame float64
+ * offsets, so the float32 values stay near zero whatever the length, and the frame's posterior mean of the bracket (zero by the
+ * chain rule of entropy) is taken out of grad.  The exact, mark and gamma policies and the posterior floor do not apply.
+ * Workspace: the alpha~ store of the item kernel and an Hf store of the same size, float32 (sum_b S1p_b) x (N + 1) each, grown by
+ * the call; for a value-only call the Hf store is not allocated.  Stream contract of mm_arcposteriors_f32: launches on `stream` only, no host
+ * synchronisation; it can be captured in a hipGraph once a first call has put the batch's item forms on the device and sized the
+ * workspace (a capture before that returns MM_ERR_INVALID). */
+int mm_pathentropy_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                       float *entropy, float *grad, float *gamma, int64_t g_stride_b, int64_t g_stride_n, int64_t g_stride_p,
+                       float *ttl, void *stream);
 
 /* alpha-recursion(alpha_hat, T_hat', C_hat*V_hat) (src/inference.jl:62-74) as
  * called from pdfposteriors (:150-152): out is the reference's state_A, a

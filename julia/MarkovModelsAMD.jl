@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, samplepaths, expectedcost, leakyposteriors, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -292,6 +292,31 @@ function expectedcost(b::ROCBatch, V::ROCArray{Float32,3}, cost::ROCArray{Float3
         pointer(risk), pointer(grad), pointer(γ), 1, B * P, B, pointer(ttl),
         AMDGPU.stream().stream))
     risk, grad, γ, ttl
+end
+
+"""
+    pathentropy(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing; grad = true) -> (H, grad, γ, ttl)
+
+Entropy of the posterior over complete paths, H_b = -Σ_π P(π | V_b) log P(π | V_b) in nats, and its gradient in the emissions
+(mm_pathentropy_f32 in the header) of a log-semiring batch.  `V` and `lens` as for `pdfposteriors`.  Returns `H` (B), `grad` = ∂H / ∂V
+and `γ` (the pdf posteriors), both B × P × N like `pdfposteriors`' γ, and ttl = log Z.  With `grad = false` only the forward kernel
+runs (value and ttl, for confidence scoring) and `grad`, `γ` come back as `nothing`.
+"""
+function pathentropy(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing; grad = true)
+    P, N, B = size(V)
+    P == b.P || throw(DimensionMismatch("V has $P pdfs, the FSMs $(b.P)"))
+    H = ROCArray{Float32}(undef, B)
+    g = grad ? ROCArray{Float32}(undef, B, P, N) : nothing
+    γ = grad ? ROCArray{Float32}(undef, B, P, N) : nothing
+    ttl = ROCArray{Float32}(undef, B)
+    lp = lens === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(lens))
+    check(ccall((:mm_pathentropy_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64,
+         Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int64, Int64, Int64, Ptr{Float32}, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, lp, N,
+        pointer(H), grad ? pointer(g) : Ptr{Float32}(C_NULL), grad ? pointer(γ) : Ptr{Float32}(C_NULL), 1, B * P, B, pointer(ttl),
+        AMDGPU.stream().stream))
+    H, g, γ, ttl
 end
 
 """

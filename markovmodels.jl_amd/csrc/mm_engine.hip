@@ -431,7 +431,7 @@ static Geometry pick_geometry(mm_batch_t h) {
 }
 
 // ---- one plan per entry that runs on the item form: its launch geometry and where its state vectors live
-enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky };
+enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy };
 struct ItemPlan {
     ItemEntry e;
     int NW, NI;        // waves per workgroup, register-resident items per wave of the instance (8 or 0)
@@ -440,8 +440,8 @@ struct ItemPlan {
     size_t lds_bytes;  // dynamic LDS of the chosen placement (Arcs: of the forward kernel; mm_arc_kernel adds MM_ARC_LDS_EXTRA)
 };
 // The only source of the above.  The vectors are global when the entry's LDS plan (the item kernel's, with the stage rows for
-// all but the export modes, + the arc kernel's extra; Cost: cost_lds_plan; Leaky: leaky_lds_plan) does not fit 160 KB, when MM_BIGV
-// asks for it, or for the arc, sampling, cost and leaky kernels when NI = 0: they have no streamed-only instance with the vectors in LDS.
+// all but the export modes, + the arc kernel's extra; Cost: cost_lds_plan; Leaky: leaky_lds_plan; Entropy: entropy_lds_plan) does not fit
+// 160 KB, when MM_BIGV asks for it, or for the arc, sampling, cost, leaky and entropy kernels when NI = 0: they have no streamed-only instance with the vectors in LDS.
 // `global` never depends on max_items, nor does NI except Tropical's (8: the whole graph is register-resident): mm_batch_create
 // asks before the item forms are up, and ensure_item_forms raises max_items later -- only NW follows it.
 static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
@@ -450,14 +450,15 @@ static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
     const int P1p = (h->max_P1 + 3) & ~3;
     auto bytes = [&](int S1p) {
         if (e == ItemEntry::Leaky) return mm_leaky_lds_bytes(S1p, P1p);
+        if (e == ItemEntry::Entropy) return mm_entropy_lds_bytes(S1p, P1p);
         return e == ItemEntry::Cost ? mm_cost_lds_bytes(S1p, P1p) : size_t(lds_plan(S1p, P1p, e != ItemEntry::Export).total) * 4;
     };
-    const bool derived = e == ItemEntry::Arcs || e == ItemEntry::Sample || e == ItemEntry::Cost || e == ItemEntry::Leaky;
+    const bool derived = e == ItemEntry::Arcs || e == ItemEntry::Sample || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy;
     ItemPlan pl{e, g.NW, g.NI, false, false, 0};
     pl.global = bytes(h->max_S1p) + (e == ItemEntry::Arcs ? MM_ARC_LDS_EXTRA : 0) > lds_max || h->dbg.bigv || (derived && g.NI == 0);
     pl.lds_bytes = bytes(pl.global ? 0 : h->max_S1p);
     // (8 items' arcs and their sums / the pair arithmetic / the leak term and its sums per wave: compiled for 8 waves per CU)
-    if (e == ItemEntry::Arcs || e == ItemEntry::Cost || e == ItemEntry::Leaky) pl.NW = std::min(g.NW, 8);
+    if (e == ItemEntry::Arcs || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy) pl.NW = std::min(g.NW, 8);
     if (e == ItemEntry::Sample) pl.stage = !pl.global && !h->dbg.sample_nostage && size_t(h->max_S1p) * 8 <= lds_max;
     if (e == ItemEntry::Tropical) {
         // register-resident items when the whole graph fits 8 items per wave -- as many waves as there is work for (latency), at most
@@ -468,15 +469,16 @@ static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
     }
     return pl;
 }
-// ... for an entry about to launch: refuses what the plan cannot run.  (Cost keeps its global vectors in the workspace at
-// 8 floats per state, the others in h->ws_big at 4: bind_big, ItemWs)
+// ... for an entry about to launch: refuses what the plan cannot run.  (Cost and Entropy keep their global vectors in the workspace
+// at 8 floats per state, the others in h->ws_big at 4: bind_big, ItemWs)
+static bool ws_holds_big(ItemEntry e) { return e == ItemEntry::Cost || e == ItemEntry::Entropy; }
 static int item_plan_check(mm_batch_t h, const ItemPlan &pl) {
-    if (pl.global && pl.e != ItemEntry::Cost && !h->ws_big)
+    if (pl.global && !ws_holds_big(pl.e) && !h->ws_big)
         return fail(MM_ERR_UNSUPPORTED, "FSM too large for the LDS and no global-memory vectors were allocated");
     return pl.lds_bytes > MM_LDS_MAX ? fail(MM_ERR_UNSUPPORTED, "too many pdfs for the LDS: " + std::to_string(h->max_P1)) : int(MM_OK);
 }
 static void bind_big(mm_batch_t h, const ItemPlan &pl, RunParams &p) {
-    if (!pl.global || pl.e == ItemEntry::Cost) return;
+    if (!pl.global || ws_holds_big(pl.e)) return;
     p.ws_big = h->ws_big;
     p.big_stride = 4ll * h->max_S1p;
 }
@@ -2275,7 +2277,7 @@ static int batch_create_impl(const mm_fsm_t *fsms, int64_t B, mm_batch_t *out) {
         return fail(MM_ERR_HIP, "mm_batch_create: device allocation failed");
     }
     h->utts_host = std::move(utts);
-    // FSMs whose state vectors do not fit the LDS of some entry that keeps them in h->ws_big (every one but Cost): the arc kernel's
+    // FSMs whose state vectors do not fit the LDS of some entry that keeps them in h->ws_big (every one but Cost and Entropy): the arc kernel's
     // plan is the largest, and the streamed-only instances of the arc and sampling entries have the vectors there whatever the
     // size (MM_NITEMS=0 on a small graph)
     bool big = false;
@@ -2582,6 +2584,12 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
         const std::string inst = "<" + std::to_string(pl.NI) + "," + where_of(pl.global) + ">";
         s = "mm_leaky_fwd_kernel" + inst + " (forward: alpha~ with the leak term in the row epilogue) + mm_leaky_bwd_kernel" + inst +
             " (backward: z, then beta = z (+) eps c, gamma per pdf); state vectors " + (pl.global ? "in global memory" : "in LDS");
+    } else if (entry == 8) {  // mm_pathentropy_f32
+        if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_pathentropy_f32 runs on log-semiring batches only");
+        const ItemPlan pl = item_plan(h, ItemEntry::Entropy);
+        const std::string inst = "<" + std::to_string(pl.NI) + "," + where_of(pl.global) + ">";
+        s = "mm_entropy_fwd_kernel" + inst + " (forward: alpha~ and Hf, entropy and ttl; alone and without a store when neither grad nor gamma is asked for) + mm_entropy_bwd_kernel" +
+            inst + " (backward: beta~ and Hb, gamma and grad per pdf); state vectors " + (pl.global ? "in global memory" : "in LDS");
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -2987,7 +2995,7 @@ int mm_pdfposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
 }
 
 }  // extern "C"
-// ---- the entries on the item form beside pdfposteriors: arc posteriors, path sampling, expected cost, leaky posteriors (log batches only)
+// ---- the entries on the item form beside pdfposteriors: arc posteriors, path sampling, expected cost, leaky posteriors, path entropy (log batches only)
 
 // What they start with: the semiring refusal, check_run, the entry's own argument checks (`args`), the item forms -- ahead
 // of the plan: a batch created without them has max_items = 0 until they are up, and the plan would size the workgroups for no
@@ -3007,9 +3015,10 @@ static int item_entry_begin(mm_batch_t h, const char *who, ItemEntry e, const fl
 // Where they keep what they keep in h->ws for N frames: byte offsets, each aligned to 256 bytes.  The alpha~ store (at 0) and
 // the per-frame offsets as the item kernel keeps them; Arcs: the float64 sums of all backward slots, the state posteriors of
 // frame 1; Cost: the r store and its offsets, and for FSMs beyond the LDS the state vectors of both kernels ([B][8 * max S1p]
-// floats).  total: no less than what mm_pdfposteriors_f32 needs for as many frames.  (mm_batch_reserve does not cover it.)
+// floats); Entropy: as Cost, the Hf store in the place of the r store -- and no such store for a value-only call (`store` false).
+// total: no less than what mm_pdfposteriors_f32 needs for as many frames.  (mm_batch_reserve does not cover it.)
 struct ItemWs { size_t c = 0, acc = 0, post1 = 0, r = 0, o = 0, big = 0, total = 0; };
-static ItemWs item_ws_layout(mm_batch_t h, const ItemPlan &pl, int64_t N) {
+static ItemWs item_ws_layout(mm_batch_t h, const ItemPlan &pl, int64_t N, bool store = true) {
     ItemWs W;
     const size_t rows = align_up(size_t(h->total_s1p) * size_t(N + 1) * 4, 256);
     W.c = rows;
@@ -3018,9 +3027,9 @@ static ItemWs item_ws_layout(mm_batch_t h, const ItemPlan &pl, int64_t N) {
         W.acc = W.total;
         W.post1 = W.acc + align_up(size_t(h->arc_slots) * 8, 256);
         W.total = W.post1 + align_up(size_t(h->total_s1p) * 4, 256);
-    } else if (pl.e == ItemEntry::Cost) {
+    } else if (ws_holds_big(pl.e)) {
         W.r = W.total;
-        W.o = W.r + rows;
+        W.o = W.r + (store ? rows : 0);
         W.big = W.o + ws_c_bytes(h, N);
         W.total = W.big + (pl.global ? align_up(size_t(h->B) * 8 * size_t(h->max_S1p) * 4, 256) : 0);
     }
@@ -3193,6 +3202,42 @@ int mm_expectedcost_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, 
         cp.big_stride = 8ll * h->max_S1p;
     }
     return mm_launch_cost(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, p, cp, static_cast<hipStream_t>(stream));
+}
+
+// ---- posterior path entropy and its gradient (mm_kernel_entropy.hip)
+int mm_pathentropy_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, float *entropy, float *grad,
+                       float *gamma, int64_t gsb, int64_t gsn, int64_t gsp, float *ttl, void *stream) {
+    ItemPlan pl;
+    const bool backward = grad || gamma;  // neither: the forward kernel alone, no frame kept
+    int rc = item_entry_begin(h, "mm_pathentropy_f32", ItemEntry::Entropy, V, N, stream, [&]() {
+        if (!entropy) return fail(MM_ERR_INVALID, "mm_pathentropy_f32: entropy is NULL");
+        const int64_t P = h->max_P1 - 1;
+        if (backward && !strides_hold(gsb, h->B, gsn, N, gsp, P))
+            return fail(MM_ERR_DIM, "mm_pathentropy_f32: g strides (" + std::to_string(gsb) + ", " + std::to_string(gsn) + ", " + std::to_string(gsp) +
+                                        ") cannot hold " + std::to_string(h->B) + " x " + std::to_string(N) + " x " + std::to_string(P) + " elements");
+        return int(MM_OK);
+    }, &pl);
+    if (rc) return rc;
+    const ItemWs W = item_ws_layout(h, pl, N, backward);
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    rc = item_ws_bind(h, pl, W, p, stream);
+    if (rc) return rc;
+    char *ws = static_cast<char *>(h->ws);
+    EntropyParams ep{};
+    ep.entropy = entropy;
+    ep.grad = grad;
+    ep.gamma = gamma;
+    ep.gsb = gsb;
+    ep.gsn = gsn;
+    ep.gsp = gsp;
+    ep.ttl = ttl;
+    ep.ws_h = backward ? reinterpret_cast<float *>(ws + W.r) : nullptr;
+    ep.ws_o = reinterpret_cast<double *>(ws + W.o);
+    if (pl.global) {
+        ep.ws_big = reinterpret_cast<float *>(ws + W.big);
+        ep.big_stride = 8ll * h->max_S1p;
+    }
+    return mm_launch_entropy(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, backward, p, ep, static_cast<hipStream_t>(stream));
 }
 
 // ---- pdf posteriors of the leaky HMM (mm_kernel_leaky.hip)

@@ -235,6 +235,25 @@ struct CostParams {
 int mm_launch_cost(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, const RunParams &p, const CostParams &cp, hipStream_t stream);
 size_t mm_cost_lds_bytes(int S1p, int P1p);
 
+// ---- posterior path entropy and its gradient (mm_entropy_tu.hip: mm_entropy_fwd_kernel, mm_entropy_bwd_kernel on the item form)
+struct EntropyParams {
+    float *entropy;  // [B]
+    float *grad;     // strides as gamma's; NULL: not asked for
+    float *gamma;    // NULL: not asked for
+    long long gsb, gsn, gsp;
+    float *ttl;      // NULL: not asked for
+    float *ws_h;     // [sum_b S1p_b][N+1] the centred Hf rows, laid out like RunParams::ws_alpha; NULL: a value-only call keeps
+                     // no frame (neither the alpha~ rows nor C_n, O_n are written)
+    double *ws_o;    // [B][N+2] per-frame offsets O_n of the Hf rows; [0]: H
+    float *ws_big;   // global-memory vectors: [B][big_stride] floats (8 * max S1p)
+    long long big_stride;
+};
+// lds_bytes: entropy_lds_plan(...).total * 4 of the geometry (state vectors in LDS, or bigv: in EntropyParams::ws_big);
+// backward false: the forward kernel alone (value and ttl)
+int mm_launch_entropy(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, bool backward, const RunParams &p, const EntropyParams &ep,
+                      hipStream_t stream);
+size_t mm_entropy_lds_bytes(int S1p, int P1p);
+
 // ---- pdf posteriors of the leaky HMM (mm_leaky_tu.hip: mm_leaky_fwd_kernel, mm_leaky_bwd_kernel on the item form)
 struct LeakDev {  // one utterance's leak rows (mm_engine.hip ensure_leak_rows)
     const float *rho;  // [S1] log2 (+)_k pi(k) T_hat(k, j): what a leak into the initial states brings to row j

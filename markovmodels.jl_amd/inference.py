@@ -455,6 +455,26 @@ class BatchedFSM:
         out = (risk, grad, ttl) + ((gamma,) if want_gamma else ())
         return tuple(t.cpu().numpy() for t in out) if as_numpy else out
 
+    def pathentropy(self, V, lens=None, want_grad=True, want_gamma=False):
+        """Entropy of the posterior over complete paths and its gradient (mm_pathentropy_f32): ``(entropy[B], grad[B, N, P],
+        ttl[B])``, plus ``gamma[B, N, P]`` when ``want_gamma``.  ``entropy[b]`` = -sum over the paths of P(path | V_b) ln P(path | V_b)
+        in nats, ``grad`` its derivative with respect to ``V`` (``None`` without ``want_grad``), ``gamma`` the pdf posteriors,
+        ``ttl`` = log Z as ``pdfposteriors`` returns it.  With neither ``want_grad`` nor ``want_gamma`` only the forward kernel
+        runs and no frame is kept: the same ``entropy`` and ``ttl``, bit for bit (confidence scoring).  An utterance without a
+        path has entropy 0, gradient 0, ttl = -inf.  Log batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        ent = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        grad = torch.empty((B, N, P), dtype=torch.float32, device=Vt.device) if want_grad else None
+        gamma = torch.empty((B, N, P), dtype=torch.float32, device=Vt.device) if want_gamma else None
+        check(lib.mm_pathentropy_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
+                                     lt.data_ptr() if lt is not None else None, N, ent.data_ptr(),
+                                     grad.data_ptr() if grad is not None else None, gamma.data_ptr() if gamma is not None else None,
+                                     N * P, P, 1, ttl.data_ptr(), self._stream(torch)))
+        out = (ent, grad, ttl) + ((gamma,) if want_gamma else ())
+        return tuple(t.cpu().numpy() if t is not None else None for t in out) if as_numpy else out
+
     def leakyposteriors(self, V, lens=None, leak=1e-5, out=None):
         """Pdf posteriors of the leaky HMM (mm_leakyposteriors_f32): ``(gamma[B, N, P], ttl[B])`` as ``pdfposteriors`` returns
         them, with the transition matrix replaced by ``(I + leak * u * pi') * T_hat``: after any frame, from any real state, a
@@ -562,11 +582,11 @@ class BatchedFSM:
     def kernels(self, semiring: str = "log") -> str:
         """The kernels the engine launches for this batch (informational): "log" = pdfposteriors, "tropical" = bestpath, "export" =
         alpharecursion / betarecursion, "arcs" = arcposteriors, "sample" = samplepaths, "cost" = expectedcost, "leaky" =
-        leakyposteriors."""
+        leakyposteriors, "entropy" = pathentropy."""
         import ctypes
 
         buf = ctypes.create_string_buffer(1024)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7}[semiring], buf, 1024))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8}[semiring], buf, 1024))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -916,6 +936,17 @@ def expectedcost(fsm, Vhats, costs, Chats=None):
         cost[b, : lens[b]] = c[:, : lens[b]].T
     risk, grad, ttl = bf.expectedcost(V, cost, lens)
     return risk, np.ascontiguousarray(grad.transpose(0, 2, 1)), ttl
+
+
+def pathentropy(fsm, Vhats, Chats=None):
+    """Entropy of every utterance's posterior over complete paths, and its gradient in the emissions: ``(entropy[B],
+    grad[B, P, N], ttl[B])`` -- see ``BatchedFSM.pathentropy``.  ``fsm`` and the arguments as for ``pdfposteriors``: the rawunion of
+    the batch with its state maps, or a BatchedFSM / CompiledFSM (log semiring); V_hats must be what ``expand`` makes.  ``grad``
+    comes back in ``pdfposteriors``' layout.  NumPy arrays out."""
+    bf = _as_batch(fsm, Chats)
+    V, lens = _need_expanded(Vhats, bf.semiring)
+    ent, grad, ttl = bf.pathentropy(V, lens)
+    return ent, np.ascontiguousarray(grad.transpose(0, 2, 1)), ttl
 
 
 def samplepaths(fsm, Vhats, Chats=None, nsamples=1, seed=0):
