@@ -97,18 +97,133 @@ struct Plan {
     std::vector<std::vector<int>> wave_segs;  // per wave: indices into segs, in execution order
     int KA = 0, maxcost = 0, mincost = 0;
     bool ok = false;
+    int exchanges = 0;    // segments that found room only after an exchange (make_room)
+    bool pruned = false;  // not dealt: cannot beat the bound it was given (ok stays false)
     std::vector<int> n4;  // mixed layout: segments of a wave that sit in 4-slot positions (the first ones)
 };
 
+// Pair forms: a finish reads the emission factor of its row, 8 bytes at 8 * pdf -- bank pair pdf mod 32, served per half-wave; two
+// rows of one half with different pdfs in one bank pair cost an LDS cycle more.  The rows of a segment are interchangeable
+// (same lane group, same slots): the pdfs of a bank pair are dealt to the two halves in turn (rows of ONE pdf stay together:
+// a broadcast), as far as the halves' capacities go.
+// Nothing of the schedule depends on it (costs and slots are those of the segment): done once, on the plan that won.
+void deal_pdf_halves(Plan &p, const std::vector<int32_t> &row2pdf) {
+    long long before = 0, after = 0;
+    auto half_cost = [&](const Segment &sg) {
+        long long c = 0;
+        const int per_half = 32 / std::min(sg.g, 32);
+        for (int h = 0; h < 2 && sg.g <= 32; ++h) {
+            int distinct[32] = {0};
+            std::vector<int32_t> seen;
+            for (int j = h * per_half; j < std::min<int>((h + 1) * per_half, int(sg.rows.size())); ++j) {
+                const int32_t pd = row2pdf[size_t(sg.rows[size_t(j)])];
+                if (std::find(seen.begin(), seen.end(), pd) == seen.end()) {
+                    seen.push_back(pd);
+                    ++distinct[pd & 31];
+                }
+            }
+            int m = 1;
+            for (int d : distinct) m = std::max(m, d);
+            c += m - 1;
+        }
+        return c;
+    };
+    for (auto &sg : p.segs) {
+        if (sg.g > 16 || sg.rows.size() < 3) continue;
+        before += half_cost(sg);
+        const int per_half = 32 / sg.g, n = int(sg.rows.size());
+        const int cap0 = std::min(per_half, n), cap1 = n - cap0;
+        if (cap1 <= 0) continue;
+        // groups of rows by pdf, the pdfs ordered by bank pair
+        std::vector<int32_t> rows = sg.rows;
+        std::stable_sort(rows.begin(), rows.end(), [&](int32_t a, int32_t b) {
+            const int32_t pa = row2pdf[size_t(a)], pb = row2pdf[size_t(b)];
+            return (pa & 31) != (pb & 31) ? (pa & 31) < (pb & 31) : pa < pb;
+        });
+        std::vector<int32_t> half[2];
+        int nb[2][32] = {{0}, {0}};
+        for (size_t i0 = 0; i0 < rows.size();) {
+            size_t i1 = i0;
+            const int32_t pd = row2pdf[size_t(rows[i0])];
+            while (i1 < rows.size() && row2pdf[size_t(rows[i1])] == pd) ++i1;
+            const int bk = pd & 31, free0 = cap0 - int(half[0].size()), free1 = cap1 - int(half[1].size());
+            int h = nb[0][bk] < nb[1][bk] ? 0 : (nb[1][bk] < nb[0][bk] ? 1 : (free0 >= free1 ? 0 : 1));
+            if ((h ? free1 : free0) <= 0) h = 1 - h;
+            for (size_t i = i0; i < i1; ++i) {
+                if (int(half[h].size()) >= (h ? cap1 : cap0)) h = 1 - h;  // (the group is cut: both halves read the pdf)
+                if (half[h].empty() || row2pdf[size_t(half[h].back())] != pd) ++nb[h][bk];
+                half[h].push_back(rows[i]);
+            }
+            i0 = i1;
+        }
+        std::vector<int32_t> out = half[0];
+        out.insert(out.end(), half[1].begin(), half[1].end());
+        Segment trial = sg;
+        trial.rows = out;
+        if (half_cost(trial) <= half_cost(sg)) sg.rows = std::move(out);
+        after += half_cost(sg);
+    }
+    if (getenv("MM_VERBOSE_PLAN")) fprintf(stderr, "[mm] pdf_halves: extra LDS cycles of the emission reads %lld -> %lld (%zu segments)\n", before, after, p.segs.size());
+}
+
+// lanes of a row of d arcs when a lane takes at most acap of them: the smallest power of two that does (a row of exactly
+// acap arcs stays on one lane)
+int lanes_for(int d, int acap, const RowPackOpts &opt) {
+    int g = 1;
+    while ((std::max(d, 1) + g - 1) / g > acap / opt.a_round * opt.a_round && g < 64) g *= 2;
+    return g;
+}
+
+// One segment that found no wave with A free arc slots, although the waves together have them (longest-processing-time-first
+// levels the cost and leaves every wave a few slots): ONE exchange makes room -- segment j of wave w trades places with a
+// shorter segment k of wave w2 (or just moves there), so that w's free slots grow by A_j - A_k; of all exchanges after which
+// the new segment fits w, the one with the lowest levelled cost of the two waves.  At most segments^2 trials per call.
+// Returns the wave that now has room, or -1.
+template <class Cost, class Level>
+int make_room(Plan &p, int A, int c, int ka_max, std::vector<int> &load, std::vector<int> &arcs, const Cost &cost, const Level &level) {
+    const int nwc = int(p.wave_segs.size());
+    int bw = -1, bw2 = -1, bj = -1, bk = -1;
+    float bl = 0.f;
+    for (int w = 0; w < nwc; ++w) {
+        if (int(p.wave_segs[w].size()) >= MM_ROW_MAX_SLOTS) continue;
+        for (int j = 0; j < int(p.wave_segs[w].size()); ++j) {
+            const Segment &sj = p.segs[p.wave_segs[w][j]];
+            for (int w2 = 0; w2 < nwc; ++w2) {
+                if (w2 == w) continue;
+                for (int k = -1; k < int(p.wave_segs[w2].size()); ++k) {  // (-1: j moves, nothing comes back)
+                    if (k < 0 && int(p.wave_segs[w2].size()) >= MM_ROW_MAX_SLOTS) continue;
+                    const int Ak = k < 0 ? 0 : p.segs[p.wave_segs[w2][k]].A, ck = k < 0 ? 0 : cost(p.segs[p.wave_segs[w2][k]]);
+                    if (Ak >= sj.A || arcs[w] - sj.A + Ak + A > ka_max || arcs[w2] - Ak + sj.A > ka_max) continue;
+                    const float l = std::max(level(w, c + ck - cost(sj)), level(w2, cost(sj) - ck));
+                    if (bw < 0 || l < bl) bw = w, bw2 = w2, bj = j, bk = k, bl = l;
+                }
+            }
+        }
+    }
+    if (bw < 0) return -1;
+    const int sj = p.wave_segs[bw][bj], sk = bk < 0 ? -1 : p.wave_segs[bw2][bk];
+    if (sk < 0) {
+        p.wave_segs[bw].erase(p.wave_segs[bw].begin() + bj);
+        p.wave_segs[bw2].push_back(sj);
+    } else {
+        std::swap(p.wave_segs[bw][bj], p.wave_segs[bw2][bk]);
+        p.segs[sk].wave = bw;
+    }
+    p.segs[sj].wave = bw2;
+    const int dA = p.segs[sj].A - (sk < 0 ? 0 : p.segs[sk].A), dc = cost(p.segs[sj]) - (sk < 0 ? 0 : cost(p.segs[sk]));
+    arcs[bw] -= dA, arcs[bw2] += dA, load[bw] -= dc, load[bw2] += dc;
+    return bw;
+}
+
+// bound: a plan whose levelled cost cannot come below it is abandoned before the dealing (ok = false)
 Plan plan_for(const std::vector<int32_t> &rows, const std::vector<int64_t> &rowptr, int acap, const RowPackOpts &opt,
-              const std::vector<int32_t> *row2pdf = nullptr) {
+              const std::vector<int32_t> *row2pdf = nullptr, int bound = std::numeric_limits<int>::max()) {
     Plan p;
     std::vector<Unit> units;
     units.reserve(rows.size());
     for (int32_t r : rows) {
         const int d = int(rowptr[r + 1] - rowptr[r]);
-        int g = 1;
-        while ((std::max(d, 1) + g - 1) / g > acap / opt.a_round * opt.a_round && g < 64) g *= 2;
+        const int g = lanes_for(d, acap, opt);
         int A = (std::max(d, 1) + g - 1) / g;
         A = (A + opt.a_round - 1) / opt.a_round * opt.a_round;
         units.push_back(Unit{int32_t(r), g, A, d});
@@ -153,68 +268,6 @@ Plan plan_for(const std::vector<int32_t> &rows, const std::vector<int64_t> &rowp
             p.segs.push_back(std::move(s));
         }
     }
-    // Pair forms: a finish reads the emission factor of its row, 8 bytes at 8 * pdf -- bank pair pdf mod 32, served per half-wave; two
-    // rows of one half with different pdfs in one bank pair cost an LDS cycle more.  The rows of a segment are interchangeable
-    // (same lane group, same slots): the pdfs of a bank pair are dealt to the two halves in turn (rows of ONE pdf stay together:
-    // a broadcast), as far as the halves' capacities go.
-    if (opt.pdf_halves && row2pdf) {
-        long long before = 0, after = 0;
-        auto half_cost = [&](const Segment &sg) {
-            long long c = 0;
-            const int per_half = 32 / std::min(sg.g, 32);
-            for (int h = 0; h < 2 && sg.g <= 32; ++h) {
-                int distinct[32] = {0};
-                std::vector<int32_t> seen;
-                for (int j = h * per_half; j < std::min<int>((h + 1) * per_half, int(sg.rows.size())); ++j) {
-                    const int32_t pd = (*row2pdf)[size_t(sg.rows[size_t(j)])];
-                    if (std::find(seen.begin(), seen.end(), pd) == seen.end()) {
-                        seen.push_back(pd);
-                        ++distinct[pd & 31];
-                    }
-                }
-                int m = 1;
-                for (int d : distinct) m = std::max(m, d);
-                c += m - 1;
-            }
-            return c;
-        };
-        for (auto &sg : p.segs) {
-            if (sg.g > 16 || sg.rows.size() < 3) continue;
-            before += half_cost(sg);
-            const int per_half = 32 / sg.g, n = int(sg.rows.size());
-            const int cap0 = std::min(per_half, n), cap1 = n - cap0;
-            if (cap1 <= 0) continue;
-            // groups of rows by pdf, the pdfs ordered by bank pair
-            std::vector<int32_t> rows = sg.rows;
-            std::stable_sort(rows.begin(), rows.end(), [&](int32_t a, int32_t b) {
-                const int32_t pa = (*row2pdf)[size_t(a)], pb = (*row2pdf)[size_t(b)];
-                return (pa & 31) != (pb & 31) ? (pa & 31) < (pb & 31) : pa < pb;
-            });
-            std::vector<int32_t> half[2];
-            int nb[2][32] = {{0}, {0}};
-            for (size_t i0 = 0; i0 < rows.size();) {
-                size_t i1 = i0;
-                const int32_t pd = (*row2pdf)[size_t(rows[i0])];
-                while (i1 < rows.size() && (*row2pdf)[size_t(rows[i1])] == pd) ++i1;
-                const int bk = pd & 31, free0 = cap0 - int(half[0].size()), free1 = cap1 - int(half[1].size());
-                int h = nb[0][bk] < nb[1][bk] ? 0 : (nb[1][bk] < nb[0][bk] ? 1 : (free0 >= free1 ? 0 : 1));
-                if ((h ? free1 : free0) <= 0) h = 1 - h;
-                for (size_t i = i0; i < i1; ++i) {
-                    if (int(half[h].size()) >= (h ? cap1 : cap0)) h = 1 - h;  // (the group is cut: both halves read the pdf)
-                    if (half[h].empty() || (*row2pdf)[size_t(half[h].back())] != pd) ++nb[h][bk];
-                    half[h].push_back(rows[i]);
-                }
-                i0 = i1;
-            }
-            std::vector<int32_t> out = half[0];
-            out.insert(out.end(), half[1].begin(), half[1].end());
-            Segment trial = sg;
-            trial.rows = out;
-            if (half_cost(trial) <= half_cost(sg)) sg.rows = std::move(out);
-            after += half_cost(sg);
-        }
-        if (getenv("MM_VERBOSE_PLAN")) fprintf(stderr, "[mm] pdf_halves: extra LDS cycles of the emission reads %lld -> %lld (%zu segments)\n", before, after, p.segs.size());
-    }
     const int nwc = std::max(1, std::min<int>(opt.nwc_max, int(p.segs.size())));
     auto cost = [&](const Segment &s) { return s.A + opt.finish_cost + opt.group_cost * log2i(s.g); };
     std::vector<int> idx(p.segs.size());
@@ -224,6 +277,18 @@ Plan plan_for(const std::vector<int32_t> &rows, const std::vector<int64_t> &rowp
     p.wave_segs.assign(nwc, {});
     p.n4.assign(nwc, 0);
     auto level = [&](int w, int extra) { return float(load[w] + extra) / opt.group_speed[std::min(w >> 2, 3)]; };
+    {   // no dealing brings the most loaded wave below the mean load, or below the longest segment on the fastest wave
+        float total = 0.f, speed = 0.f, fastest = 0.f;
+        for (int w = 0; w < nwc; ++w) speed += opt.group_speed[std::min(w >> 2, 3)], fastest = std::max(fastest, opt.group_speed[std::min(w >> 2, 3)]);
+        for (const Segment &sg : p.segs) total += float(cost(sg));
+        const float lb = std::max(total / speed, idx.empty() ? 0.f : float(cost(p.segs[idx[0]])) / fastest);
+        if (int(lb + 0.5f) > bound) {
+            p.pruned = true;
+            return p;
+        }
+    }
+    // (the forms with positions of their own -- wave, Viterbi -- keep the plain dealing)
+    const bool may_exchange = opt.every_cap && opt.mix_n4 < 0 && !opt.seg_stride && !opt.acap_force;
     for (int i : idx) {
         int best = -1;
         const int c = cost(p.segs[i]);
@@ -237,7 +302,11 @@ Plan plan_for(const std::vector<int32_t> &rows, const std::vector<int64_t> &rowp
             }
             if (best < 0 || level(w, c) < level(best, c) || (level(w, c) == level(best, c) && arcs[w] < arcs[best])) best = w;
         }
-        if (best < 0) return p;  // more than MM_ROW_MAX_SLOTS segments per wave
+        if (best < 0 && may_exchange) {
+            best = make_room(p, p.segs[i].A, c, opt.ka_max, load, arcs, cost, level);
+            p.exchanges += best >= 0;
+        }
+        if (best < 0) return p;  // more than MM_ROW_MAX_SLOTS segments per wave, or no room in any
         p.segs[i].wave = best;
         p.wave_segs[best].push_back(i);
         load[best] += cost(p.segs[i]);
@@ -502,17 +571,51 @@ bool make_rows(int64_t nrows, const std::vector<int64_t> &rowptr, const std::vec
     if (opt.copy_perm && ((ntot + 1 + 31) & ~int64_t(31)) * 4 > opt.rs) return false;  // (copy 1 scrambles inside blocks of 32)
     // ---- schedule: the cap on arcs per lane of one row decides how many rows are split over lane groups; take
     // the cap whose most loaded wave is cheapest
+    // Every even cap from 12 up to the register window (rows of up to ka_max arcs fit one lane; 48 and 64 for the forms whose
+    // window allows them), but: a cap that gives every row the lanes of the cap before gives the same plan (the lanes only
+    // fall as the cap grows), and a plan that cannot beat the best so far is not dealt (plan_for's bound).  Small graphs --
+    // every row below 12 arcs -- thus cost ONE plan.  The wave and Viterbi forms fix their cap.
+    std::vector<int> degs;  // the distinct row lengths
+    for (int32_t r : myrows) degs.push_back(int(rowptr[r + 1] - rowptr[r]));
+    std::sort(degs.begin(), degs.end());
+    degs.erase(std::unique(degs.begin(), degs.end()), degs.end());
+    std::vector<int> caps;  // the caps to plan with, ascending
+    const int cap_top = std::min(opt.ka_max, 64);
+    if (opt.acap_force) {
+        caps.push_back(opt.acap_force);
+    } else if (opt.every_cap) {
+        for (int c = 12; c <= cap_top; c += 2) caps.push_back(c);
+    } else {
+        for (int c : {12, 16, 24, 32, 48, 64})
+            if (c <= cap_top) caps.push_back(c);
+    }
+    std::vector<int> lanes, lanes_before;
     Plan best;
-    for (int acap : {4, 12, 16, 24, 32, 48, 64}) {
-        if (opt.acap_force ? acap != opt.acap_force : (acap == 4 || acap > opt.ka_max)) continue;
-        Plan p = plan_for(myrows, rowptr, acap, opt, &row2pdf);
-        if (!p.ok && getenv("MM_VERBOSE_PLAN"))
-            fprintf(stderr, "[mm] plan with at most %d arcs per lane and row: %zu segments on %zu waves, KA %d (limit %d)\n", acap, p.segs.size(),
-                    p.wave_segs.size(), p.KA, opt.ka_max);
+    for (int acap : caps) {
+        lanes.clear();
+        for (int d : degs) lanes.push_back(lanes_for(d, acap, opt));
+        if (lanes == lanes_before) continue;
+        lanes_before = lanes;
+        Plan p = plan_for(myrows, rowptr, acap, opt, &row2pdf, best.ok ? best.maxcost : std::numeric_limits<int>::max());
+        if (!p.ok && getenv("MM_VERBOSE_PLAN")) {
+            if (p.pruned)
+                fprintf(stderr, "[mm] plan with at most %d arcs per lane and row: %zu segments, not dealt (its mean load is above the best cost %d)\n", acap,
+                        p.segs.size(), best.maxcost);
+            else
+                fprintf(stderr, "[mm] plan with at most %d arcs per lane and row: %zu segments on %zu waves, no wave has room for all (limit %d)\n", acap,
+                        p.segs.size(), p.wave_segs.size(), opt.ka_max);
+        }
         if (!p.ok) continue;
-        if (!best.ok || p.maxcost < best.maxcost || (p.maxcost == best.maxcost && p.KA < best.KA)) best = std::move(p);
+        if (getenv("MM_VERBOSE_PLAN"))
+            fprintf(stderr, "[mm] plan with at most %d arcs per lane and row: %zu segments, cost %d..%d, KA %d\n", acap, p.segs.size(), p.mincost, p.maxcost, p.KA);
+        // lowest cost of the most loaded wave, then fewest arc slots; of plans that tie in both, the one with fewer segments (config 3's
+        // forward form: cap 38, 40 segments, against cap 36, 41 segments, both 70 / 44 -- 2.559 against 2.595 ms per step)
+        if (!best.ok || p.maxcost < best.maxcost || (p.maxcost == best.maxcost && p.KA < best.KA) ||
+            (opt.every_cap && p.maxcost == best.maxcost && p.KA == best.KA && p.segs.size() < best.segs.size()))
+            best = std::move(p);
     }
     if (!best.ok) return false;
+    if (opt.pdf_halves) deal_pdf_halves(best, row2pdf);
     PROF_LAP(0);
     const int NWC = int(best.wave_segs.size());
     int KA = std::max(2, (best.KA + 1) & ~1);
@@ -552,6 +655,7 @@ bool make_rows(int64_t nrows, const std::vector<int64_t> &rowptr, const std::vec
     g.ncopy = opt.copies ? opt.copies : (opt.pair ? 1 : 2);
     const uint32_t SC = uint32_t(g.scale);
     const bool want_q = (backward || opt.pair || opt.want_partner) && opt.q_positions;  // pdf-major positions
+    g.exchanges = best.exchanges;
     g.maxcost = best.maxcost;
     g.mincost = best.mincost;
     // ---- numbering: the order in which the rows are finished

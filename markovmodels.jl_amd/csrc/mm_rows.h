@@ -17,7 +17,9 @@
 //     stores -- one finish per row per frame, no partial sums through LDS and no barrier between the
 //     products and the finishing step (the quad kernels need both);
 //   * the segments are dealt to the waves longest-processing-time first under a cost model (arcs + a constant
-//     per finish), so that the waves reach the single barrier of a frame together;
+//     per finish), so that the waves reach the single barrier of a frame together; how many lanes a long row gets
+//     follows from a cap on the arcs of one row per lane, and every even cap from 12 up to ka_max is planned: the
+//     plan with the cheapest most loaded wave is kept (then fewest arc slots);
 //   * internal numbering ("position") of the states of one direction = the order in which they are finished
 //     (wave, segment, lane group): the stores of a finish go to 64 / g consecutive positions (conflict free
 //     in LDS, coalesced in the alpha store);
@@ -74,6 +76,7 @@ struct RowGraph {
     double pad_eff = 0;           // real arcs / arc slots
     float wmin_log2 = 0;          // smallest log2 weight of an arc
     int maxcost = 0, mincost = 0; // cost model: most / least loaded wave
+    int exchanges = 0;            // segments of the plan that found a wave only after an exchange of two others
 };
 
 struct RowPackOpts {
@@ -143,6 +146,10 @@ struct RowPackOpts {
     // Pair forms: the rows of a segment are dealt to its two half-waves so that the emission factors a finish reads (8 bytes at
     // 8 * pdf) meet in as few bank pairs as possible (plan_for)
     bool pdf_halves = false;
+    // The caps on the arcs of one row per lane that are planned: true = every even cap from 12 up to ka_max, an exchange of two
+    // segments when one finds no wave with room, ties to the plan with fewer segments; false = the caps 12, 16, 24, 32, 48, 64
+    // alone and the plain dealing (the team forms: their kernels measured no gain from the longer list)
+    bool every_cap = true;
     bool naive_stats = true;  // also model the arcs in CSR order (RowGraph::conflict_before: informational)
     bool q_positions = true;  // pdf-major positions of the rows (the kernels that sum the posteriors per pdf over contiguous ranges);
                               // false: the slot table's q field stays 0 (the wave kernel has its own pdf tables)
