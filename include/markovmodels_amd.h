@@ -117,6 +117,7 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * 5 = mm_samplepaths_f32 (log batches only), 6 = mm_expectedcost_f32 (log batches only), 7 = mm_leakyposteriors_f32 (log batches
  * only),
  * 8 = mm_pathentropy_f32 (log batches only): mm_entropy_fwd_kernel<NI,lds|global> + mm_entropy_bwd_kernel<...>.
+ * 9 = mm_filterposteriors_f32 (log batches only): mm_filter_kernel<NI,lds|global>.
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -340,6 +341,56 @@ int mm_leakyposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b,
 int mm_pathentropy_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
                        float *entropy, float *grad, float *gamma, int64_t g_stride_b, int64_t g_stride_n, int64_t g_stride_p,
                        float *ttl, void *stream);
+
+/* Forward filtering posteriors with a carried state: the causal quantities of a log batch -- what online confidence, keyword /
+ * filler spotting, HMM-smoothed activity detection and endpointing run on -- and the way to run a recursion over audio in chunks.
+ * Every other posterior of this header is a smoothing quantity and needs the whole utterance.  For utterance b the extended system
+ * is that of src/fsm.jl:19-28 (S real states and the phony final state f, T_hat = [T omega; 0 1]) with lhs = C_hat * expand(V_b)
+ * and length len = len_b, exactly as mm_pdfposteriors_f32 uses it; frames counted from 1 here and from 0 in the arrays:
+ *
+ *   start(j)     = alpha_hat(j)  (state_in == NULL)   or   exp(state_in_b(j))   for real j;   start(f) = 0
+ *   a_1(j)       = start(j) lhs_1(j)
+ *   a_n(j)       = lhs_n(j) sum_i a_{n-1}(i) T_hat(i,j)                  n = 2..len     (a_n(f) = 0: the phony pdf is -inf there)
+ *   l_n          = ln sum_j a_n(j),   l_0 := 0
+ *   incr(n)      = l_n - l_{n-1}                                         ln P(V_n | V_1..n-1) given the start vector
+ *   filt(n,p)    = sum_{j : pdf(j) = p} a_n(j) / sum_j a_n(j)            the filtering posterior; rows sum to 1
+ *   state_out(j) = ln sum_i a_len(i) T_hat(i,j) - l_len                  for ALL j of the extended system, j = f included
+ *   ttl          = l_len + state_out(f)                                  = log Z_b when state_in == NULL
+ *
+ * state_out is the one-step prediction before the next emission, normalised by the mass alive at the last frame; its final entry
+ * is the log of the fraction of that mass the final weights accept.  It follows that sum_n incr(n) + state_out(f) is the log Z
+ * mm_pdfposteriors_f32 normalises by; that CHUNKING IS EXACT -- a call on frames 1..L1 and a second call on frames L1+1..L with
+ * state_in = the first call's state_out give, concatenated, the filt and incr of the single call, and log Z = the sum of incr over
+ * all chunks + state_out(f) of the last chunk --; that filt(n,.) and incr(n) do not depend on V at frames after n; that on a graph
+ * whose final weights are the same for every real state filt(len,.) is the smoothing posterior gamma(len,.) (on other graphs it is
+ * not); and that a constant added to all emissions of a frame changes filt not at all and incr of that frame by that constant.
+ *   V, lens, N   as mm_pdfposteriors_f32
+ *   state_in     device float[mm_batch_total_states], natural log: element (b, s) at state_offset_b + s (one column of
+ *                mm_alpharecursion_f32's layout).  NULL: the FSMs' own initial vectors.  The entry of the phony final state is ignored
+ *   state_out    device, out, same layout (NULL: not written).  state_in == state_out is allowed: a workgroup reads its segment
+ *                before it writes it
+ *   filt         device, out (NULL: not computed): element (b, n, p) at filt[b*f_stride_b + n*f_stride_n + p*f_stride_p],
+ *                probabilities; the strides as mm_leakyposteriors_f32's (the reference's column-major B x P x N layout included).
+ *                Strides that cannot hold B x N x P distinct elements: MM_ERR_DIM
+ *   incr         device, out (NULL: not written): element (b, n) at incr[b*i_stride_b + n].  i_stride_b < N: MM_ERR_DIM
+ *   ttl          device float[B], out (NULL: not written)
+ * All four outputs NULL: MM_ERR_INVALID.  Conventions: frames n >= len_b of filt and incr are exact zeros.  len_b = 0 gives
+ * filt = 0, incr = 0, ttl = -inf and state_out = a copy of state_in -- with state_in == NULL: ln alpha_hat, the vector NULL stands
+ * for (how a caller obtains a reset vector).  An utterance whose alive mass becomes zero at frame d <= len_b (a frame of all -inf,
+ * a start vector without a live state) keeps its values of the frames before d; from d on filt = 0 and incr = -inf, ttl = -inf and
+ * state_out = -inf everywhere.  Nothing is NaN.
+ * MM_LOG batches only: Tropical and ProbSemiring batches return MM_ERR_UNSUPPORTED.  Runs on the item form of every FSM of every log
+ * batch (any size, shared or distinct graphs), one workgroup per utterance, whatever kernels mm_pdfposteriors_f32 picks for the
+ * batch: ONE kernel, the forward step of the item kernel; behind each step's barrier the per-pdf sums of the finished frame are
+ * taken over fixed lists relative to that frame's own maximum -- no atomics, so a repeated call returns the same bits, and filt
+ * does not depend on the level of V.  No frame is kept: the call uses no workspace, whatever N.  The exact, mark and gamma policies
+ * and the posterior floor do not apply.  Stream contract of mm_arcposteriors_f32: launches on `stream` only, no host
+ * synchronisation; it can be captured in a hipGraph once a first call has put the batch's item forms on the device (a capture
+ * before that returns MM_ERR_INVALID). */
+int mm_filterposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                            const float *state_in, float *state_out,
+                            float *filt, int64_t f_stride_b, int64_t f_stride_n, int64_t f_stride_p,
+                            float *incr, int64_t i_stride_b, float *ttl, void *stream);
 
 /* alpha-recursion(alpha_hat, T_hat', C_hat*V_hat) (src/inference.jl:62-74) as
  * called from pdfposteriors (:150-152): out is the reference's state_A, a

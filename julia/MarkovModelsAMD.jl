@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -339,6 +339,36 @@ function leakyposteriors(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing; le
         pointer(γ), 1, B * P, B, pointer(ttl),
         AMDGPU.stream().stream))
     γ, ttl
+end
+
+"""
+    filterposteriors(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing; state = nothing, filt = true) -> (filt, incr, ttl, state_out)
+
+Forward filtering posteriors with a carried state (mm_filterposteriors_f32 in the header) of a log-semiring batch: `filt` (B × P × N
+like `pdfposteriors`' γ) = P(pdf_n = p | V up to frame n), `incr` (N × B) = log P(V_n | V before n), ttl = log Z when `state` is
+`nothing`, and `state_out` (`total_states(b)` natural logs: the one-step prediction behind the last frame, the final entries the log
+of the alive mass the final weights accept).  `state` = an earlier call's `state_out` continues where that call stopped: chunking is
+exact, and log Z = the sum of all `incr` + the last `state_out`'s final entry.  `filt = false` skips the per-pdf pass (`filt` comes
+back as `nothing`; the other results keep their bits).  `V` and `lens` as for `pdfposteriors`; `lens[b] = 0` passes the state through.
+"""
+function filterposteriors(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing; state = nothing, filt = true)
+    P, N, B = size(V)
+    P == b.P || throw(DimensionMismatch("V has $P pdfs, the FSMs $(b.P)"))
+    S = Int(ccall((:mm_batch_total_states, LIB), Int64, (Ptr{Cvoid},), b.handle))
+    state === nothing || length(state) == S || throw(DimensionMismatch("state has $(length(state)) entries, the batch $S states"))
+    f = filt ? ROCArray{Float32}(undef, B, P, N) : nothing
+    incr = ROCArray{Float32}(undef, N, B)
+    ttl = ROCArray{Float32}(undef, B)
+    state_out = ROCArray{Float32}(undef, S)
+    lp = lens === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(lens))
+    check(ccall((:mm_filterposteriors_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Float32}, Ptr{Float32},
+         Ptr{Float32}, Int64, Int64, Int64, Ptr{Float32}, Int64, Ptr{Float32}, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, lp, N,
+        state === nothing ? Ptr{Float32}(C_NULL) : pointer(state), pointer(state_out),
+        filt ? pointer(f) : Ptr{Float32}(C_NULL), 1, B * P, B, pointer(incr), N, pointer(ttl),
+        AMDGPU.stream().stream))
+    f, incr, ttl, state_out
 end
 
 """

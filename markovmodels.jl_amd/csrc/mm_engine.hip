@@ -431,7 +431,7 @@ static Geometry pick_geometry(mm_batch_t h) {
 }
 
 // ---- one plan per entry that runs on the item form: its launch geometry and where its state vectors live
-enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy };
+enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter };
 struct ItemPlan {
     ItemEntry e;
     int NW, NI;        // waves per workgroup, register-resident items per wave of the instance (8 or 0)
@@ -440,8 +440,9 @@ struct ItemPlan {
     size_t lds_bytes;  // dynamic LDS of the chosen placement (Arcs: of the forward kernel; mm_arc_kernel adds MM_ARC_LDS_EXTRA)
 };
 // The only source of the above.  The vectors are global when the entry's LDS plan (the item kernel's, with the stage rows for
-// all but the export modes, + the arc kernel's extra; Cost: cost_lds_plan; Leaky: leaky_lds_plan; Entropy: entropy_lds_plan) does not fit
-// 160 KB, when MM_BIGV asks for it, or for the arc, sampling, cost, leaky and entropy kernels when NI = 0: they have no streamed-only instance with the vectors in LDS.
+// all but the export modes, + the arc kernel's extra; Cost: cost_lds_plan; Leaky: leaky_lds_plan; Entropy: entropy_lds_plan; Filter:
+// filter_lds_plan, no larger than the export modes') does not fit 160 KB, when MM_BIGV asks for it, or for the arc, sampling, cost,
+// leaky, entropy and filter kernels when NI = 0: they have no streamed-only instance with the vectors in LDS.
 // `global` never depends on max_items, nor does NI except Tropical's (8: the whole graph is register-resident): mm_batch_create
 // asks before the item forms are up, and ensure_item_forms raises max_items later -- only NW follows it.
 static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
@@ -451,14 +452,16 @@ static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
     auto bytes = [&](int S1p) {
         if (e == ItemEntry::Leaky) return mm_leaky_lds_bytes(S1p, P1p);
         if (e == ItemEntry::Entropy) return mm_entropy_lds_bytes(S1p, P1p);
+        if (e == ItemEntry::Filter) return mm_filter_lds_bytes(S1p, P1p);
         return e == ItemEntry::Cost ? mm_cost_lds_bytes(S1p, P1p) : size_t(lds_plan(S1p, P1p, e != ItemEntry::Export).total) * 4;
     };
-    const bool derived = e == ItemEntry::Arcs || e == ItemEntry::Sample || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy;
+    const bool derived = e == ItemEntry::Arcs || e == ItemEntry::Sample || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy ||
+                         e == ItemEntry::Filter;
     ItemPlan pl{e, g.NW, g.NI, false, false, 0};
     pl.global = bytes(h->max_S1p) + (e == ItemEntry::Arcs ? MM_ARC_LDS_EXTRA : 0) > lds_max || h->dbg.bigv || (derived && g.NI == 0);
     pl.lds_bytes = bytes(pl.global ? 0 : h->max_S1p);
     // (8 items' arcs and their sums / the pair arithmetic / the leak term and its sums per wave: compiled for 8 waves per CU)
-    if (e == ItemEntry::Arcs || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy) pl.NW = std::min(g.NW, 8);
+    if (e == ItemEntry::Arcs || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy || e == ItemEntry::Filter) pl.NW = std::min(g.NW, 8);
     if (e == ItemEntry::Sample) pl.stage = !pl.global && !h->dbg.sample_nostage && size_t(h->max_S1p) * 8 <= lds_max;
     if (e == ItemEntry::Tropical) {
         // register-resident items when the whole graph fits 8 items per wave -- as many waves as there is work for (latency), at most
@@ -2593,6 +2596,12 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
         const std::string inst = "<" + std::to_string(pl.NI) + "," + where_of(pl.global) + ">";
         s = "mm_entropy_fwd_kernel" + inst + " (forward: alpha~ and Hf, entropy and ttl; alone and without a store when neither grad nor gamma is asked for) + mm_entropy_bwd_kernel" +
             inst + " (backward: beta~ and Hb, gamma and grad per pdf); state vectors " + (pl.global ? "in global memory" : "in LDS");
+    } else if (entry == 9) {  // mm_filterposteriors_f32
+        if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_filterposteriors_f32 runs on log-semiring batches only");
+        const ItemPlan pl = item_plan(h, ItemEntry::Filter);
+        s = "mm_filter_kernel<" + std::to_string(pl.NI) + "," + where_of(pl.global) +
+            "> (forward alone: filt and incr per frame from the finished vector, state_out and ttl; no frame kept); state vectors " +
+            (pl.global ? "in global memory" : "in LDS");
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -2998,7 +3007,8 @@ int mm_pdfposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
 }
 
 }  // extern "C"
-// ---- the entries on the item form beside pdfposteriors: arc posteriors, path sampling, expected cost, leaky posteriors, path entropy (log batches only)
+// ---- the entries on the item form beside pdfposteriors: arc posteriors, path sampling, expected cost, leaky posteriors, path entropy,
+// filtering posteriors (log batches only)
 
 // What they start with: the semiring refusal, check_run, the entry's own argument checks (`args`), the item forms -- ahead
 // of the plan: a batch created without them has max_items = 0 until they are up, and the plan would size the workgroups for no
@@ -3019,10 +3029,12 @@ static int item_entry_begin(mm_batch_t h, const char *who, ItemEntry e, const fl
 // the per-frame offsets as the item kernel keeps them; Arcs: the float64 sums of all backward slots, the state posteriors of
 // frame 1; Cost: the r store and its offsets, and for FSMs beyond the LDS the state vectors of both kernels ([B][8 * max S1p]
 // floats); Entropy: as Cost, the Hf store in the place of the r store -- and no such store for a value-only call (`store` false).
-// total: no less than what mm_pdfposteriors_f32 needs for as many frames.  (mm_batch_reserve does not cover it.)
+// total: no less than what mm_pdfposteriors_f32 needs for as many frames.  (mm_batch_reserve does not cover it.)  Filter keeps
+// nothing: its offsets stay in registers, total = 0 whatever N -- the workspace is neither grown nor touched.
 struct ItemWs { size_t c = 0, acc = 0, post1 = 0, r = 0, o = 0, big = 0, total = 0; };
 static ItemWs item_ws_layout(mm_batch_t h, const ItemPlan &pl, int64_t N, bool store = true) {
     ItemWs W;
+    if (pl.e == ItemEntry::Filter) return W;
     const size_t rows = align_up(size_t(h->total_s1p) * size_t(N + 1) * 4, 256);
     W.c = rows;
     W.total = W.c + ws_c_bytes(h, N);
@@ -3241,6 +3253,39 @@ int mm_pathentropy_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, c
         ep.big_stride = 8ll * h->max_S1p;
     }
     return mm_launch_entropy(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, backward, p, ep, static_cast<hipStream_t>(stream));
+}
+
+// ---- forward filtering posteriors with a carried state (mm_kernel_filter.hip)
+int mm_filterposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, const float *state_in,
+                            float *state_out, float *filt, int64_t fsb, int64_t fsn, int64_t fsp, float *incr, int64_t isb, float *ttl,
+                            void *stream) {
+    // what the arguments alone show comes first (without a batch: the frames' own extent), then the batch's refusals
+    if (!state_out && !filt && !incr && !ttl) return fail(MM_ERR_INVALID, "mm_filterposteriors_f32: state_out, filt, incr and ttl are all NULL");
+    if (incr && isb < N) return fail(MM_ERR_DIM, "mm_filterposteriors_f32: i_stride_b " + std::to_string(isb) + " < " + std::to_string(N) + " frames");
+    {
+        const int64_t B = h ? h->B : 1, P = h ? h->max_P1 - 1 : 1;
+        if (filt && !strides_hold(fsb, B, fsn, N, fsp, P))
+            return fail(MM_ERR_DIM, "mm_filterposteriors_f32: f strides (" + std::to_string(fsb) + ", " + std::to_string(fsn) + ", " + std::to_string(fsp) +
+                                        ") cannot hold " + std::to_string(B) + " x " + std::to_string(N) + " x " + std::to_string(P) + " elements");
+    }
+    ItemPlan pl;
+    int rc = item_entry_begin(h, "mm_filterposteriors_f32", ItemEntry::Filter, V, N, stream, []() { return int(MM_OK); }, &pl);
+    if (rc) return rc;
+    const ItemWs W = item_ws_layout(h, pl, N);
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    rc = item_ws_bind(h, pl, W, p, stream);
+    if (rc) return rc;
+    FilterParams fp{};
+    fp.state_in = state_in;
+    fp.state_out = state_out;
+    fp.filt = filt;
+    fp.fsb = fsb;
+    fp.fsn = fsn;
+    fp.fsp = fsp;
+    fp.incr = incr;
+    fp.isb = isb;
+    fp.ttl = ttl;
+    return mm_launch_filter(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, p, fp, static_cast<hipStream_t>(stream));
 }
 
 // ---- pdf posteriors of the leaky HMM (mm_kernel_leaky.hip)

@@ -267,4 +267,19 @@ struct LeakParams {
 int mm_launch_leaky(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, const RunParams &p, const LeakParams &lp, hipStream_t stream);
 size_t mm_leaky_lds_bytes(int S1p, int P1p);
 
+// ---- forward filtering posteriors with a carried state (mm_filter_tu.hip: mm_filter_kernel on the item form)
+struct FilterParams {
+    const float *state_in;  // [total states] natural log, element (b, s) at state_off_b + s; NULL: the FSMs' own initial vectors
+    float *state_out;       // as state_in (may be the same buffer); NULL: not asked for
+    float *filt;            // NULL: not asked for
+    long long fsb, fsn, fsp;
+    float *incr;            // [b * isb + n]; NULL: not asked for
+    long long isb;
+    float *ttl;             // NULL: not asked for
+};
+// lds_bytes: filter_lds_plan(...).total * 4 of the geometry (state vectors in LDS, or bigv: in RunParams::ws_big); the call keeps
+// nothing in the workspace
+int mm_launch_filter(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, const RunParams &p, const FilterParams &fp, hipStream_t stream);
+size_t mm_filter_lds_bytes(int S1p, int P1p);
+
 }  // namespace mm

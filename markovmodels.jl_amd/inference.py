@@ -499,6 +499,58 @@ class BatchedFSM:
             return gamma.cpu().numpy(), ttl.cpu().numpy()
         return gamma, ttl
 
+    def filterposteriors(self, V, lens=None, state=None, out=None, want_state=False, want_filt=True):
+        """Forward filtering posteriors with a carried state (mm_filterposteriors_f32): ``(filt[B, N, P], incr[B, N], ttl[B])``,
+        plus ``state_out[total_states]`` when ``want_state``.  ``filt[b, n, p]`` = P(pdf_n = p | V_b at frames 0..n), the causal
+        counterpart of ``pdfposteriors``' gamma; ``incr[b, n]`` = ln P(V_n | V_0..n-1), the increments of the prefix
+        log-likelihood; ``ttl`` = log Z as ``pdfposteriors`` returns it when ``state`` is None.  ``state`` continues a recursion
+        where an earlier call stopped: a float32 device tensor ``[total_states]`` of natural logs, element (b, s) at
+        ``state_offsets[b] + s`` -- an earlier call's ``state_out`` (the one-step prediction behind its last frame, its final
+        entries the log of the mass the final weights accept); None starts from the FSMs' own initial vectors.  Chunking is
+        exact: the ``filt`` and ``incr`` of consecutive chunks are those of one call on the whole, and log Z = the sum of all
+        ``incr`` + the last ``state_out``'s final entry (``streaming.ForwardFilter`` keeps that book).  ``lens[b] = 0`` passes
+        the state through.  With ``want_filt=False`` ``filt`` is None and not computed: the same ``incr``, ``ttl`` and state,
+        bit for bit (likelihood only).  ``want_state`` may also be the tensor that receives the state -- ``state`` itself included:
+        a workgroup reads its segment before it writes it.  ``out`` as for ``pdfposteriors``.  Frames beyond the lengths are zeros; from a frame
+        without a live state on ``filt`` = 0 and ``incr`` = -inf.  No frame is kept: the call uses no workspace.  Log batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        if out is not None:
+            # the kernels write through raw pointers and strides: a wrong buffer is memory corruption, not an exception
+            if not want_filt:
+                raise ValueError("out given with want_filt=False")
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != Vt.device:
+                raise TypeError("out must be a float32 tensor on V's device")
+            if out.dim() != 3 or tuple(out.shape) != (B, N, P):
+                raise _lib.DimensionMismatch(-2, f"out must be [B={B}, N={N}, P={P}], got {tuple(out.shape)}")
+        st = None
+        if state is not None:
+            st = torch.as_tensor(np.ascontiguousarray(state, dtype=np.float32)).cuda() if not isinstance(state, torch.Tensor) else state
+            if st.dtype != torch.float32 or st.device != Vt.device:
+                raise TypeError("state must be a float32 tensor on V's device")
+            if st.dim() != 1 or st.numel() != self.total_states or not st.is_contiguous():
+                raise _lib.DimensionMismatch(-2, f"state must be a contiguous [{self.total_states}] vector, got {tuple(st.shape)}")
+        filt = (out if out is not None else torch.empty((B, N, P), dtype=torch.float32, device=Vt.device)) if want_filt else None
+        incr = torch.empty((B, N), dtype=torch.float32, device=Vt.device)
+        ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        so = None
+        if isinstance(want_state, torch.Tensor):
+            so = want_state
+            if so.dtype != torch.float32 or so.device != Vt.device:
+                raise TypeError("the state buffer must be a float32 tensor on V's device")
+            if so.dim() != 1 or so.numel() != self.total_states or not so.is_contiguous():
+                raise _lib.DimensionMismatch(-2, f"the state buffer must be a contiguous [{self.total_states}] vector, got {tuple(so.shape)}")
+        elif want_state:
+            so = torch.empty(self.total_states, dtype=torch.float32, device=Vt.device)
+        fs = (filt.stride(0), filt.stride(1), filt.stride(2)) if filt is not None else (0, 0, 0)
+        check(lib.mm_filterposteriors_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
+                                          lt.data_ptr() if lt is not None else None, N,
+                                          st.data_ptr() if st is not None else None, so.data_ptr() if so is not None else None,
+                                          filt.data_ptr() if filt is not None else None, fs[0], fs[1], fs[2],
+                                          incr.data_ptr(), incr.stride(0), ttl.data_ptr(), self._stream(torch)))
+        res = (filt, incr, ttl) + ((so,) if so is not None else ())
+        return tuple(t.cpu().numpy() if t is not None else None for t in res) if as_numpy else res
+
     def maxstateposteriors(self, V, lens=None):
         """Max-marginals of the tropical semiring, (sum S1) x (N+1), computed on the device."""
         return self._export(lib.mm_maxstateposteriors_f32, V, lens)
@@ -582,11 +634,11 @@ class BatchedFSM:
     def kernels(self, semiring: str = "log") -> str:
         """The kernels the engine launches for this batch (informational): "log" = pdfposteriors, "tropical" = bestpath, "export" =
         alpharecursion / betarecursion, "arcs" = arcposteriors, "sample" = samplepaths, "cost" = expectedcost, "leaky" =
-        leakyposteriors, "entropy" = pathentropy."""
+        leakyposteriors, "entropy" = pathentropy, "filter" = filterposteriors."""
         import ctypes
 
         buf = ctypes.create_string_buffer(1024)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8}[semiring], buf, 1024))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9}[semiring], buf, 1024))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -904,6 +956,30 @@ def leakyposteriors(fsm, Vhats, Chats=None, leak=1e-5, seqlengths=None):
     V, lens = _need_expanded(Vh, bf.semiring)
     g, ttl = bf.leakyposteriors(V, lens, leak=leak)
     return np.ascontiguousarray(g.transpose(0, 2, 1)), ttl
+
+
+def filterposteriors(fsm, Vhats, Chats=None, seqlengths=None):
+    """Forward filtering posteriors -- see ``BatchedFSM.filterposteriors`` -- in ``pdfposteriors``' call shape, from the FSMs' own
+    initial vectors: ``fsm`` the rawunion of the batch with its state maps, or a BatchedFSM / CompiledFSM (log semiring,
+    Float32); V_hats what ``expand`` makes.  Returns (filt[B, P, N] probabilities, incr[B, N], ttl[B]): NumPy arrays for host
+    inputs, device tensors for float32 V_hats on the HIP device given with their ``seqlengths``."""
+    if not hasattr(Vhats, "dim"):  # (a generator is read once)
+        Vhats = list(Vhats)
+    bf = _as_batch(fsm, Chats)
+    Vd = _device_vhats(Vhats)
+    if Vd is not None and seqlengths is not None:
+        torch = _torch()
+        B, P1, N1 = Vd.shape
+        if B != bf.B:
+            raise _lib.DimensionMismatch(-2, f"{B} matrices V_hat for a batch of {bf.B} FSMs")
+        lens = torch.as_tensor(seqlengths, dtype=torch.int32, device=Vd.device)
+        f, incr, ttl = bf.filterposteriors(Vd[:, : P1 - 1, : N1 - 1].transpose(1, 2).contiguous(), lens)
+        return f.transpose(1, 2), incr, ttl
+    # (device V_hats without their lengths: to the host, as pdfposteriors moves them, where the phony row gives the lengths)
+    Vh = [np.asarray(v.cpu() if hasattr(v, "cpu") else v) for v in Vhats]
+    V, lens = _need_expanded(Vh, bf.semiring)
+    f, incr, ttl = bf.filterposteriors(V, lens)
+    return np.ascontiguousarray(f.transpose(0, 2, 1)), incr, ttl
 
 
 def arcposteriors(fsm, Vhats, Chats=None, want_init=False):
