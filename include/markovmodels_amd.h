@@ -118,6 +118,7 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * only),
  * 8 = mm_pathentropy_f32 (log batches only): mm_entropy_fwd_kernel<NI,lds|global> + mm_entropy_bwd_kernel<...>.
  * 9 = mm_filterposteriors_f32 (log batches only): mm_filter_kernel<NI,lds|global>.
+ * 10 = mm_windowposteriors_f32 (log batches only): mm_window_fwd_kernel<NI,lds|global> + mm_window_bwd_kernel<...>.
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -391,6 +392,59 @@ int mm_filterposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b
                             const float *state_in, float *state_out,
                             float *filt, int64_t f_stride_b, int64_t f_stride_n, int64_t f_stride_p,
                             float *incr, int64_t i_stride_b, float *ttl, void *stream);
+
+/* Fixed-lag smoothing posteriors: the forward-backward of a log batch over a WINDOW of the audio, which starts from a carried vector
+ * instead of the FSM's initial vector and ends open (beta = 1 on every real state: the audio goes on) or on the final weights.
+ * What lies between mm_filterposteriors_f32 (causal, nothing of the future) and the smoothing entries (the whole utterance):
+ * P(pdf_n | V_1..n+L) for online alignment, keyword spotting, endpointing and confidence, and the forward-backward of training on
+ * long recordings cut into windows (ttl = ln P(window | carried start), d ttl / d V = gamma, the next window continues from
+ * state_out where mm_leakyposteriors_f32 restarts from the initial distribution).  For utterance b the extended system and
+ * lhs = C_hat * expand(V_b) are exactly those of mm_filterposteriors_f32, len = len_b; frames counted from 1 here and from 0 in the
+ * arrays, f the phony final state:
+ *
+ *   start(j)     = alpha_hat(j)  (state_in == NULL)   or   exp(state_in_b(j))   for real j;   start(f) = 0
+ *   a_1(j)       = start(j) lhs_1(j);   a_n(j) = lhs_n(j) sum_i a_{n-1}(i) T_hat(i,j)     n = 2..len      (the filter's a_n)
+ *   l_n          = ln sum_j a_n(j),   l_0 := 0
+ *   b_len(i)     = 1                   (closed_b == 0: the audio goes on behind the window)
+ *   b_len(i)     = T_hat(i, f)         (closed_b != 0: the audio ends at frame len; the final weights)
+ *   b_n(i)       = sum_{j real} T_hat(i,j) lhs_{n+1}(j) b_{n+1}(j)                         n < len
+ *   gamma(n,p)   = sum_{j : pdf(j) = p} a_n(j) b_n(j) / sum_j a_n(j) b_n(j)                rows sum to 1
+ *   ttl          = ln sum_j a_len(j) b_len(j)      open: = l_len = ln P(V_1..len | start); closed and state_in == NULL: = log Z_b
+ *   c            = commit_b clamped to [0, len]    (commit == NULL: c = len)
+ *   state_out(j) = ln sum_i a_c(i) T_hat(i,j) - l_c     for ALL j, f included: the filter's state_out after c frames
+ *   lcommit      = l_c
+ *
+ *   V, lens, N   as mm_pdfposteriors_f32
+ *   state_in, state_out   layout and aliasing rule of mm_filterposteriors_f32: they may be one buffer.  state_out NULL: not written
+ *   closed       device int32[B]; NULL: every utterance is open
+ *   commit       device int32[B]; NULL: c = len
+ *   lcommit      device float[B], out (NULL: not written)
+ *   gamma        device, out: element (b, n, p) at gamma[b*g_stride_b + n*g_stride_n + p*g_stride_p]; the strides as
+ *                mm_leakyposteriors_f32's.  NULL: MM_ERR_INVALID.  Strides that cannot hold B x N x P distinct elements: MM_ERR_DIM
+ *   ttl          device float[B], out (NULL: not written)
+ * Argument errors that need no device are reported before the NULL-batch check.  MM_LOG batches only: Tropical and ProbSemiring
+ * batches return MM_ERR_UNSUPPORTED.
+ * Conventions: frames n >= len of gamma are exact zeros.  len = 0 gives gamma = 0, ttl = -inf, lcommit = 0 and state_out = a copy
+ * of the start vector (state_in == NULL: ln alpha_hat).  c = 0 with len > 0 also gives a copy of the start vector and lcommit = 0.
+ * A window of zero total mass -- the alive mass dies at some frame d <= len, or the window is closed and the final weights accept
+ * none of it -- gives gamma = 0 in all its frames and ttl = -inf; its state_out and lcommit are still the prefix's values when every
+ * frame up to c is alive, else -inf.  Nothing is NaN.
+ * Consequences: (a) closed with state_in == NULL: gamma and ttl are those of mm_pdfposteriors_f32.  (b) open: gamma(len,.) =
+ * filt(len,.) of mm_filterposteriors_f32, ttl = the sum of its incr, and with c = len state_out is its state_out.  (c) RE-WINDOWING
+ * IS EXACT: a window over frames 1..M with commit c and a second window over frames c+1..M with state_in = the first window's
+ * state_out and the same closed: the second has the first's gamma on frames c+1..M, and its ttl = the first's ttl - the first's
+ * lcommit.  (d) a constant added to every emission of a frame changes gamma not at all and ttl by that constant.  (e) d ttl /
+ * d V(n,p) = gamma(n,p).  (f) gamma(n,.) of an open window does not depend on frames after len.  (g) no atomics: a repeated call
+ * returns the same bits.
+ * Runs on the item form of every FSM of every log batch, one workgroup per utterance: mm_window_fwd_kernel (the filter kernel's
+ * step; the frame's largest emission lives in the float64 offset, every alpha~ row is stored) and mm_window_bwd_kernel (per-pdf
+ * sums over fixed lists, each frame normalised by its own sum).  The exact, mark and gamma policies and the posterior floor do not
+ * apply.  Workspace: the alpha~ store of the item kernel, float32 (sum_b S1p_b) x (N + 1), grown by the call.  Stream contract of
+ * mm_arcposteriors_f32: launches on `stream` only, no host synchronisation; it can be captured in a hipGraph once a first call has
+ * put the batch's item forms on the device and sized the workspace (a capture before that returns MM_ERR_INVALID). */
+int mm_windowposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                            const float *state_in, const int32_t *closed, const int32_t *commit, float *state_out, float *lcommit,
+                            float *gamma, int64_t g_stride_b, int64_t g_stride_n, int64_t g_stride_p, float *ttl, void *stream);
 
 /* alpha-recursion(alpha_hat, T_hat', C_hat*V_hat) (src/inference.jl:62-74) as
  * called from pdfposteriors (:150-152): out is the reference's state_A, a

@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -369,6 +369,36 @@ function filterposteriors(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing; s
         filt ? pointer(f) : Ptr{Float32}(C_NULL), 1, B * P, B, pointer(incr), N, pointer(ttl),
         AMDGPU.stream().stream))
     f, incr, ttl, state_out
+end
+
+"""
+    windowposteriors(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing; state = nothing, closed = nothing, commit = nothing) -> (γ, ttl, lcommit, state_out)
+
+Fixed-lag smoothing posteriors (mm_windowposteriors_f32 in the header) of a log-semiring batch: the forward-backward over a window of
+the audio that starts from `state` (an earlier call's `state_out`; `nothing`: the FSMs' own initial vectors) and ends open -- β = 1 on
+every real state, the audio goes on -- or, for the utterances with `closed[b] != 0`, on the final weights.  `γ` (B × P × N like
+`pdfposteriors`' γ), ttl = log P(window | start), `state_out` = `filterposteriors`' state after `commit[b]` frames (`nothing`: all
+`lens[b]`) and `lcommit` the log-likelihood of those frames.  A second window over the frames from `commit` on, from `state_out`,
+has this window's γ there and ttl - lcommit as its ttl.  `closed` and `commit` are `ROCVector{Int32}` of length B.
+"""
+function windowposteriors(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing; state = nothing, closed = nothing, commit = nothing)
+    P, N, B = size(V)
+    P == b.P || throw(DimensionMismatch("V has $P pdfs, the FSMs $(b.P)"))
+    S = Int(ccall((:mm_batch_total_states, LIB), Int64, (Ptr{Cvoid},), b.handle))
+    state === nothing || length(state) == S || throw(DimensionMismatch("state has $(length(state)) entries, the batch $S states"))
+    γ = ROCArray{Float32}(undef, B, P, N)
+    ttl = ROCArray{Float32}(undef, B)
+    lcommit = ROCArray{Float32}(undef, B)
+    state_out = ROCArray{Float32}(undef, S)
+    ip(x) = x === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(x))
+    check(ccall((:mm_windowposteriors_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Float32}, Ptr{Int32}, Ptr{Int32},
+         Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int64, Int64, Int64, Ptr{Float32}, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, ip(lens), N,
+        state === nothing ? Ptr{Float32}(C_NULL) : pointer(state), ip(closed), ip(commit),
+        pointer(state_out), pointer(lcommit), pointer(γ), 1, B * P, B, pointer(ttl),
+        AMDGPU.stream().stream))
+    γ, ttl, lcommit, state_out
 end
 
 """

@@ -431,7 +431,7 @@ static Geometry pick_geometry(mm_batch_t h) {
 }
 
 // ---- one plan per entry that runs on the item form: its launch geometry and where its state vectors live
-enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter };
+enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter, Window };
 struct ItemPlan {
     ItemEntry e;
     int NW, NI;        // waves per workgroup, register-resident items per wave of the instance (8 or 0)
@@ -441,8 +441,9 @@ struct ItemPlan {
 };
 // The only source of the above.  The vectors are global when the entry's LDS plan (the item kernel's, with the stage rows for
 // all but the export modes, + the arc kernel's extra; Cost: cost_lds_plan; Leaky: leaky_lds_plan; Entropy: entropy_lds_plan; Filter:
-// filter_lds_plan, no larger than the export modes') does not fit 160 KB, when MM_BIGV asks for it, or for the arc, sampling, cost,
-// leaky, entropy and filter kernels when NI = 0: they have no streamed-only instance with the vectors in LDS.
+// filter_lds_plan, no larger than the export modes'; Window: window_lds_plan, the arc kernel's size) does not fit 160 KB, when
+// MM_BIGV asks for it, or for the arc, sampling, cost, leaky, entropy, filter and window kernels when NI = 0: they have no
+// streamed-only instance with the vectors in LDS.
 // `global` never depends on max_items, nor does NI except Tropical's (8: the whole graph is register-resident): mm_batch_create
 // asks before the item forms are up, and ensure_item_forms raises max_items later -- only NW follows it.
 static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
@@ -453,15 +454,18 @@ static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
         if (e == ItemEntry::Leaky) return mm_leaky_lds_bytes(S1p, P1p);
         if (e == ItemEntry::Entropy) return mm_entropy_lds_bytes(S1p, P1p);
         if (e == ItemEntry::Filter) return mm_filter_lds_bytes(S1p, P1p);
+        if (e == ItemEntry::Window) return mm_window_lds_bytes(S1p, P1p);
         return e == ItemEntry::Cost ? mm_cost_lds_bytes(S1p, P1p) : size_t(lds_plan(S1p, P1p, e != ItemEntry::Export).total) * 4;
     };
     const bool derived = e == ItemEntry::Arcs || e == ItemEntry::Sample || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy ||
-                         e == ItemEntry::Filter;
+                         e == ItemEntry::Filter || e == ItemEntry::Window;
     ItemPlan pl{e, g.NW, g.NI, false, false, 0};
     pl.global = bytes(h->max_S1p) + (e == ItemEntry::Arcs ? MM_ARC_LDS_EXTRA : 0) > lds_max || h->dbg.bigv || (derived && g.NI == 0);
     pl.lds_bytes = bytes(pl.global ? 0 : h->max_S1p);
     // (8 items' arcs and their sums / the pair arithmetic / the leak term and its sums per wave: compiled for 8 waves per CU)
-    if (e == ItemEntry::Arcs || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy || e == ItemEntry::Filter) pl.NW = std::min(g.NW, 8);
+    if (e == ItemEntry::Arcs || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy || e == ItemEntry::Filter ||
+        e == ItemEntry::Window)
+        pl.NW = std::min(g.NW, 8);
     if (e == ItemEntry::Sample) pl.stage = !pl.global && !h->dbg.sample_nostage && size_t(h->max_S1p) * 8 <= lds_max;
     if (e == ItemEntry::Tropical) {
         // register-resident items when the whole graph fits 8 items per wave -- as many waves as there is work for (latency), at most
@@ -2602,6 +2606,12 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
         s = "mm_filter_kernel<" + std::to_string(pl.NI) + "," + where_of(pl.global) +
             "> (forward alone: filt and incr per frame from the finished vector, state_out and ttl; no frame kept); state vectors " +
             (pl.global ? "in global memory" : "in LDS");
+    } else if (entry == 10) {  // mm_windowposteriors_f32
+        if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_windowposteriors_f32 runs on log-semiring batches only");
+        const ItemPlan pl = item_plan(h, ItemEntry::Window);
+        const std::string inst = "<" + std::to_string(pl.NI) + "," + where_of(pl.global) + ">";
+        s = "mm_window_fwd_kernel" + inst + " (forward from the carried start vector: alpha~ stored, state_out and lcommit at the commit frame) + mm_window_bwd_kernel" +
+            inst + " (backward from an open or a closed end: gamma per pdf, ttl); state vectors " + (pl.global ? "in global memory" : "in LDS");
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -3008,7 +3018,7 @@ int mm_pdfposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
 
 }  // extern "C"
 // ---- the entries on the item form beside pdfposteriors: arc posteriors, path sampling, expected cost, leaky posteriors, path entropy,
-// filtering posteriors (log batches only)
+// filtering posteriors, window posteriors (log batches only)
 
 // What they start with: the semiring refusal, check_run, the entry's own argument checks (`args`), the item forms -- ahead
 // of the plan: a batch created without them has max_items = 0 until they are up, and the plan would size the workgroups for no
@@ -3026,7 +3036,7 @@ static int item_entry_begin(mm_batch_t h, const char *who, ItemEntry e, const fl
 }
 
 // Where they keep what they keep in h->ws for N frames: byte offsets, each aligned to 256 bytes.  The alpha~ store (at 0) and
-// the per-frame offsets as the item kernel keeps them; Arcs: the float64 sums of all backward slots, the state posteriors of
+// the per-frame offsets as the item kernel keeps them (all that Leaky and Window keep); Arcs: the float64 sums of all backward slots, the state posteriors of
 // frame 1; Cost: the r store and its offsets, and for FSMs beyond the LDS the state vectors of both kernels ([B][8 * max S1p]
 // floats); Entropy: as Cost, the Hf store in the place of the r store -- and no such store for a value-only call (`store` false).
 // total: no less than what mm_pdfposteriors_f32 needs for as many frames.  (mm_batch_reserve does not cover it.)  Filter keeps
@@ -3286,6 +3296,39 @@ int mm_filterposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t v
     fp.isb = isb;
     fp.ttl = ttl;
     return mm_launch_filter(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, p, fp, static_cast<hipStream_t>(stream));
+}
+
+// ---- fixed-lag smoothing posteriors: the forward-backward of a window with a carried start and an open end (mm_kernel_window.hip)
+int mm_windowposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, const float *state_in,
+                            const int32_t *closed, const int32_t *commit, float *state_out, float *lcommit, float *gamma, int64_t gsb,
+                            int64_t gsn, int64_t gsp, float *ttl, void *stream) {
+    // what the arguments alone show comes first (without a batch: the frames' own extent), then the batch's refusals
+    if (!gamma) return fail(MM_ERR_INVALID, "mm_windowposteriors_f32: gamma is NULL");
+    {
+        const int64_t B = h ? h->B : 1, P = h ? h->max_P1 - 1 : 1;
+        if (!strides_hold(gsb, B, gsn, N, gsp, P))
+            return fail(MM_ERR_DIM, "mm_windowposteriors_f32: g strides (" + std::to_string(gsb) + ", " + std::to_string(gsn) + ", " + std::to_string(gsp) +
+                                        ") cannot hold " + std::to_string(B) + " x " + std::to_string(N) + " x " + std::to_string(P) + " elements");
+    }
+    ItemPlan pl;
+    int rc = item_entry_begin(h, "mm_windowposteriors_f32", ItemEntry::Window, V, N, stream, []() { return int(MM_OK); }, &pl);
+    if (rc) return rc;
+    const ItemWs W = item_ws_layout(h, pl, N);
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    rc = item_ws_bind(h, pl, W, p, stream);
+    if (rc) return rc;
+    p.gamma = gamma;
+    p.gsb = gsb;
+    p.gsn = gsn;
+    p.gsp = gsp;
+    p.ttl = ttl;
+    WindowParams wp{};
+    wp.state_in = state_in;
+    wp.state_out = state_out;
+    wp.closed = closed;
+    wp.commit = commit;
+    wp.lcommit = lcommit;
+    return mm_launch_window(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, p, wp, static_cast<hipStream_t>(stream));
 }
 
 // ---- pdf posteriors of the leaky HMM (mm_kernel_leaky.hip)

@@ -282,4 +282,17 @@ struct FilterParams {
 int mm_launch_filter(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, const RunParams &p, const FilterParams &fp, hipStream_t stream);
 size_t mm_filter_lds_bytes(int S1p, int P1p);
 
+// ---- fixed-lag smoothing posteriors (mm_window_tu.hip: mm_window_fwd_kernel, mm_window_bwd_kernel on the item form)
+struct WindowParams {
+    const float *state_in;  // as FilterParams::state_in; NULL: the FSMs' own initial vectors
+    float *state_out;       // as state_in (may be the same buffer); NULL: not asked for
+    const int *closed;      // [B] != 0: the window ends on the final weights; NULL: every window ends open
+    const int *commit;      // [B] the frame state_out and lcommit belong to (clamped to [0, len]); NULL: len
+    float *lcommit;         // [B]; NULL: not asked for
+};
+// lds_bytes: window_lds_plan(...).total * 4 of the geometry (state vectors in LDS, or bigv: in RunParams::ws_big); gamma and ttl
+// (NULL: not asked for) go where RunParams says
+int mm_launch_window(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, const RunParams &p, const WindowParams &wp, hipStream_t stream);
+size_t mm_window_lds_bytes(int S1p, int P1p);
+
 }  // namespace mm

@@ -551,6 +551,67 @@ class BatchedFSM:
         res = (filt, incr, ttl) + ((so,) if so is not None else ())
         return tuple(t.cpu().numpy() if t is not None else None for t in res) if as_numpy else res
 
+    def windowposteriors(self, V, lens=None, state=None, closed=None, commit=None, out=None, want_state=False):
+        """Fixed-lag smoothing posteriors (mm_windowposteriors_f32): the forward-backward over a WINDOW of the audio that starts
+        from a carried vector and ends open or on the final weights -- ``(gamma[B, N, P], ttl[B], lcommit[B])``, plus
+        ``state_out[total_states]`` when ``want_state``.  ``state`` as for ``filterposteriors`` (None: the FSMs' own initial
+        vectors).  ``closed`` (int32 ``[B]``, None: all open): 0 -- the audio goes on behind the window, beta = 1 on every real
+        state at the last frame, ``gamma[b, n]`` = P(pdf_n | V_b at the window's frames) and ``ttl`` = ln P(window | start);
+        != 0 -- the audio ends with the window, the final weights close it (with ``state`` None: ``pdfposteriors``' gamma and
+        log Z).  ``commit`` (int32 ``[B]``, clamped to ``[0, lens[b]]``; None: ``lens``): the frame count c whose one-step
+        prediction ``state_out`` is -- ``filterposteriors``' state after c frames -- and ``lcommit`` = ln P(the first c frames |
+        start).  Re-windowing is exact: a second window over the frames from c on, with ``state`` = this ``state_out`` and the
+        same ``closed``, has this window's gamma on those frames, and its ``ttl`` is this ``ttl`` - ``lcommit``
+        (``streaming.FixedLagSmoother`` keeps that book).  ``want_state`` may also be the tensor that receives the state,
+        ``state`` itself included.  ``out`` as for ``pdfposteriors``.  Frames beyond the lengths are zeros; a window without
+        mass has gamma = 0 and ttl = -inf.  d ttl / d V = gamma.  Log batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        if out is not None:
+            # the kernels write through raw pointers and strides: a wrong buffer is memory corruption, not an exception
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != Vt.device:
+                raise TypeError("out must be a float32 tensor on V's device")
+            if out.dim() != 3 or tuple(out.shape) != (B, N, P):
+                raise _lib.DimensionMismatch(-2, f"out must be [B={B}, N={N}, P={P}], got {tuple(out.shape)}")
+        st = None
+        if state is not None:
+            st = torch.as_tensor(np.ascontiguousarray(state, dtype=np.float32)).cuda() if not isinstance(state, torch.Tensor) else state
+            if st.dtype != torch.float32 or st.device != Vt.device:
+                raise TypeError("state must be a float32 tensor on V's device")
+            if st.dim() != 1 or st.numel() != self.total_states or not st.is_contiguous():
+                raise _lib.DimensionMismatch(-2, f"state must be a contiguous [{self.total_states}] vector, got {tuple(st.shape)}")
+
+        def per_utt(x, name):
+            if x is None:
+                return None
+            t = x.to(device=Vt.device, dtype=torch.int32) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.int32)).to(Vt.device)
+            if t.dim() != 1 or t.numel() != B:
+                raise _lib.DimensionMismatch(-2, f"{name} must be a [{B}] vector, got {tuple(t.shape)}")
+            return t.contiguous()
+
+        cl, cm = per_utt(closed, "closed"), per_utt(commit, "commit")
+        gamma = out if out is not None else torch.empty((B, N, P), dtype=torch.float32, device=Vt.device)
+        ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        lcommit = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        so = None
+        if isinstance(want_state, torch.Tensor):
+            so = want_state
+            if so.dtype != torch.float32 or so.device != Vt.device:
+                raise TypeError("the state buffer must be a float32 tensor on V's device")
+            if so.dim() != 1 or so.numel() != self.total_states or not so.is_contiguous():
+                raise _lib.DimensionMismatch(-2, f"the state buffer must be a contiguous [{self.total_states}] vector, got {tuple(so.shape)}")
+        elif want_state:
+            so = torch.empty(self.total_states, dtype=torch.float32, device=Vt.device)
+        check(lib.mm_windowposteriors_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
+                                          lt.data_ptr() if lt is not None else None, N,
+                                          st.data_ptr() if st is not None else None,
+                                          cl.data_ptr() if cl is not None else None, cm.data_ptr() if cm is not None else None,
+                                          so.data_ptr() if so is not None else None, lcommit.data_ptr(),
+                                          gamma.data_ptr(), gamma.stride(0), gamma.stride(1), gamma.stride(2), ttl.data_ptr(),
+                                          self._stream(torch)))
+        res = (gamma, ttl, lcommit) + ((so,) if so is not None else ())
+        return tuple(t.cpu().numpy() for t in res) if as_numpy else res
+
     def maxstateposteriors(self, V, lens=None):
         """Max-marginals of the tropical semiring, (sum S1) x (N+1), computed on the device."""
         return self._export(lib.mm_maxstateposteriors_f32, V, lens)
@@ -634,11 +695,11 @@ class BatchedFSM:
     def kernels(self, semiring: str = "log") -> str:
         """The kernels the engine launches for this batch (informational): "log" = pdfposteriors, "tropical" = bestpath, "export" =
         alpharecursion / betarecursion, "arcs" = arcposteriors, "sample" = samplepaths, "cost" = expectedcost, "leaky" =
-        leakyposteriors, "entropy" = pathentropy, "filter" = filterposteriors."""
+        leakyposteriors, "entropy" = pathentropy, "filter" = filterposteriors, "window" = windowposteriors."""
         import ctypes
 
         buf = ctypes.create_string_buffer(1024)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9}[semiring], buf, 1024))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10}[semiring], buf, 1024))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -980,6 +1041,30 @@ def filterposteriors(fsm, Vhats, Chats=None, seqlengths=None):
     V, lens = _need_expanded(Vh, bf.semiring)
     f, incr, ttl = bf.filterposteriors(V, lens)
     return np.ascontiguousarray(f.transpose(0, 2, 1)), incr, ttl
+
+
+def windowposteriors(fsm, Vhats, Chats=None, seqlengths=None, closed=None):
+    """Window posteriors -- see ``BatchedFSM.windowposteriors`` -- in ``pdfposteriors``' call shape, from the FSMs' own initial
+    vectors: ``fsm`` the rawunion of the batch with its state maps, or a BatchedFSM / CompiledFSM (log semiring, Float32);
+    V_hats what ``expand`` makes; ``closed`` None: every window ends open.  Returns (gamma[B, P, N] probabilities, ttl[B]):
+    NumPy arrays for host inputs, device tensors for float32 V_hats on the HIP device given with their ``seqlengths``."""
+    if not hasattr(Vhats, "dim"):  # (a generator is read once)
+        Vhats = list(Vhats)
+    bf = _as_batch(fsm, Chats)
+    Vd = _device_vhats(Vhats)
+    if Vd is not None and seqlengths is not None:
+        torch = _torch()
+        B, P1, N1 = Vd.shape
+        if B != bf.B:
+            raise _lib.DimensionMismatch(-2, f"{B} matrices V_hat for a batch of {bf.B} FSMs")
+        lens = torch.as_tensor(seqlengths, dtype=torch.int32, device=Vd.device)
+        g, ttl, _ = bf.windowposteriors(Vd[:, : P1 - 1, : N1 - 1].transpose(1, 2).contiguous(), lens, closed=closed)
+        return g.transpose(1, 2), ttl
+    # (device V_hats without their lengths: to the host, as pdfposteriors moves them, where the phony row gives the lengths)
+    Vh = [np.asarray(v.cpu() if hasattr(v, "cpu") else v) for v in Vhats]
+    V, lens = _need_expanded(Vh, bf.semiring)
+    g, ttl, _ = bf.windowposteriors(V, lens, closed=closed)
+    return np.ascontiguousarray(g.transpose(0, 2, 1)), ttl
 
 
 def arcposteriors(fsm, Vhats, Chats=None, want_init=False):

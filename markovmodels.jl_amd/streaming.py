@@ -1,4 +1,4 @@
-"""Streaming inference on top of the engine: the forward filter of a log batch run over audio in chunks.
+"""Streaming inference on top of the engine: the forward filter and the fixed-lag smoother of a log batch run over audio in chunks.
 
 ``ForwardFilter`` keeps, per utterance of a batch, the carried state of ``BatchedFSM.filterposteriors`` (mm_filterposteriors_f32:
 the one-step prediction behind the last frame seen, normalised by the mass alive there) and the running prefix log-likelihood.
@@ -6,6 +6,9 @@ the one-step prediction behind the last frame seen, normalised by the mass alive
 ln P(V_n | V before n) of its frames: online confidence, keyword / filler spotting, HMM-smoothed activity detection, endpointing.
 Chunking is exact -- the chunks' results are those of one call on the whole audio -- and costs no graph compilation: the state is
 an argument of the call.  Everything is a launch chain on the caller's stream; nothing synchronises the host.
+
+``FixedLagSmoother`` is its companion on ``BatchedFSM.windowposteriors`` (mm_windowposteriors_f32): every frame waits for ``lag``
+frames of its future and is emitted once, with the smoothing posterior given everything pushed by then.
 """
 from __future__ import annotations
 
@@ -59,4 +62,104 @@ class ForwardFilter:
         m = torch.as_tensor(mask).to(device=self.state.device, dtype=torch.bool)
         self.state.copy_(torch.where(m[self._utt], self._reset, self.state))
         self.loglik.masked_fill_(m, 0.0)
+        return self
+
+
+class FixedLagSmoother:
+    """The fixed-lag smoother of ``batch`` (a log-semiring ``BatchedFSM``), one stream of audio per utterance: the companion of
+    ``ForwardFilter`` that lets every frame see ``lag`` frames of its future, P(pdf_n | V up to n + lag), on
+    ``BatchedFSM.windowposteriors`` (mm_windowposteriors_f32).
+
+    Every frame is emitted exactly once, by the ``push`` that brings the ``lag``-th frame behind it or by ``finish``.  Its
+    posterior is conditioned on EVERYTHING pushed up to the push that emitted it -- at least ``lag`` frames ahead, more for the
+    older frames of a long chunk -- or on the whole audio up to its end for the frames ``finish`` emits; it is exactly the
+    open-window (``finish``: the closed) smoothing posterior given all frames of the utterance so far, not an approximation by a
+    truncated window: the frames before the window are in the carried state.  A push costs one forward-backward over
+    ``lag + chunk`` frames (the filter's push: one forward pass over ``chunk`` frames); the utterances advance each by its own
+    ``lens``, not in lock step.  Everything is a launch chain on the caller's stream; nothing synchronises the host except what
+    ``count`` costs the caller to read.
+
+    ``state``    float32 ``[total_states]`` device tensor: ``filterposteriors``' carried state behind the last emitted frame
+    ``loglik``   float64 ``[B]`` device tensor: ln P(the frames emitted so far)
+    ``pending``  float32 ``[B, lag, P]`` device tensor, ``npending`` int32 ``[B]``: the frames pushed and not yet emitted"""
+
+    def __init__(self, batch, lag):
+        import torch
+
+        if int(lag) < 1:
+            raise ValueError("lag must be at least one frame (lag 0 is the forward filter: streaming.ForwardFilter)")
+        self.batch, self.lag = batch, int(lag)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        B = batch.B
+        self.pending = torch.zeros((B, self.lag, batch.P), dtype=torch.float32, device=dev)
+        self.npending = torch.zeros(B, dtype=torch.int32, device=dev)
+        # the reset vector, once: a window with lens = 0 passes the start vector through (NULL in: ln alpha_hat)
+        self._reset = batch.windowposteriors(self.pending[:, :1], self.npending, want_state=True)[3]
+        sizes = torch.as_tensor([int(c.S1) for c in batch.cfsms], device=dev)
+        self._utt = torch.repeat_interleave(torch.arange(B, device=dev), sizes)  # state -> utterance
+        self.state = self._reset.clone()
+        self.loglik = torch.zeros(B, dtype=torch.float64, device=dev)
+
+    def push(self, V_chunk, lens=None):
+        """The next chunk ``V_chunk[B, n, P]`` (``lens[b]`` of its frames belong to utterance b; 0: the utterance stands still).
+        Returns ``(gamma[B, n, P], count[B])``: the first ``count[b]`` rows of ``gamma[b]`` are the smoothed posteriors of b's
+        oldest pending frames, in order (``count[b]`` = pending + ``lens[b]`` - ``lag``, at least 0 and at most n -- the width
+        every count fits without asking the device); the rows behind them are zeros.  NumPy for a NumPy chunk, device tensors
+        for a device chunk."""
+        import torch
+
+        as_numpy = not isinstance(V_chunk, torch.Tensor)
+        dev = self.state.device
+        Vc = torch.as_tensor(V_chunk, dtype=torch.float32).to(dev) if as_numpy else V_chunk
+        B, n, P = Vc.shape
+        L = torch.full((B,), n, dtype=torch.int32, device=dev) if lens is None else torch.as_tensor(lens).to(device=dev, dtype=torch.int32)
+        L = L.clamp(0, n)
+        W = self.lag + n
+        t = torch.arange(W, device=dev)[None, :]  # [1, W]
+        npd = self.npending[:, None].long()
+        # utterance b's window: its pending frames, then its frames of the chunk
+        both = torch.cat([self.pending, Vc], dim=1)
+        src = torch.where(t < npd, t, (self.lag + t - npd).clamp(max=W - 1))
+        win = torch.gather(both, 1, src[:, :, None].expand(B, W, P)).contiguous()
+        wlen = self.npending + L
+        commit = (wlen - self.lag).clamp(min=0)
+        gamma, _, lcommit, _ = self.batch.windowposteriors(win, wlen, state=self.state, commit=commit, want_state=self.state)
+        self.loglik += lcommit.double()
+        # the frames behind the commit frame stay pending
+        keep = (commit[:, None].long() + t[:, : self.lag]).clamp(max=W - 1)
+        self.pending = torch.gather(win, 1, keep[:, :, None].expand(B, self.lag, P)).contiguous()
+        self.npending = wlen - commit
+        out = gamma[:, :n] * (t[:, :n] < commit[:, None]).unsqueeze(-1)
+        return (out.cpu().numpy(), commit.cpu().numpy()) if as_numpy else (out, commit)
+
+    def finish(self, mask=None, as_numpy=False):
+        """The audio of the utterances of ``mask`` (bool ``[B]``; None: all) ends here: one closed window over their pending
+        frames.  Returns ``(gamma[B, lag, P], count[B], logz[B])``: the first ``count[b]`` rows of ``gamma[b]`` are the posteriors
+        of b's remaining frames -- given the whole audio --, ``logz`` (float64) = ``loglik`` + the closed window's ``ttl``, the
+        log Z ``pdfposteriors`` gives the whole audio.  The other utterances take no part (count 0, logz -inf) and go on
+        afterwards; the masked ones are reset."""
+        import torch
+
+        dev = self.state.device
+        m = torch.ones(self.batch.B, dtype=torch.bool, device=dev) if mask is None else torch.as_tensor(mask).to(device=dev, dtype=torch.bool)
+        count = torch.where(m, self.npending, torch.zeros_like(self.npending))
+        gamma, ttl, _ = self.batch.windowposteriors(self.pending, count, state=self.state, closed=m.to(torch.int32))
+        logz = self.loglik + ttl.double()
+        self.reset(m)
+        return (gamma.cpu().numpy(), count.cpu().numpy(), logz.cpu().numpy()) if as_numpy else (gamma, count, logz)
+
+    def reset(self, mask=None):
+        """Put the utterances of ``mask`` (bool ``[B]``; None: all) back on their FSMs' initial vectors with nothing pending,
+        ``loglik`` on 0."""
+        import torch
+
+        if mask is None:
+            self.state.copy_(self._reset)
+            self.loglik.zero_()
+            self.npending.zero_()
+            return self
+        m = torch.as_tensor(mask).to(device=self.state.device, dtype=torch.bool)
+        self.state.copy_(torch.where(m[self._utt], self._reset, self.state))
+        self.loglik.masked_fill_(m, 0.0)
+        self.npending.masked_fill_(m, 0)
         return self
