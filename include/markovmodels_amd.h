@@ -119,6 +119,7 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * 8 = mm_pathentropy_f32 (log batches only): mm_entropy_fwd_kernel<NI,lds|global> + mm_entropy_bwd_kernel<...>.
  * 9 = mm_filterposteriors_f32 (log batches only): mm_filter_kernel<NI,lds|global>.
  * 10 = mm_windowposteriors_f32 (log batches only): mm_window_fwd_kernel<NI,lds|global> + mm_window_bwd_kernel<...>.
+ * 11 = mm_viterbiwindow_f32 (tropical batches only): mm_vitwindow_fwd_kernel<NI,lds|global> + mm_vitwindow_trace_kernel<lds|global>.
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -489,6 +490,65 @@ int mm_maxstateposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride
 int mm_viterbi_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens,
                    int64_t N, int32_t *path, int64_t path_stride_b, float *score, int32_t *bp,
                    int64_t bp_stride_n, void *stream);
+
+/* Windowed best paths: the Viterbi recursion of a tropical batch over a WINDOW of the audio, which starts from a carried vector
+ * instead of the FSM's initial vector and ends open (on the best real state: the audio goes on) or in the phony final state -- and
+ * the CONVERGENCE POINT, the last frame through which every surviving path passes: the path up to it can never change, whatever
+ * audio follows.  The tropical counterpart of mm_windowposteriors_f32 for online alignment, keyword spotting, endpointing on the
+ * best path and live captioning, where mm_viterbi_f32 would re-run the whole prefix at every chunk.  For utterance b the extended
+ * system, lhs = C_hat * expand(V_b) and len = len_b are exactly those of mm_viterbi_f32; natural log; frames counted from 1 here
+ * and from 0 in the arrays, f the phony final state:
+ *
+ *   start(j)   = alpha_hat(j) (state_in == NULL)  or  state_in_b(j)   for real j;  start(f) = -inf
+ *   d_1(j)     = start(j) + lhs_1(j)
+ *   d_n(j)     = (max_i d_{n-1}(i) + T_hat(i,j)) + lhs_n(j),  bp_n(j) = the LOWEST i among the maximisers (-1 if the max is -inf)
+ *   e(i)       = d_len(i)                     closed_b == 0 (the audio goes on)
+ *   e(i)       = d_len(i) + T_hat(i,f)        closed_b != 0 (the audio ends at frame len)
+ *   score      = max_i e(i);  s_len = the lowest maximiser;  s_n = bp_{n+1}(s_{n+1});   path(n) = s_n, 0-based, -1 for n >= len
+ *   A_len      = { real i : e(i) > -inf };   A_n = { bp_{n+1}(j) : j in A_{n+1} }      the states surviving paths pass at frame n
+ *   converged  = the largest n in 1..len with |A_n| = 1;  0 if there is none
+ *   c          = clamp(commit_b, 0, len)   (commit == NULL: len when commit_converged == 0, else 0);
+ *                commit_converged != 0:  c = max(c, converged)
+ *   m_c        = max_{j real} d_c(j)
+ *   state_out(j) = (max_i d_c(i) + T_hat(i,j)) - m_c      for ALL j, f included
+ *   mcommit    = m_c;   ncommit = c
+ *
+ *   V, lens, N   as mm_viterbi_f32
+ *   state_in, state_out   layout and aliasing rule of mm_filterposteriors_f32: they may be one buffer.  state_out NULL: not written
+ *   closed       device int32[B]; NULL: every utterance is open
+ *   commit       device int32[B]; NULL: see c above
+ *   mcommit      device float[B], ncommit, converged device int32[B], out (each NULL: not written)
+ *   path, score  as mm_viterbi_f32's.  NULL: MM_ERR_INVALID.  path_stride_b < N: MM_ERR_DIM
+ * Argument errors that need no device are reported before the NULL-batch check.  MM_TROPICAL batches only: Log and ProbSemiring
+ * batches return MM_ERR_UNSUPPORTED.
+ * Arithmetic: the float32 operations of mm_viterbi_f32's item kernel in the same order -- one add per arc, a max, one add of the
+ * emission -- and one subtraction for state_out.  No multiply, nothing that can contract.
+ * Conventions: len = 0 gives path all -1, score = -inf, converged = 0, ncommit = 0, mcommit = 0 and state_out = a copy of the start
+ * vector (state_in == NULL: alpha_hat).  c = 0 with len > 0 gives the same copy and mcommit = 0.  A window without a path (score =
+ * -inf) has path all -1 and converged = 0; its state_out and mcommit are still the prefix's values when m_c > -inf, else -inf
+ * everywhere.  Nothing is NaN.
+ * Consequences: (a) closed with state_in == NULL: path and score are those of mm_viterbi_f32, bit for bit.  (b) FINALITY: an open
+ * window of len frames and any longer window from the same start, open or closed, that has a path: the two paths agree on frames
+ * 1..converged, bit for bit (the forward pass is causal and the back-pointers of the first len frames are identical).  (c)
+ * RE-WINDOWING: a window over frames 1..M with commit c and a second window over frames c+1..M with state_in = the first window's
+ * state_out and the same closed: in exact arithmetic the second has the first's path on frames c+1..M and its score = the first's
+ * score - mcommit; in float32 this holds bit for bit whenever every sum is exactly representable (weights and emissions that are
+ * multiples of 1/16 of moderate size, say).  When c <= converged, the committed frames of successive windows concatenate to the
+ * best path of the whole audio.  (d) a constant added to every emission of a frame changes no path and no converged, and moves
+ * score by that constant.  (e) no atomics whose order matters: a repeated call returns the same bits.
+ * Runs on the item form of every FSM of every tropical batch, one workgroup per utterance: mm_vitwindow_fwd_kernel<NI,lds|global>
+ * (mm_viterbi_f32's item kernel from the carried start; per frame it stores the back-pointer row, the row of PRE-EMISSION maxima
+ * -- state_out of whatever commit frame the second kernel arrives at is that row minus m_c, so no arc pass is repeated -- and the
+ * frame's maximum over the real states) and mm_vitwindow_trace_kernel (the best path by one lane; the surviving set as byte flags,
+ * propagated through the back-pointer rows until one state is left: O((len - converged) * S) work).  Workspace, grown by the call
+ * and covered by mm_batch_workspace_bytes: int32 and float32 rows (sum_b S1p_b) x (N + 1) each, float32 B x (N + 2), int32 B.
+ * Stream contract of mm_arcposteriors_f32: launches on `stream` only, no host synchronisation; it can be captured in a hipGraph
+ * once a first call has put the batch's item forms on the device and sized the workspace (a capture before that returns
+ * MM_ERR_INVALID). */
+int mm_viterbiwindow_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                         const float *state_in, const int32_t *closed, const int32_t *commit, int commit_converged, float *state_out,
+                         float *mcommit, int32_t *ncommit, int32_t *path, int64_t path_stride_b, float *score, int32_t *converged,
+                         void *stream);
 
 /* totalsum(alpha, T, omega, n) / totalcumsum(alpha, T, omega, n) (src/algorithms.jl:8-29;
  * totalweightsum(fsm, n) = totalcumsum, :36), one value per FSM of the batch, in the batch's semiring

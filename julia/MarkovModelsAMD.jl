@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, viterbiwindow, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -600,6 +600,39 @@ function bestpath(b::ROCBatch{K}, V::ROCArray{Float32,3}, lens = nothing) where 
         b.handle, pointer(V), P * N, P, lp, N, pointer(path), N, pointer(score), C_NULL, 0,
         AMDGPU.stream().stream))
     Array(path) .+ Int32(1), Array(score)
+end
+
+"""
+    viterbiwindow(b::ROCBatch{<:TropicalSemiring}, V, lens = nothing; state = nothing, closed = nothing, commit = nothing, commit_converged = false)
+        -> (paths, scores, converged, ncommit, mcommit, state_out)
+
+Windowed best paths (mm_viterbiwindow_f32 in the header): the Viterbi recursion over a window of the audio that starts from `state`
+(an earlier call's `state_out`; `nothing`: the FSMs' own initial vectors) and ends open -- on the best real state, the audio goes
+on -- or, for the utterances with `closed[b] != 0`, in the final state.  `converged[b]` is the last frame every surviving path
+passes: the path up to it is final.  `state_out` and `mcommit` belong to frame `commit[b]` (with `commit_converged`: no earlier than
+`converged[b]`), `ncommit` says which; a second window over the frames behind it, from `state_out`, continues the path.  States are
+returned 1-based (0: no state), `closed` and `commit` are `ROCVector{Int32}` of length B.
+"""
+function viterbiwindow(b::ROCBatch{K}, V::ROCArray{Float32,3}, lens = nothing; state = nothing, closed = nothing, commit = nothing,
+                       commit_converged::Bool = false) where K <: TropicalSemiring
+    P, N, B = size(V)
+    S = Int(ccall((:mm_batch_total_states, LIB), Int64, (Ptr{Cvoid},), b.handle))
+    state === nothing || length(state) == S || throw(DimensionMismatch("state has $(length(state)) entries, the batch $S states"))
+    path = ROCArray{Int32}(undef, N, B)
+    score = ROCArray{Float32}(undef, B)
+    converged = ROCArray{Int32}(undef, B)
+    ncommit = ROCArray{Int32}(undef, B)
+    mcommit = ROCArray{Float32}(undef, B)
+    state_out = ROCArray{Float32}(undef, S)
+    ip(x) = x === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(x))
+    check(ccall((:mm_viterbiwindow_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Float32}, Ptr{Int32}, Ptr{Int32}, Cint,
+         Ptr{Float32}, Ptr{Float32}, Ptr{Int32}, Ptr{Int32}, Int64, Ptr{Float32}, Ptr{Int32}, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, ip(lens), N,
+        state === nothing ? Ptr{Float32}(C_NULL) : pointer(state), ip(closed), ip(commit), commit_converged ? 1 : 0,
+        pointer(state_out), pointer(mcommit), pointer(ncommit), pointer(path), N, pointer(score), pointer(converged),
+        AMDGPU.stream().stream))
+    Array(path) .+ Int32(1), Array(score), Array(converged), Array(ncommit), Array(mcommit), state_out
 end
 
 """

@@ -2,7 +2,7 @@
 
 Host-side mirror of the reference's hot-path interface (src/MarkovModels.jl:14-45:
 FSM, nstates, rawunion, CompiledFSM, batch, compile, expand, alpha-recursion,
-beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, arcposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
+beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, windowbestpath, arcposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
 The directory name contains a dot, so load it with
 ``__graft_entry__.load_package()`` (importlib) rather than a plain import.
 """
@@ -31,6 +31,7 @@ from .inference import (  # noqa: F401
     totalcumsum,
     totalsum,
     totalweightsum,
+    windowbestpath,
     windowposteriors,
     αrecursion,
     βrecursion,
@@ -42,4 +43,4 @@ from .mbr import expected_cost, smbr_loss  # noqa: F401
 from . import entropy  # noqa: F401
 from .entropy import conditional_entropy_loss, path_entropy  # noqa: F401
 from . import streaming  # noqa: F401
-from .streaming import FixedLagSmoother, ForwardFilter  # noqa: F401
+from .streaming import FixedLagSmoother, ForwardFilter, OnlineViterbi  # noqa: F401

@@ -62,6 +62,7 @@ SYMBOLS = [
     "mm_betarecursion_f32",
     "mm_maxstateposteriors_f32",
     "mm_viterbi_f32",
+    "mm_viterbiwindow_f32",
     "mm_totalsum_f32",
     "mm_set_rccl",
     "mm_allreduce_logz",
@@ -181,6 +182,8 @@ def _load():
         fn.argtypes = [vp, fp, i64, i64, vp, i64, fp, i64, vp]
     lib.mm_viterbi_f32.restype = C.c_int
     lib.mm_viterbi_f32.argtypes = [vp, fp, i64, i64, vp, i64, vp, i64, fp, vp, i64, vp]
+    lib.mm_viterbiwindow_f32.restype = C.c_int
+    lib.mm_viterbiwindow_f32.argtypes = [vp, fp, i64, i64, vp, i64, fp, vp, vp, C.c_int, fp, fp, vp, vp, i64, fp, vp, vp]
     lib.mm_totalsum_f32.restype = C.c_int
     lib.mm_totalsum_f32.argtypes = [vp, i64, C.c_int, fp, vp]
     lib.mm_set_rccl.restype = C.c_int

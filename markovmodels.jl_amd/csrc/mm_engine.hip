@@ -431,7 +431,7 @@ static Geometry pick_geometry(mm_batch_t h) {
 }
 
 // ---- one plan per entry that runs on the item form: its launch geometry and where its state vectors live
-enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter, Window };
+enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter, Window, VitWindow };
 struct ItemPlan {
     ItemEntry e;
     int NW, NI;        // waves per workgroup, register-resident items per wave of the instance (8 or 0)
@@ -443,7 +443,8 @@ struct ItemPlan {
 // all but the export modes, + the arc kernel's extra; Cost: cost_lds_plan; Leaky: leaky_lds_plan; Entropy: entropy_lds_plan; Filter:
 // filter_lds_plan, no larger than the export modes'; Window: window_lds_plan, the arc kernel's size) does not fit 160 KB, when
 // MM_BIGV asks for it, or for the arc, sampling, cost, leaky, entropy, filter and window kernels when NI = 0: they have no
-// streamed-only instance with the vectors in LDS.
+// streamed-only instance with the vectors in LDS.  VitWindow (tropical batches): the tropical kernel's geometry, its LDS plan + the
+// arc kernel's extra.
 // `global` never depends on max_items, nor does NI except Tropical's (8: the whole graph is register-resident): mm_batch_create
 // asks before the item forms are up, and ensure_item_forms raises max_items later -- only NW follows it.
 static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
@@ -455,6 +456,7 @@ static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
         if (e == ItemEntry::Entropy) return mm_entropy_lds_bytes(S1p, P1p);
         if (e == ItemEntry::Filter) return mm_filter_lds_bytes(S1p, P1p);
         if (e == ItemEntry::Window) return mm_window_lds_bytes(S1p, P1p);
+        if (e == ItemEntry::VitWindow) return mm_vitwindow_lds_bytes(S1p, P1p);
         return e == ItemEntry::Cost ? mm_cost_lds_bytes(S1p, P1p) : size_t(lds_plan(S1p, P1p, e != ItemEntry::Export).total) * 4;
     };
     const bool derived = e == ItemEntry::Arcs || e == ItemEntry::Sample || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy ||
@@ -467,7 +469,7 @@ static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
         e == ItemEntry::Window)
         pl.NW = std::min(g.NW, 8);
     if (e == ItemEntry::Sample) pl.stage = !pl.global && !h->dbg.sample_nostage && size_t(h->max_S1p) * 8 <= lds_max;
-    if (e == ItemEntry::Tropical) {
+    if (e == ItemEntry::Tropical || e == ItemEntry::VitWindow) {
         // register-resident items when the whole graph fits 8 items per wave -- as many waves as there is work for (latency), at most
         // 8 items each --, else streamed
         pl.NI = g.NI == 8 && h->max_items <= 8 * MM_MAX_WAVES ? 8 : 0;
@@ -2612,6 +2614,14 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
         const std::string inst = "<" + std::to_string(pl.NI) + "," + where_of(pl.global) + ">";
         s = "mm_window_fwd_kernel" + inst + " (forward from the carried start vector: alpha~ stored, state_out and lcommit at the commit frame) + mm_window_bwd_kernel" +
             inst + " (backward from an open or a closed end: gamma per pdf, ttl); state vectors " + (pl.global ? "in global memory" : "in LDS");
+    } else if (entry == 11) {  // mm_viterbiwindow_f32
+        if (h->semiring != MM_TROPICAL) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_viterbiwindow_f32 runs on tropical batches only");
+        const ItemPlan pl = item_plan(h, ItemEntry::VitWindow);
+        s = "mm_vitwindow_fwd_kernel<" + std::to_string(pl.NI) + "," + where_of(pl.global) +
+            "> (tropical forward from the carried start vector: back-pointer rows, pre-emission maxima and the frames' maxima stored) + "
+            "mm_vitwindow_trace_kernel<" + where_of(mm_vitwindow_flags_global(h->max_S1p)) +
+            "> (best path, surviving sets back to the convergence point, state_out and mcommit at the commit frame); state vectors " +
+            (pl.global ? "in global memory" : "in LDS");
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -2673,10 +2683,23 @@ static WsLayout ws_layout(mm_batch_t h, int64_t N) {
     return L;
 }
 
+// Where mm_viterbiwindow_f32 keeps what it keeps in h->ws for N frames (tropical batches): the int32 back-pointer rows, the float32
+// rows of pre-emission maxima (both (sum_b S1p_b) x (N + 1)), the frames' maxima [B][N + 2] floats and the end states [B] ints
+struct VitWindowWs { size_t best = 0, m = 0, end = 0, total = 0; };
+static VitWindowWs vitwindow_ws_layout(mm_batch_t h, int64_t N) {
+    VitWindowWs W;
+    W.best = align_up(size_t(h->total_s1p) * size_t(N + 1) * 4, 256);
+    W.m = 2 * W.best;
+    W.end = W.m + align_up(size_t(h->B) * size_t(N + 2) * 4, 256);
+    W.total = W.end + align_up(size_t(h->B) * 4, 256);
+    return W;
+}
+
 size_t mm_batch_workspace_bytes(mm_batch_t h, int64_t N) {
     if (!h || N < 0) return 0;
     if (h->log_twin) return mm_batch_workspace_bytes(h->log_twin, N) + align_up(size_t(h->B) * size_t(N) * size_t(h->max_P1 - 1) * 4, 256);
-    return ws_layout(h, N).total;
+    const size_t total = ws_layout(h, N).total;
+    return h->semiring == MM_TROPICAL ? std::max(total, vitwindow_ws_layout(h, N).total) : total;
 }
 
 
@@ -3714,6 +3737,50 @@ int mm_viterbi_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const
                        static_cast<hipStream_t>(stream), p);
     HIP_TRY(hipGetLastError());
     return MM_OK;
+}
+
+// ---- windowed best paths: the Viterbi recursion of a window with a carried start and an open end (mm_kernel_vitwindow.hip)
+int mm_viterbiwindow_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, const float *state_in,
+                         const int32_t *closed, const int32_t *commit, int commit_converged, float *state_out, float *mcommit,
+                         int32_t *ncommit, int32_t *path, int64_t path_stride_b, float *score, int32_t *converged, void *stream) {
+    // what the arguments alone show comes first, then the batch's refusals
+    if (!path || !score) return fail(MM_ERR_INVALID, "mm_viterbiwindow_f32: path/score is NULL");
+    if (path_stride_b < N) return fail(MM_ERR_DIM, "mm_viterbiwindow_f32: path_stride_b < N");
+    if (h && h->semiring != MM_TROPICAL)
+        return fail(MM_ERR_UNSUPPORTED, std::string("mm_viterbiwindow_f32: tropical batches only (this batch is ") +
+                                            (h->semiring == MM_LOG ? "log-semiring" : "ProbSemiring") + ")");
+    int rc = check_run(h, "mm_viterbiwindow_f32", V, N, MM_TROPICAL);
+    if (!rc) rc = ensure_item_forms(h, stream);
+    if (rc) return rc;
+    const ItemPlan pl = item_plan(h, ItemEntry::VitWindow);
+    rc = item_plan_check(h, pl);
+    if (!rc) rc = ensure_ws(h, mm_batch_workspace_bytes(h, N), stream);
+    if (rc) return rc;
+    const VitWindowWs W = vitwindow_ws_layout(h, N);
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    bind_big(h, pl, p);
+    if (h->ws_big) {  // (the trace kernel's flags of FSMs beyond its LDS)
+        p.ws_big = h->ws_big;
+        p.big_stride = 4ll * h->max_S1p;
+    }
+    p.path = path;
+    p.path_stride_b = path_stride_b;
+    p.score = score;
+    VitWindowParams wp{};
+    wp.state_in = state_in;
+    wp.state_out = state_out;
+    wp.closed = closed;
+    wp.commit = commit;
+    wp.commit_converged = commit_converged;
+    wp.mcommit = mcommit;
+    wp.ncommit = ncommit;
+    wp.converged = converged;
+    char *ws = static_cast<char *>(h->ws);
+    wp.ws_bp = reinterpret_cast<int *>(ws);
+    wp.ws_best = reinterpret_cast<float *>(ws + W.best);
+    wp.ws_m = reinterpret_cast<float *>(ws + W.m);
+    wp.ws_end = reinterpret_cast<int *>(ws + W.end);
+    return mm_launch_vitwindow(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, h->max_S1p, p, wp, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

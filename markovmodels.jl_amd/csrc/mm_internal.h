@@ -295,4 +295,27 @@ struct WindowParams {
 int mm_launch_window(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, const RunParams &p, const WindowParams &wp, hipStream_t stream);
 size_t mm_window_lds_bytes(int S1p, int P1p);
 
+// ---- windowed best paths (mm_vitwindow_tu.hip: mm_vitwindow_fwd_kernel, mm_vitwindow_trace_kernel on the item form; tropical batches)
+struct VitWindowParams {
+    const float *state_in;  // layout of FilterParams::state_in, natural log; NULL: the FSMs' own initial vectors
+    float *state_out;       // as state_in (may be the same buffer); NULL: not asked for
+    const int *closed;      // [B] != 0: the window ends in the phony final state; NULL: every window ends open
+    const int *commit;      // [B] the frame state_out and mcommit belong to (clamped to [0, len]); NULL: len, or 0 with commit_converged
+    int commit_converged;   // != 0: the commit frame is no earlier than the convergence point
+    float *mcommit;         // [B]; NULL: not asked for
+    int *ncommit;           // [B]; NULL: not asked for
+    int *converged;         // [B]; NULL: not asked for
+    // workspace, rows laid out like RunParams::ws_alpha (per utterance [N + 1][S1p]):
+    int *ws_bp;             // row 0: the flags of the states a surviving path ends in; row r >= 1: the back-pointers of frame r + 1
+    float *ws_best;         // row r >= 1: the pre-emission maxima of step r + 1 (state_out of commit frame r before m_r is taken off)
+    float *ws_m;            // [B][N + 2]: [n] = the maximum of frame n over the real states, n = 1..len
+    int *ws_end;            // [B] the state the best path ends in at frame len (-1: no path)
+};
+// lds_bytes: mm_vitwindow_lds_bytes of the geometry (state vectors in LDS, or bigv: in RunParams::ws_big); path and score go where
+// RunParams says
+int mm_launch_vitwindow(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, int max_S1p, const RunParams &p, const VitWindowParams &wp,
+                        hipStream_t stream);
+size_t mm_vitwindow_lds_bytes(int S1p, int P1p);
+bool mm_vitwindow_flags_global(int S1p);  // the trace kernel's flags do not fit the LDS: they live in RunParams::ws_big
+
 }  // namespace mm

@@ -695,11 +695,12 @@ class BatchedFSM:
     def kernels(self, semiring: str = "log") -> str:
         """The kernels the engine launches for this batch (informational): "log" = pdfposteriors, "tropical" = bestpath, "export" =
         alpharecursion / betarecursion, "arcs" = arcposteriors, "sample" = samplepaths, "cost" = expectedcost, "leaky" =
-        leakyposteriors, "entropy" = pathentropy, "filter" = filterposteriors, "window" = windowposteriors."""
+        leakyposteriors, "entropy" = pathentropy, "filter" = filterposteriors, "window" = windowposteriors,
+        "vitwindow" = viterbiwindow (tropical batches)."""
         import ctypes
 
         buf = ctypes.create_string_buffer(1024)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10}[semiring], buf, 1024))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11}[semiring], buf, 1024))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -725,6 +726,64 @@ class BatchedFSM:
         if as_numpy:
             res = tuple(r.cpu().numpy() for r in res)
         return res
+
+    def viterbiwindow(self, V, lens=None, state=None, closed=None, commit=None, commit_converged=False, want_state=False):
+        """Windowed best paths (mm_viterbiwindow_f32): the Viterbi recursion over a WINDOW of the audio that starts from a carried
+        vector and ends open or in the final state -- ``(path[B, N], score[B], converged[B], ncommit[B], mcommit[B], state_out)``;
+        ``state_out[total_states]`` is None without ``want_state``.  ``state`` is an earlier call's ``state_out`` (float32
+        ``[total_states]``, natural log, element (b, s) at ``state_offsets[b] + s``); None starts from the FSMs' own initial vectors.
+        ``closed`` (int32 ``[B]``, None: all open): 0 -- the audio goes on behind the window, the path ends in the best real state of
+        the last frame; != 0 -- the audio ends with the window, the path ends in the final state (with ``state`` None: ``viterbi``'s
+        path and score, bit for bit).  ``converged[b]`` is the convergence point: the last frame count n at which every surviving
+        path passes ONE state -- ``path[b, :n]`` is final, whatever audio follows (0: none yet).  ``commit`` (int32 ``[B]``, clamped to
+        ``[0, lens[b]]``; None: ``lens``, or 0 with ``commit_converged``) is the frame count c that ``state_out`` and ``mcommit``
+        (the largest score of a path over the first c frames, taken off ``state_out``) belong to; ``commit_converged`` raises it to
+        ``converged`` where that is later; ``ncommit`` returns it.  Re-windowing: a second window over the frames from c on, with
+        ``state`` = this ``state_out`` and the same ``closed``, continues this path and scores ``score - mcommit``
+        (``streaming.OnlineViterbi`` keeps that book).  ``want_state`` may also be the tensor that receives the state, ``state``
+        itself included.  ``path`` is -1 beyond the lengths and where there is no path.  Tropical batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        st = None
+        if state is not None:
+            st = torch.as_tensor(np.ascontiguousarray(state, dtype=np.float32)).cuda() if not isinstance(state, torch.Tensor) else state
+            if st.dtype != torch.float32 or st.device != Vt.device:
+                raise TypeError("state must be a float32 tensor on V's device")
+            if st.dim() != 1 or st.numel() != self.total_states or not st.is_contiguous():
+                raise _lib.DimensionMismatch(-2, f"state must be a contiguous [{self.total_states}] vector, got {tuple(st.shape)}")
+
+        def per_utt(x, name):
+            if x is None:
+                return None
+            t = x.to(device=Vt.device, dtype=torch.int32) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.int32)).to(Vt.device)
+            if t.dim() != 1 or t.numel() != B:
+                raise _lib.DimensionMismatch(-2, f"{name} must be a [{B}] vector, got {tuple(t.shape)}")
+            return t.contiguous()
+
+        cl, cm = per_utt(closed, "closed"), per_utt(commit, "commit")
+        path = torch.empty((B, N), dtype=torch.int32, device=Vt.device)
+        score = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        conv = torch.empty(B, dtype=torch.int32, device=Vt.device)
+        ncommit = torch.empty(B, dtype=torch.int32, device=Vt.device)
+        mcommit = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        so = None
+        if isinstance(want_state, torch.Tensor):
+            so = want_state
+            if so.dtype != torch.float32 or so.device != Vt.device:
+                raise TypeError("the state buffer must be a float32 tensor on V's device")
+            if so.dim() != 1 or so.numel() != self.total_states or not so.is_contiguous():
+                raise _lib.DimensionMismatch(-2, f"the state buffer must be a contiguous [{self.total_states}] vector, got {tuple(so.shape)}")
+        elif want_state:
+            so = torch.empty(self.total_states, dtype=torch.float32, device=Vt.device)
+        check(lib.mm_viterbiwindow_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
+                                       lt.data_ptr() if lt is not None else None, N,
+                                       st.data_ptr() if st is not None else None,
+                                       cl.data_ptr() if cl is not None else None, cm.data_ptr() if cm is not None else None,
+                                       1 if commit_converged else 0, so.data_ptr() if so is not None else None,
+                                       mcommit.data_ptr(), ncommit.data_ptr(), path.data_ptr(), path.stride(0), score.data_ptr(),
+                                       conv.data_ptr(), self._stream(torch)))
+        res = (path, score, conv, ncommit, mcommit, so)
+        return tuple(t.cpu().numpy() if t is not None else None for t in res) if as_numpy else res
 
 
     def totalsum(self, n: int, cumulative: bool = False):
@@ -1143,6 +1202,16 @@ def bestpath(fsm, Vhats, Chats=None):
     V, lens = _need_expanded(Vhats)
     path, score = bf.viterbi(V, lens)
     return [path[b, : lens[b]].copy() for b in range(bf.B)], score
+
+
+def windowbestpath(fsm, Vhats, Chats=None, closed=None):
+    """Windowed best paths -- see ``BatchedFSM.viterbiwindow`` -- in ``bestpath``'s call shape, from the FSMs' own initial vectors:
+    per utterance the 0-based state sequence of the window's best path, its weight and its convergence point (the leading
+    ``converged[b]`` states are final whatever audio follows).  ``closed`` None: every window ends open."""
+    bf = _as_batch(fsm, Chats)
+    V, lens = _need_expanded(Vhats)
+    path, score, conv, _, _, _ = bf.viterbiwindow(V, lens, closed=closed)
+    return [path[b, : lens[b]].copy() for b in range(bf.B)], score, conv
 
 
 def maxstateposteriors(fsm, Vhats, Chats=None):

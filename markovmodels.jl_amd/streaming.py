@@ -1,4 +1,5 @@
-"""Streaming inference on top of the engine: the forward filter and the fixed-lag smoother of a log batch run over audio in chunks.
+"""Streaming inference on top of the engine: the forward filter and the fixed-lag smoother of a log batch, and the online best-path
+decoder of a tropical batch, run over audio in chunks.
 
 ``ForwardFilter`` keeps, per utterance of a batch, the carried state of ``BatchedFSM.filterposteriors`` (mm_filterposteriors_f32:
 the one-step prediction behind the last frame seen, normalised by the mass alive there) and the running prefix log-likelihood.
@@ -9,6 +10,9 @@ an argument of the call.  Everything is a launch chain on the caller's stream; n
 
 ``FixedLagSmoother`` is its companion on ``BatchedFSM.windowposteriors`` (mm_windowposteriors_f32): every frame waits for ``lag``
 frames of its future and is emitted once, with the smoothing posterior given everything pushed by then.
+
+``OnlineViterbi`` is the decoder, on ``BatchedFSM.viterbiwindow`` (mm_viterbiwindow_f32): every frame is emitted once, as soon as
+all surviving paths agree on it (the convergence point), or when ``max_pending`` frames wait behind it.
 """
 from __future__ import annotations
 
@@ -161,5 +165,112 @@ class FixedLagSmoother:
         m = torch.as_tensor(mask).to(device=self.state.device, dtype=torch.bool)
         self.state.copy_(torch.where(m[self._utt], self._reset, self.state))
         self.loglik.masked_fill_(m, 0.0)
+        self.npending.masked_fill_(m, 0)
+        return self
+
+
+class OnlineViterbi:
+    """The online best-path decoder of ``batch`` (a tropical ``BatchedFSM``), one stream of audio per utterance, on
+    ``BatchedFSM.viterbiwindow`` (mm_viterbiwindow_f32): online alignment, keyword spotting, endpointing on the best path, live
+    captioning -- without re-running the prefix at every chunk.
+
+    A ``push`` runs one open window over the pending frames and the chunk and emits every frame up to the window's CONVERGENCE
+    POINT, the last frame all surviving paths pass: those states are final, they are the best path of the whole audio whatever
+    follows.  The frames behind it stay pending, at most ``max_pending`` of them: what would not fit is committed from the
+    window's current best path before it is final -- the fixed-lag truncation, an approximation, counted in ``nforced`` (0: the
+    output is exactly ``viterbi``'s path of the whole audio).  Every frame is emitted exactly once, by a ``push`` or by
+    ``finish``; the utterances advance each by its own ``lens``.  Everything is a launch chain on the caller's stream: the
+    data-dependent commit stays in device tensors, nothing synchronises the host except what ``count`` costs the caller to read.
+
+    ``state``    float32 ``[total_states]`` device tensor: ``viterbiwindow``'s carried state behind the last emitted frame
+    ``score``    float64 ``[B]`` device tensor: the sum of ``mcommit``, the best score over the frames emitted so far
+    ``nforced``  int64 ``[B]`` device tensor: frames emitted before they were final
+    ``pending``  float32 ``[B, max_pending, P]`` device tensor, ``npending`` int32 ``[B]``: the frames pushed and not yet emitted"""
+
+    def __init__(self, batch, max_pending):
+        import torch
+
+        if int(max_pending) < 1:
+            raise ValueError("max_pending must be at least one frame")
+        self.batch, self.max_pending = batch, int(max_pending)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        B = batch.B
+        self.pending = torch.zeros((B, self.max_pending, batch.P), dtype=torch.float32, device=dev)
+        self.npending = torch.zeros(B, dtype=torch.int32, device=dev)
+        # the reset vector, once: a window with lens = 0 passes the start vector through (NULL in: alpha_hat)
+        self._reset = batch.viterbiwindow(self.pending[:, :1], self.npending, want_state=True)[5]
+        sizes = torch.as_tensor([int(c.S1) for c in batch.cfsms], device=dev)
+        self._utt = torch.repeat_interleave(torch.arange(B, device=dev), sizes)  # state -> utterance
+        self._final = torch.as_tensor(batch.state_offsets[1:] - 1, dtype=torch.int64, device=dev)
+        self.state = self._reset.clone()
+        self.score = torch.zeros(B, dtype=torch.float64, device=dev)
+        self.nforced = torch.zeros(B, dtype=torch.int64, device=dev)
+
+    def push(self, V_chunk, lens=None):
+        """The next chunk ``V_chunk[B, n, P]`` (``lens[b]`` of its frames belong to utterance b; 0: the utterance stands still).
+        Returns ``(states[B, max_pending + n], count[B])``: the first ``count[b]`` entries of ``states[b]`` are the newly emitted
+        0-based states of b's oldest pending frames, in order, the rest is -1 (as are the states of an utterance without a
+        path).  NumPy for a NumPy chunk, device tensors for a device chunk."""
+        import torch
+
+        as_numpy = not isinstance(V_chunk, torch.Tensor)
+        dev = self.state.device
+        Vc = torch.as_tensor(V_chunk, dtype=torch.float32).to(dev) if as_numpy else V_chunk
+        B, n, P = Vc.shape
+        L = torch.full((B,), n, dtype=torch.int32, device=dev) if lens is None else torch.as_tensor(lens).to(device=dev, dtype=torch.int32)
+        L = L.clamp(0, n)
+        W = self.max_pending + n
+        t = torch.arange(W, device=dev)[None, :]  # [1, W]
+        npd = self.npending[:, None].long()
+        # utterance b's window: its pending frames, then its frames of the chunk
+        both = torch.cat([self.pending, Vc], dim=1)
+        src = torch.where(t < npd, t, (self.max_pending + t - npd).clamp(max=W - 1))
+        win = torch.gather(both, 1, src[:, :, None].expand(B, W, P)).contiguous()
+        wlen = self.npending + L
+        forced = (wlen - self.max_pending).clamp(min=0)
+        path, _, conv, ncommit, mcommit, _ = self.batch.viterbiwindow(win, wlen, state=self.state, commit=forced, commit_converged=True,
+                                                                      want_state=self.state)
+        self.score += mcommit.double()
+        self.nforced += (ncommit - conv).clamp(min=0).long()
+        # the frames behind the commit frame stay pending
+        keep = (ncommit[:, None].long() + t[:, : self.max_pending]).clamp(max=W - 1)
+        self.pending = torch.gather(win, 1, keep[:, :, None].expand(B, self.max_pending, P)).contiguous()
+        self.npending = wlen - ncommit
+        out = torch.where(t < ncommit[:, None], path, torch.full_like(path, -1))
+        return (out.cpu().numpy(), ncommit.cpu().numpy()) if as_numpy else (out, ncommit)
+
+    def finish(self, mask=None, as_numpy=False):
+        """The audio of the utterances of ``mask`` (bool ``[B]``; None: all) ends here: one closed window over their pending
+        frames.  Returns ``(states[B, max_pending], count[B], score[B])``: the first ``count[b]`` entries of ``states[b]`` are the
+        states of b's remaining frames, ``score`` (float64) = the running ``score`` + the closed window's, the weight ``viterbi``
+        gives the best path of the whole audio when ``nforced`` is 0.  An utterance with nothing pending ends on the carried state's
+        final entry, the best final weight behind its last frame (a window without a frame has no score of its own).  The other
+        utterances take no part (count 0, score -inf) and go on afterwards; the masked ones are reset."""
+        import torch
+
+        dev = self.state.device
+        m = torch.ones(self.batch.B, dtype=torch.bool, device=dev) if mask is None else torch.as_tensor(mask).to(device=dev, dtype=torch.bool)
+        count = torch.where(m, self.npending, torch.zeros_like(self.npending))
+        path, sc, _, _, _, _ = self.batch.viterbiwindow(self.pending, count, state=self.state, closed=m.to(torch.int32))
+        sc = torch.where(m & (count == 0), self.state[self._final], sc)
+        total = self.score + sc.double()
+        self.reset(m)
+        return (path.cpu().numpy(), count.cpu().numpy(), total.cpu().numpy()) if as_numpy else (path, count, total)
+
+    def reset(self, mask=None):
+        """Put the utterances of ``mask`` (bool ``[B]``; None: all) back on their FSMs' initial vectors with nothing pending,
+        ``score`` and ``nforced`` on 0."""
+        import torch
+
+        if mask is None:
+            self.state.copy_(self._reset)
+            self.score.zero_()
+            self.nforced.zero_()
+            self.npending.zero_()
+            return self
+        m = torch.as_tensor(mask).to(device=self.state.device, dtype=torch.bool)
+        self.state.copy_(torch.where(m[self._utt], self._reset, self.state))
+        self.score.masked_fill_(m, 0.0)
+        self.nforced.masked_fill_(m, 0)
         self.npending.masked_fill_(m, 0)
         return self
