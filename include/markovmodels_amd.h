@@ -120,6 +120,8 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * 9 = mm_filterposteriors_f32 (log batches only): mm_filter_kernel<NI,lds|global>.
  * 10 = mm_windowposteriors_f32 (log batches only): mm_window_fwd_kernel<NI,lds|global> + mm_window_bwd_kernel<...>.
  * 11 = mm_viterbiwindow_f32 (tropical batches only): mm_vitwindow_fwd_kernel<NI,lds|global> + mm_vitwindow_trace_kernel<lds|global>.
+ * 12 = mm_weightedposteriors_f32 (log batches only): mm_weights_kernel + mm_log_kernel<MODE_FB,NI,1> + mm_weighted_bwd_kernel<NI,lds|global>
+ * + mm_weighted_scatter_kernel.
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -180,6 +182,38 @@ int mm_pdfposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, i
  * synchronisation; it can be captured in a hipGraph once a first call has made the batch's arc forms and sized the workspace. */
 int mm_arcposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
                          float *counts, int64_t c_stride_b, float *init_counts, int64_t i_stride_b, float *ttl, void *stream);
+
+/* Posteriors with call-time arc weights and their full gradient.  The topology, the state maps and every compiled form of the
+ * batch stay as they are; the arc log-weights and the initial log-weights of THIS call come as device tensors:
+ *   W       device (NULL: the FSMs' own weights): W[b*w_stride_b + k], k < nnz_b, is the natural-log weight of the k-th stored entry
+ *           of T_hat of utterance b's FSM, in the order the caller gave the entries to mm_fsm_create (the order `counts` uses).
+ *           Finite, or -inf: the entry is absent for this call.  EVERY stored entry has a slot in both item forms whatever its own
+ *           weight (an entry stored with -inf included), so W can set every entry but one: the phony self-loop (final -> final)
+ *           is one(K) whatever W holds at its index -- expand() needs it to be.
+ *           w_stride_b == 0: one weight vector for the whole batch (and ONE copy of the graph's weights on the device, not B) --
+ *           allowed only when all B handles of the batch are the same FSM, else MM_ERR_INVALID; 0 < w_stride_b < max_b nnz_b, or a
+ *           negative stride: MM_ERR_DIM
+ *   W_init  device (NULL: the FSMs' own alpha_hat): W_init[b*wi_stride_b + m] is the weight of the m-th stored entry of alpha_hat,
+ *           in init_idx order; wi_stride_b is checked like w_stride_b (against max_b n_init_b)
+ *   gamma, ttl            what mm_pdfposteriors_f32 is defined to return for the batch whose FSMs hold these weights (ttl = log Z_b)
+ *   counts, init_counts   what mm_arcposteriors_f32 is defined to return for that batch; slots nnz_b <= k < c_stride_b untouched
+ * Each of the four outputs is optional (NULL); all four NULL: MM_ERR_INVALID.  gamma's strides are checked as
+ * mm_expectedcost_f32 checks them, c_stride_b and i_stride_b as mm_arcposteriors_f32 does.  Consequently
+ *   counts_b[k] = d log Z_b / d W_b[k],  init_counts_b[m] = d log Z_b / d W_init_b[m],  gamma_b = d log Z_b / d V_b,
+ * and an entry at -inf has count 0.  Conventions of the arc entry: no accepting path under the call's weights (len_b = 0
+ * included): gamma = 0, all counts 0, ttl = -inf; gamma of frames n >= len_b are exact zeros; the phony self-loop's count gets its
+ * N - len_b; never a NaN for inputs that are finite or -inf.  The exact, mark and gamma policies and the posterior floor do not
+ * apply.  What the arguments alone show is refused ahead of the batch.  MM_LOG batches only: Tropical and ProbSemiring batches
+ * return MM_ERR_UNSUPPORTED.
+ * The weights are read on the device, on `stream`, when the call runs: the call is a chain of launches on `stream` and nothing
+ * else, deterministic (no atomics: the same bits on every run), and can be captured in a hipGraph once a first call has put the
+ * forms on the device and sized the workspace (mm_batch_reserve does not cover it; a capture before that: MM_ERR_INVALID) -- a
+ * replay after W was overwritten in place follows the new weights. */
+int mm_weightedposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                              const float *W, int64_t w_stride_b, const float *W_init, int64_t wi_stride_b,
+                              float *gamma, int64_t g_stride_b, int64_t g_stride_n, int64_t g_stride_p,
+                              float *counts, int64_t c_stride_b, float *init_counts, int64_t i_stride_b,
+                              float *ttl, void *stream);
 
 /* Posterior path sampling (forward filtering, backward sampling): nsamples state sequences per utterance, drawn from the
  * posterior over complete paths

@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, viterbiwindow, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, viterbiwindow, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -238,6 +238,45 @@ function arcposteriors(b::ROCBatch, V::ROCArray{Float32,3}, fsms::AbstractVector
     mats = [SparseMatrixCSC(size(T, 1), size(T, 2), copy(T.colptr), copy(T.rowval), c[1:nnz(T), u]) for (u, T) in enumerate(Ts)]
     inits = [SparseVector(length(a), copy(SparseArrays.nonzeroinds(a)), iv[1:nnz(a), u]) for (u, a) in enumerate(αs)]
     mats, inits, Array(ttl)
+end
+
+"""
+    weightedposteriors(b::ROCBatch, V::ROCArray{Float32,3}, fsms, W, lens = nothing; W_init = nothing) -> (γ, counts, init, ttl)
+
+Posteriors with call-time arc weights (mm_weightedposteriors_f32 in the header) of a log-semiring batch: the topology and the
+compiled forms stay the batch's, the arc log-weights of this call are `W` and the initial log-weights `W_init`, both on the
+device.  `W` a `ROCVector{Float32}` is one weight vector for the whole batch (all utterances must be the same FSM), a
+`ROCMatrix{Float32}` of nnz rows and B columns one per utterance, `nothing` the FSMs' own; the entries follow `nonzeros(T̂)`
+(the order `counts` uses), `W_init` likewise follows `nonzeros(α̂)`.  `-Inf32` takes an entry out for this call; the phony
+self-loop stays one(K).  Returns γ (P × N × B, as `pdfposteriors`), the counts and initial occupancies as `arcposteriors`
+returns them, and ttl = log Z: `counts = ∂ log Z / ∂ W`, `init = ∂ log Z / ∂ W_init`, `γ = ∂ log Z / ∂ V`.
+"""
+function weightedposteriors(b::ROCBatch, V::ROCArray{Float32,3}, fsms::AbstractVector, W, lens = nothing; W_init = nothing)
+    P, N, B = size(V)
+    P == b.P || throw(DimensionMismatch("V has $P pdfs, the FSMs $(b.P)"))
+    length(fsms) == B || throw(DimensionMismatch("$(length(fsms)) FSMs for a batch of $B utterances"))
+    Ts = [SparseMatrixCSC(f.T̂) for f in fsms]
+    αs = [SparseVector(f.α̂) for f in fsms]
+    K = maximum(nnz, Ts)
+    I = max(1, maximum(nnz, αs))
+    wptr(w) = w === nothing ? Ptr{Float32}(C_NULL) : Ptr{Float32}(pointer(w))
+    wstride(w, need) = (w === nothing || ndims(w) == 1) ? 0 :
+        (size(w, 1) >= need && size(w, 2) == B ? size(w, 1) : throw(DimensionMismatch("weights must be $need × $B, got $(size(w))")))
+    W === nothing || size(W, 1) >= K || throw(DimensionMismatch("W has $(size(W, 1)) entries, the largest FSM $K"))
+    γ = ROCArray{Float32}(undef, B, P, N)
+    counts = ROCArray{Float32}(undef, K, B)
+    init = ROCArray{Float32}(undef, I, B)
+    ttl = ROCArray{Float32}(undef, B)
+    lp = lens === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(lens))
+    check(ccall((:mm_weightedposteriors_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Float32}, Int64, Ptr{Float32}, Int64,
+         Ptr{Float32}, Int64, Int64, Int64, Ptr{Float32}, Int64, Ptr{Float32}, Int64, Ptr{Float32}, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, lp, N, wptr(W), wstride(W, K), wptr(W_init), wstride(W_init, maximum(nnz, αs)),
+        pointer(γ), 1, B * P, B, pointer(counts), K, pointer(init), I, pointer(ttl), AMDGPU.stream().stream))
+    c, iv = Array(counts), Array(init)
+    mats = [SparseMatrixCSC(size(T, 1), size(T, 2), copy(T.colptr), copy(T.rowval), c[1:nnz(T), u]) for (u, T) in enumerate(Ts)]
+    inits = [SparseVector(length(a), copy(SparseArrays.nonzeroinds(a)), iv[1:nnz(a), u]) for (u, a) in enumerate(αs)]
+    permutedims(γ, (2, 3, 1)), mats, inits, Array(ttl)
 end
 
 """

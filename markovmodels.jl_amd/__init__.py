@@ -2,7 +2,7 @@
 
 Host-side mirror of the reference's hot-path interface (src/MarkovModels.jl:14-45:
 FSM, nstates, rawunion, CompiledFSM, batch, compile, expand, alpha-recursion,
-beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, windowbestpath, arcposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
+beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, windowbestpath, arcposteriors, weightedposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
 The directory name contains a dot, so load it with
 ``__graft_entry__.load_package()`` (importlib) rather than a plain import.
 """
@@ -32,6 +32,7 @@ from .inference import (  # noqa: F401
     totalsum,
     totalweightsum,
     windowbestpath,
+    weightedposteriors,
     windowposteriors,
     αrecursion,
     βrecursion,
@@ -42,5 +43,7 @@ from .lfmmi import lfmmi_loss  # noqa: F401
 from .mbr import expected_cost, smbr_loss  # noqa: F401
 from . import entropy  # noqa: F401
 from .entropy import conditional_entropy_loss, path_entropy  # noqa: F401
+from . import graphweights  # noqa: F401
+from .graphweights import graph_loglik, reestimate  # noqa: F401
 from . import streaming  # noqa: F401
 from .streaming import FixedLagSmoother, ForwardFilter, OnlineViterbi  # noqa: F401

@@ -212,6 +212,9 @@ struct mm_fsm_s {
     // leaky posteriors (MM_LOG): the leak rows -- rho(j) = (+)_k alpha_hat(k) T_hat(k, j), log2 domain, [S1] -- made on the first
     // mm_leakyposteriors_f32 call that needs them
     DevMem leak_blob;
+    // posteriors with call-time weights (MM_LOG): the weight form -- slot -> caller entry of both item forms, state -> entry of
+    // alpha_hat -- made on the first mm_weightedposteriors_f32 call that needs it
+    DevMem weight_blob;
 };
 
 // Test/diagnostic switches.  Read from the environment at mm_batch_create (and once per process for the entries that have no
@@ -349,6 +352,10 @@ struct mm_batch_s {
     DevMem d_samp;
     // leaky posteriors (mm_leakyposteriors_f32): the utterances' LeakDev descriptors on the device (made on the first call)
     DevMem d_leak;
+    // posteriors with call-time weights (mm_weightedposteriors_f32): the utterances' WeightDev descriptors on the device (made on the
+    // first call), the slots of all their forward / backward item forms (what a weight plane per utterance holds)
+    DevMem d_wforms;
+    int64_t w_slots[2] = {0, 0};
 };
 
 static bool on_pairs(mm_batch_t h) { return h->fb == Fb::Pairs || h->fb == Fb::Split; }
@@ -431,20 +438,21 @@ static Geometry pick_geometry(mm_batch_t h) {
 }
 
 // ---- one plan per entry that runs on the item form: its launch geometry and where its state vectors live
-enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter, Window, VitWindow };
+enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter, Window, VitWindow, Weighted };
 struct ItemPlan {
     ItemEntry e;
     int NW, NI;        // waves per workgroup, register-resident items per wave of the instance (8 or 0)
     bool global;       // the state vectors in global memory (BIGV), else in LDS
     bool stage;        // (Sample) mm_sample_kernel keeps two alpha~ rows in LDS, else it gathers them from global memory
-    size_t lds_bytes;  // dynamic LDS of the chosen placement (Arcs: of the forward kernel; mm_arc_kernel adds MM_ARC_LDS_EXTRA)
+    size_t lds_bytes;  // dynamic LDS of the chosen placement (Arcs: of the forward kernel; mm_arc_kernel adds MM_ARC_LDS_EXTRA;
+                       // Weighted: of mm_weighted_bwd_kernel -- its forward launch takes the item kernel's plan, as the arc entry's)
 };
 // The only source of the above.  The vectors are global when the entry's LDS plan (the item kernel's, with the stage rows for
 // all but the export modes, + the arc kernel's extra; Cost: cost_lds_plan; Leaky: leaky_lds_plan; Entropy: entropy_lds_plan; Filter:
 // filter_lds_plan, no larger than the export modes'; Window: window_lds_plan, the arc kernel's size) does not fit 160 KB, when
 // MM_BIGV asks for it, or for the arc, sampling, cost, leaky, entropy, filter and window kernels when NI = 0: they have no
 // streamed-only instance with the vectors in LDS.  VitWindow (tropical batches): the tropical kernel's geometry, its LDS plan + the
-// arc kernel's extra.
+// arc kernel's extra.  Weighted: the arc kernel's size + one row of state posteriors (mm_weighted_lds_bytes), 8 waves like Arcs.
 // `global` never depends on max_items, nor does NI except Tropical's (8: the whole graph is register-resident): mm_batch_create
 // asks before the item forms are up, and ensure_item_forms raises max_items later -- only NW follows it.
 static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
@@ -457,16 +465,17 @@ static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
         if (e == ItemEntry::Filter) return mm_filter_lds_bytes(S1p, P1p);
         if (e == ItemEntry::Window) return mm_window_lds_bytes(S1p, P1p);
         if (e == ItemEntry::VitWindow) return mm_vitwindow_lds_bytes(S1p, P1p);
+        if (e == ItemEntry::Weighted) return mm_weighted_lds_bytes(S1p, P1p);
         return e == ItemEntry::Cost ? mm_cost_lds_bytes(S1p, P1p) : size_t(lds_plan(S1p, P1p, e != ItemEntry::Export).total) * 4;
     };
     const bool derived = e == ItemEntry::Arcs || e == ItemEntry::Sample || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy ||
-                         e == ItemEntry::Filter || e == ItemEntry::Window;
+                         e == ItemEntry::Filter || e == ItemEntry::Window || e == ItemEntry::Weighted;
     ItemPlan pl{e, g.NW, g.NI, false, false, 0};
     pl.global = bytes(h->max_S1p) + (e == ItemEntry::Arcs ? MM_ARC_LDS_EXTRA : 0) > lds_max || h->dbg.bigv || (derived && g.NI == 0);
     pl.lds_bytes = bytes(pl.global ? 0 : h->max_S1p);
     // (8 items' arcs and their sums / the pair arithmetic / the leak term and its sums per wave: compiled for 8 waves per CU)
     if (e == ItemEntry::Arcs || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy || e == ItemEntry::Filter ||
-        e == ItemEntry::Window)
+        e == ItemEntry::Window || e == ItemEntry::Weighted)
         pl.NW = std::min(g.NW, 8);
     if (e == ItemEntry::Sample) pl.stage = !pl.global && !h->dbg.sample_nostage && size_t(h->max_S1p) * 8 <= lds_max;
     if (e == ItemEntry::Tropical || e == ItemEntry::VitWindow) {
@@ -2622,6 +2631,13 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
             "mm_vitwindow_trace_kernel<" + where_of(mm_vitwindow_flags_global(h->max_S1p)) +
             "> (best path, surviving sets back to the convergence point, state_out and mcommit at the commit frame); state vectors " +
             (pl.global ? "in global memory" : "in LDS");
+    } else if (entry == 12) {  // mm_weightedposteriors_f32
+        if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_weightedposteriors_f32 runs on log-semiring batches only");
+        const ItemPlan pl = item_plan(h, ItemEntry::Weighted);
+        const std::string ni = std::to_string(pl.NI);
+        s = "mm_weights_kernel (the call's weight planes, init vectors and descriptors; not launched when W and W_init are NULL) + mm_log_kernel<MODE_FB," + ni +
+            ",1> (forward, on the call's descriptors) + mm_weighted_bwd_kernel<" + ni + "," + where_of(pl.global) +
+            "> (backward: the arcs' sums by their owning lanes, gamma per pdf) + mm_weighted_scatter_kernel; state vectors " + (pl.global ? "in global memory" : "in LDS");
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -3064,17 +3080,31 @@ static int item_entry_begin(mm_batch_t h, const char *who, ItemEntry e, const fl
 // floats); Entropy: as Cost, the Hf store in the place of the r store -- and no such store for a value-only call (`store` false).
 // total: no less than what mm_pdfposteriors_f32 needs for as many frames.  (mm_batch_reserve does not cover it.)  Filter keeps
 // nothing: its offsets stay in registers, total = 0 whatever N -- the workspace is neither grown nor touched.
-struct ItemWs { size_t c = 0, acc = 0, post1 = 0, r = 0, o = 0, big = 0, total = 0; };
-static ItemWs item_ws_layout(mm_batch_t h, const ItemPlan &pl, int64_t N, bool store = true) {
+struct ItemWs { size_t c = 0, acc = 0, post1 = 0, r = 0, o = 0, big = 0, plane[2] = {0, 0}, initp = 0, utts = 0, total = 0; };
+// Weighted: the arc entry's areas, then what the call's weights need (wplanes / wiplanes: 0 none given, 1 one vector for the batch
+// -- the planes of ONE FSM --, 2 a vector per utterance): the {col, w} planes of both item forms, the dense init vectors, the call's
+// descriptors.
+static ItemWs item_ws_layout(mm_batch_t h, const ItemPlan &pl, int64_t N, bool store = true, int wplanes = 0, int wiplanes = 0) {
     ItemWs W;
     if (pl.e == ItemEntry::Filter) return W;
     const size_t rows = align_up(size_t(h->total_s1p) * size_t(N + 1) * 4, 256);
     W.c = rows;
     W.total = W.c + ws_c_bytes(h, N);
-    if (pl.e == ItemEntry::Arcs) {
+    if (pl.e == ItemEntry::Arcs || pl.e == ItemEntry::Weighted) {
         W.acc = W.total;
         W.post1 = W.acc + align_up(size_t(h->arc_slots) * 8, 256);
         W.total = W.post1 + align_up(size_t(h->total_s1p) * 4, 256);
+        if (pl.e == ItemEntry::Weighted && (wplanes || wiplanes)) {
+            const mm_fsm_s &f0 = *h->fsms[0];
+            for (int d = 0; d < 2; ++d) {
+                W.plane[d] = W.total;
+                W.total += align_up(size_t(wplanes == 2 ? h->w_slots[d] : wplanes == 1 ? f0.packed[d].n_slot_rows * 64 : 0) * sizeof(Slot), 256);
+            }
+            W.initp = W.total;
+            W.total += align_up(size_t(wiplanes == 2 ? h->total_s1p : wiplanes == 1 ? f0.S1p : 0) * 4, 256);
+            W.utts = W.total;
+            W.total += align_up(size_t(h->B) * sizeof(UttDesc), 256);
+        }
     } else if (ws_holds_big(pl.e)) {
         W.r = W.total;
         W.o = W.r + (store ? rows : 0);
@@ -3352,6 +3382,156 @@ int mm_windowposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t v
     wp.commit = commit;
     wp.lcommit = lcommit;
     return mm_launch_window(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, p, wp, static_cast<hipStream_t>(stream));
+}
+
+// ---- posteriors with call-time arc weights (mm_kernel_weighted.hip)
+// the caller entry behind every slot of item form d (-1: a padding slot, or the phony self-loop -- they keep the FSM's own weight)
+static std::vector<int32_t> pack_slot2k(const mm_fsm_s &f, int d) {
+    const Packed &pk = f.packed[d];  // (ensure_item_forms packed it)
+    std::vector<int32_t> slot2k(size_t(pk.n_slot_rows) * 64, -1);
+    const std::vector<int64_t> &rowptr = f.mat[d].rowptr;
+    // the caller's entry of every entry of mat[d]: bwd_caller for T_hat; for T_hat' (rows = destinations, sources ascending, ties in
+    // T_hat's order: transpose is stable) the walk over T_hat that transpose made
+    std::vector<int64_t> caller;
+    if (d == 1) {
+        caller = f.bwd_caller;
+    } else {
+        caller.resize(size_t(f.nnz));
+        std::vector<int64_t> cur(rowptr.begin(), rowptr.end() - 1);
+        const Csr &bwd = f.mat[1];
+        for (int64_t i = 0; i < f.S1; ++i)
+            for (int64_t a = bwd.rowptr[size_t(i)]; a < bwd.rowptr[size_t(i) + 1]; ++a) caller[size_t(cur[size_t(bwd.col[size_t(a)])]++)] = f.bwd_caller[size_t(a)];
+    }
+    for (size_t it = 0; it < pk.items.size(); ++it) {
+        const ItemMeta &im = pk.items[it];
+        const int g = 1 << im.log2g;
+        for (int lane = 0; lane < 64; ++lane) {
+            const int32_t row = pk.rowinfo[it * 64 + size_t(lane)].row;
+            if (row < 0) continue;
+            // (pack_rows: lane `sub` of the row's group holds arcs sub, sub + g, ... in slots k = 0, 1, ...)
+            int64_t k = 0;
+            for (int64_t a = rowptr[size_t(row)] + (lane & (g - 1)); a < rowptr[size_t(row) + 1]; a += g, ++k) {
+                const int64_t c = caller[size_t(a)];
+                if (c != f.kphony) slot2k[size_t((int64_t(im.slot_row) + k) * 64 + lane)] = int32_t(c);
+            }
+        }
+    }
+    return slot2k;
+}
+// The weight forms: per FSM slot2k of both directions and state2init; per utterance a WeightDev with its first slots in the planes.
+// With them the batch's global vectors where only this entry's LDS plan asks for them (as ensure_leak_rows).
+static int ensure_weight_forms(mm_batch_t h, const ItemPlan &pl, void *stream) {
+    if (pl.global && !h->ws_big) {
+        if (capturing(stream))
+            return fail(MM_ERR_INVALID, "the global vectors of this batch are not on the device yet: run mm_weightedposteriors_f32 once outside a stream capture");
+        if (hipMalloc(&h->ws_big, size_t(h->B) * 4 * size_t(h->max_S1p) * sizeof(float)) != hipSuccess) {
+            h->ws_big = nullptr;
+            return fail(MM_ERR_HIP, "mm_weightedposteriors_f32: device allocation failed");
+        }
+    }
+    int64_t slots[2] = {0, 0};
+    const int rc = ensure_derived_forms<WeightDev>(
+        h, stream, "weight", "mm_weightedposteriors_f32", h->d_wforms, &mm_fsm_s::weight_blob,
+        [](mm_fsm_t f, Blob &bl) {
+            (void)bl.add(pack_slot2k(*f, 0));  // (at 0)
+            (void)bl.add(pack_slot2k(*f, 1));
+            std::vector<int32_t> s2i(size_t(f->S1), -1);
+            for (size_t m = 0; m < f->init_order.size(); ++m) s2i[size_t(f->init_order[m])] = int32_t(m);  // (a state given twice: the last, as mm_fsm_create)
+            (void)bl.add(s2i);
+        },
+        [&](mm_fsm_t f) {
+            const char *base = static_cast<const char *>(f->weight_blob.get());
+            const int64_t n0 = f->packed[0].n_slot_rows * 64, n1 = f->packed[1].n_slot_rows * 64;
+            const size_t o1 = align_up(size_t(n0) * 4, 256), o2 = align_up(o1 + size_t(n1) * 4, 256);  // (where Blob::add put them)
+            WeightDev w{};
+            w.slot2k[0] = reinterpret_cast<const int *>(base);
+            w.slot2k[1] = reinterpret_cast<const int *>(base + o1);
+            w.state2init = reinterpret_cast<const int *>(base + o2);
+            w.plane_off[0] = slots[0];
+            w.plane_off[1] = slots[1];
+            w.nslots[0] = int(n0);
+            w.nslots[1] = int(n1);
+            slots[0] += n0;
+            slots[1] += n1;
+            return w;
+        });
+    if (!rc && slots[1]) {  // (0: they were up already)
+        h->w_slots[0] = slots[0];
+        h->w_slots[1] = slots[1];
+    }
+    return rc;
+}
+
+int mm_weightedposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, const float *Wt, int64_t wsb,
+                              const float *Wi, int64_t wisb, float *gamma, int64_t gsb, int64_t gsn, int64_t gsp, float *counts, int64_t csb,
+                              float *init_counts, int64_t isb, float *ttl, void *stream) {
+    const char *who = "mm_weightedposteriors_f32";
+    // what the arguments alone show comes first (without a batch: the frames' own extent), then the batch's refusals
+    if (!gamma && !counts && !init_counts && !ttl) return fail(MM_ERR_INVALID, std::string(who) + ": gamma, counts, init_counts and ttl are all NULL");
+    if ((Wt && wsb < 0) || (Wi && wisb < 0))
+        return fail(MM_ERR_DIM, std::string(who) + ": w_stride_b " + std::to_string(wsb) + " / wi_stride_b " + std::to_string(wisb) + " is negative");
+    if (gamma) {
+        const int64_t B = h ? h->B : 1, P = h ? h->max_P1 - 1 : 1;
+        if (!strides_hold(gsb, B, gsn, N, gsp, P))
+            return fail(MM_ERR_DIM, std::string(who) + ": g strides (" + std::to_string(gsb) + ", " + std::to_string(gsn) + ", " + std::to_string(gsp) +
+                                        ") cannot hold " + std::to_string(B) + " x " + std::to_string(N) + " x " + std::to_string(P) + " elements");
+    }
+    if (h && h->semiring == MM_LOG) {  // (the batch's own numbers need no device either)
+        bool same = true;
+        int64_t max_nnz = 0, max_init = 0;
+        for (int64_t b = 0; b < h->B; ++b) {
+            same &= h->fsms[size_t(b)] == h->fsms[0];
+            max_nnz = std::max<int64_t>(max_nnz, h->fsms[size_t(b)]->nnz);
+            max_init = std::max<int64_t>(max_init, int64_t(h->fsms[size_t(b)]->init_order.size()));
+        }
+        if (((Wt && wsb == 0) || (Wi && wisb == 0)) && !same)
+            return fail(MM_ERR_INVALID, std::string(who) + ": stride 0 (one weight vector for the batch) needs all " + std::to_string(h->B) + " handles of the batch to be the same FSM");
+        if (Wt && wsb > 0 && wsb < max_nnz)
+            return fail(MM_ERR_DIM, std::string(who) + ": w_stride_b " + std::to_string(wsb) + " < " + std::to_string(max_nnz) + " entries of the largest FSM");
+        if (Wi && wisb > 0 && wisb < max_init)
+            return fail(MM_ERR_DIM, std::string(who) + ": wi_stride_b " + std::to_string(wisb) + " < " + std::to_string(max_init) + " initial states of the largest FSM");
+        if (counts && csb < max_nnz)
+            return fail(MM_ERR_DIM, std::string(who) + ": c_stride_b " + std::to_string(csb) + " < " + std::to_string(max_nnz) + " entries of the largest FSM");
+        if (init_counts && isb < max_init)
+            return fail(MM_ERR_DIM, std::string(who) + ": i_stride_b " + std::to_string(isb) + " < " + std::to_string(max_init) + " initial states of the largest FSM");
+    }
+    ItemPlan pl;
+    int rc = item_entry_begin(h, who, ItemEntry::Weighted, V, N, stream, []() { return int(MM_OK); }, &pl);
+    if (rc) return rc;
+    rc = ensure_arc_forms(h, stream);
+    if (!rc) rc = ensure_weight_forms(h, pl, stream);
+    if (rc) return rc;
+    const ItemWs W = item_ws_layout(h, pl, N, true, Wt ? (wsb == 0 ? 1 : 2) : 0, Wi ? (wisb == 0 ? 1 : 2) : 0);
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    rc = item_ws_bind(h, pl, W, p, stream);
+    if (rc) return rc;
+    p.gamma = gamma;
+    p.gsb = gsb;
+    p.gsn = gsn;
+    p.gsp = gsp;
+    char *ws = static_cast<char *>(h->ws);
+    WeightedParams wp{};
+    wp.arcs = static_cast<const ArcDev *>(h->d_arcs.get());
+    wp.wforms = static_cast<const WeightDev *>(h->d_wforms.get());
+    wp.utts_own = h->d_utts;
+    wp.utts_call = (Wt || Wi) ? reinterpret_cast<UttDesc *>(ws + W.utts) : nullptr;
+    wp.W = Wt;
+    wp.wsb = wsb;
+    wp.W_init = Wi;
+    wp.wisb = wisb;
+    wp.plane[0] = reinterpret_cast<Slot *>(ws + W.plane[0]);
+    wp.plane[1] = reinterpret_cast<Slot *>(ws + W.plane[1]);
+    wp.init_plane = reinterpret_cast<float *>(ws + W.initp);
+    wp.acc = reinterpret_cast<double *>(ws + W.acc);
+    wp.post1 = reinterpret_cast<float *>(ws + W.post1);
+    wp.counts = counts;
+    wp.csb = csb;
+    wp.init_counts = init_counts;
+    wp.isb = isb;
+    wp.ttl = ttl;
+    // (the forward launch is the arc entry's: the item kernel's plan of the same placement)
+    const size_t lds_fwd = size_t(lds_plan(pl.global ? 0 : h->max_S1p, (h->max_P1 + 3) & ~3, true).total) * 4;
+    return mm_launch_weighted(h->B, pl.NW, pl.NI, pl.global, lds_fwd, pl.lds_bytes, p, wp, static_cast<hipStream_t>(stream));
 }
 
 // ---- pdf posteriors of the leaky HMM (mm_kernel_leaky.hip)

@@ -318,4 +318,42 @@ int mm_launch_vitwindow(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, 
 size_t mm_vitwindow_lds_bytes(int S1p, int P1p);
 bool mm_vitwindow_flags_global(int S1p);  // the trace kernel's flags do not fit the LDS: they live in RunParams::ws_big
 
+// ---- posteriors with call-time arc weights (mm_weighted_tu.hip: mm_weights_kernel, mm_log_kernel's forward half on the call's
+// descriptors, mm_weighted_bwd_kernel and mm_weighted_scatter_kernel on the item form)
+struct UttDesc;  // mm_kernels.hip
+struct Slot;     // mm_pack.h
+struct WeightDev {  // one utterance's weight form (mm_engine.hip ensure_weight_forms)
+    const int *slot2k[2];   // [nslots[d]] slot of the forward / backward item form -> caller entry; -1: the slot keeps the FSM's own
+                            // weight (a padding slot, the phony self-loop)
+    const int *state2init;  // [S1] state -> its entry of alpha_hat in init_idx order, -1: none
+    long long plane_off[2];  // this utterance's first slot in a per-utterance weight plane of each direction
+    int nslots[2];
+};
+struct WeightedParams {
+    const ArcDev *arcs;       // [B]
+    const WeightDev *wforms;  // [B]
+    const UttDesc *utts_own;  // the batch's descriptors
+    UttDesc *utts_call;       // [B] the call's descriptors: g[0].slots, g[1].slots and init point at the planes (NULL: no weights given)
+    const float *W;           // NULL: the FSMs' own weights
+    long long wsb;            // 0: one vector for the batch -- ONE plane, built from utterance 0's form
+    const float *W_init;      // NULL: the FSMs' own alpha_hat
+    long long wisb;
+    Slot *plane[2];           // the call's {col, w} arrays of the forward / backward item forms
+    float *init_plane;        // dense alpha_hat in log2 units, per utterance at s1p_prefix (shared: at 0)
+    double *acc;              // as ArcParams
+    float *post1;
+    float *counts;            // NULL: not asked for
+    long long csb;
+    float *init_counts;       // NULL: not asked for
+    long long isb;
+    float *ttl;               // NULL: not asked for
+};
+// LDS bytes of mm_weighted_bwd_kernel: the arc kernel's + one row of state posteriors for the per-pdf pass
+size_t mm_weighted_lds_bytes(int S1p, int P1p);
+// lds_fwd: the item kernel's plan (the forward half, as mm_launch_arcs launches it); lds_bwd: mm_weighted_lds_bytes of the geometry.
+// gamma and its strides go where RunParams says (NULL: not asked for).  p.utts: the batch's own descriptors -- with weights given
+// (wp.utts_call != NULL) the prologue runs and the kernels behind it read the call's
+int mm_launch_weighted(int64_t B, int NW, int NI, bool bigv, size_t lds_fwd, size_t lds_bwd, const RunParams &p, const WeightedParams &wp,
+                       hipStream_t stream);
+
 }  // namespace mm

@@ -1,0 +1,34 @@
+// mm_weighted_tu.hip -- translation unit of the posteriors with call-time arc weights (mm_kernel_weighted.hip): the prologue that
+// builds the call's weight planes and descriptors, the forward half of the item kernel on them, the backward kernel that sums the
+// arcs and writes gamma, the scatter into the caller's entry order.
+#define MM_SECONDARY_TU
+#include "mm_internal.h"
+#include "mm_kernel_weighted.hip"
+
+namespace mm {
+
+size_t mm_weighted_lds_bytes(int S1p, int P1p) { return size_t(lds_plan(S1p, P1p, true).total + 2 * MM_MAX_WAVES + S1p) * 4; }
+
+template <int NI, bool BIGV>
+static int launch_weighted_ni(int64_t B, int NW, size_t lds_fwd, size_t lds_bwd, const RunParams &p, const WeightedParams &wp, hipStream_t stream) {
+    const int rc = mm_launch(mm_log_kernel<MODE_FB, NI, 1, false, BIGV>, dim3(unsigned(B)), dim3(64 * NW), lds_fwd, stream, p);
+    return rc ? rc : mm_launch(mm_weighted_bwd_kernel<NI, BIGV>, dim3(unsigned(B)), dim3(64 * NW), lds_bwd, stream, p, wp);
+}
+
+int mm_launch_weighted(int64_t B, int NW, int NI, bool bigv, size_t lds_fwd, size_t lds_bwd, const RunParams &p0, const WeightedParams &wp,
+                       hipStream_t stream) {
+    if (!(NI == 8 || (NI == 0 && bigv))) return mm_fail(MM_ERR_UNSUPPORTED, "weighted posteriors: no instance for this geometry");
+    RunParams p = p0;
+    int rc = MM_OK;
+    if (wp.utts_call) {
+        rc = mm_launch(mm_weights_kernel, dim3(unsigned(B), 16), dim3(256), 0, stream, p, wp);
+        if (rc) return rc;
+        p.utts = wp.utts_call;
+    }
+    if (NI == 8) rc = bigv ? launch_weighted_ni<8, true>(B, NW, lds_fwd, lds_bwd, p, wp, stream) : launch_weighted_ni<8, false>(B, NW, lds_fwd, lds_bwd, p, wp, stream);
+    else rc = launch_weighted_ni<0, true>(B, NW, lds_fwd, lds_bwd, p, wp, stream);
+    if (rc || !(wp.counts || wp.init_counts || wp.ttl)) return rc;
+    return mm_launch(mm_weighted_scatter_kernel, dim3(unsigned(B), 4), dim3(256), 0, stream, p, wp);
+}
+
+}  // namespace mm

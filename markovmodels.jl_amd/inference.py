@@ -407,6 +407,59 @@ class BatchedFSM:
         out = (counts, ttl) + ((init,) if want_init else ())
         return tuple(t.cpu().numpy() for t in out) if as_numpy else out
 
+    def weightedposteriors(self, V, W=None, W_init=None, lens=None, want_gamma=True, want_counts=True, want_init=False, out=None):
+        """Posteriors with call-time arc weights (mm_weightedposteriors_f32): ``(gamma[B, N, P], counts[B, max nnz], ttl[B])``, plus
+        ``init[B, max n_init]`` with ``want_init``; what ``want_gamma`` / ``want_counts`` do not ask for comes back as None.  The
+        topology and every compiled form stay the batch's; ``W`` holds the natural-log weight of every stored entry of ``T_hat``
+        (the order of ``FSM.nzval``, which ``counts`` uses), ``W_init`` that of every stored entry of ``alpha_hat``
+        (``FSM.alpha_idx`` order), both float32 on the device, finite or -inf (-inf: the entry is absent for this call).  A 1-D
+        tensor is one vector for the whole batch (all B handles must be the same FSM), ``[B, >= max nnz]`` a vector per
+        utterance; None: the FSMs' own.  The phony self-loop stays one(K) whatever ``W`` holds at its index.  The outputs are
+        what ``pdfposteriors`` / ``arcposteriors`` return for FSMs compiled with these weights, so ``counts = d ttl / d W``,
+        ``init = d ttl / d W_init`` and ``gamma = d ttl / d V``.  ``out``: a [B, N, P] view gamma is written to with its own
+        strides.  Log batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        K = max(c.fsm.nnz for c in self.cfsms)
+        I = max(1, max(len(c.fsm.alpha_idx) for c in self.cfsms))
+
+        def weights(w, need, name):
+            if w is None:
+                return None, 0
+            wt = w if isinstance(w, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(w, dtype=np.float32))
+            wt = wt.to(device=Vt.device)
+            if wt.dtype != torch.float32:
+                raise TypeError(f"{name} must be float32")
+            if wt.dim() == 1:
+                if wt.numel() < need:
+                    raise _lib.DimensionMismatch(-2, f"{name} has {wt.numel()} entries, the FSM has {need}")
+                return wt.contiguous(), 0
+            if wt.dim() != 2 or wt.shape[0] != B or wt.shape[1] < need:
+                raise _lib.DimensionMismatch(-2, f"{name} must be [{need}+] or [B={B}, {need}+], got {tuple(wt.shape)}")
+            if wt.stride(1) != 1 or (B > 1 and wt.stride(0) < need):
+                wt = wt.contiguous()
+            return wt, (wt.stride(0) if B > 1 else max(wt.stride(0), need))
+
+        Wt, wsb = weights(W, K, "W")
+        Wi, wisb = weights(W_init, max(len(c.fsm.alpha_idx) for c in self.cfsms), "W_init")
+        gamma = None
+        if want_gamma:
+            if out is not None:
+                if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != Vt.device:
+                    raise TypeError("out must be a float32 tensor on V's device")
+                if tuple(out.shape) != (B, N, P):
+                    raise _lib.DimensionMismatch(-2, f"out must be [B={B}, N={N}, P={P}], got {tuple(out.shape)}")
+            gamma = out if out is not None else torch.empty((B, N, P), dtype=torch.float32, device=Vt.device)
+        counts = torch.zeros((B, K), dtype=torch.float32, device=Vt.device) if want_counts else None
+        init = torch.zeros((B, I), dtype=torch.float32, device=Vt.device) if want_init else None
+        ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        check(lib.mm_weightedposteriors_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1), ptr(lt), N, ptr(Wt), wsb, ptr(Wi), wisb,
+                                            ptr(gamma), *(gamma.stride() if gamma is not None else (0, 0, 0)),
+                                            ptr(counts), K, ptr(init), I, ttl.data_ptr(), self._stream(torch)))
+        res = (gamma, counts, ttl) + ((init,) if want_init else ())
+        return tuple(t.cpu().numpy() if t is not None else None for t in res) if as_numpy else res
+
     def samplepaths(self, V, lens=None, nsamples=1, seed=0, want_logprob=False):
         """Posterior path samples (mm_samplepaths_f32): ``(paths[B, K, N] int32, ttl[B])``, plus ``logprob[B, K]`` when
         ``want_logprob``.  ``paths[b, k, n]`` is the 0-based state of sample k of utterance b at frame n (-1 for n >= len_b, and
@@ -696,11 +749,11 @@ class BatchedFSM:
         """The kernels the engine launches for this batch (informational): "log" = pdfposteriors, "tropical" = bestpath, "export" =
         alpharecursion / betarecursion, "arcs" = arcposteriors, "sample" = samplepaths, "cost" = expectedcost, "leaky" =
         leakyposteriors, "entropy" = pathentropy, "filter" = filterposteriors, "window" = windowposteriors,
-        "vitwindow" = viterbiwindow (tropical batches)."""
+        "vitwindow" = viterbiwindow (tropical batches), "weighted" = weightedposteriors."""
         import ctypes
 
         buf = ctypes.create_string_buffer(1024)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11}[semiring], buf, 1024))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12}[semiring], buf, 1024))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -1134,6 +1187,20 @@ def arcposteriors(fsm, Vhats, Chats=None, want_init=False):
     bf = _as_batch(fsm, Chats)
     V, lens = _need_expanded(Vhats, bf.semiring)
     return bf.arcposteriors(V, lens, want_init=want_init)
+
+
+def weightedposteriors(fsm, Vhats, W, Chats=None, W_init=None, seqlengths=None):
+    """Posteriors with call-time arc weights -- see ``BatchedFSM.weightedposteriors`` -- in ``pdfposteriors``' call shape: ``fsm``
+    the rawunion of the batch with its state maps, or a BatchedFSM / CompiledFSM (log semiring); V_hats what ``expand`` makes
+    (``seqlengths`` None: the phony row gives the lengths); ``W`` one weight vector for the batch (1-D; the batch must repeat one
+    FSM) or one per utterance ([B, max nnz]), ``W_init`` likewise or None.  Returns NumPy (gamma[B, P, N], counts[B, max nnz],
+    ttl[B], init[B, max n_init])."""
+    bf = _as_batch(fsm, Chats)
+    V, lens = _need_expanded(Vhats, bf.semiring)
+    if seqlengths is not None:
+        lens = np.asarray(seqlengths, dtype=np.int32)
+    g, c, ttl, init = bf.weightedposteriors(V, W, W_init, lens, want_init=True)
+    return np.ascontiguousarray(g.transpose(0, 2, 1)), c, ttl, init
 
 
 def expectedcost(fsm, Vhats, costs, Chats=None):
