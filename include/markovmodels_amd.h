@@ -122,6 +122,7 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * 11 = mm_viterbiwindow_f32 (tropical batches only): mm_vitwindow_fwd_kernel<NI,lds|global> + mm_vitwindow_trace_kernel<lds|global>.
  * 12 = mm_weightedposteriors_f32 (log batches only): mm_weights_kernel + mm_log_kernel<MODE_FB,NI,1> + mm_weighted_bwd_kernel<NI,lds|global>
  * + mm_weighted_scatter_kernel.
+ * 13 = mm_segmentposteriors_f32 (log batches only): mm_window_fwd_kernel<NI,lds|global> + mm_segment_bwd_kernel<...>.
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -480,6 +481,55 @@ int mm_filterposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b
 int mm_windowposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
                             const float *state_in, const int32_t *closed, const int32_t *commit, float *state_out, float *lcommit,
                             float *gamma, int64_t g_stride_b, int64_t g_stride_n, int64_t g_stride_p, float *ttl, void *stream);
+
+/* Segment posteriors: the forward-backward of a log batch over a SEGMENT of the audio, which starts from a carried vector like a
+ * window of mm_windowposteriors_f32 and ends open, on the final weights or on a carried END vector -- and hands back the end vector
+ * of the segment before it.  What the window entry cannot do: end on what comes after it.  With it the exact smoothing posteriors
+ * of a long recording -- the gamma of mm_pdfposteriors_f32, the LF-MMI gradient -- take the workspace of ONE chunk, whatever the
+ * length of the audio: pass 1 is mm_filterposteriors_f32 over the chunks (no frame kept; the start state of every chunk saved),
+ * pass 2 this entry over the chunks in reverse, each from its saved state, ending on the vector the chunk behind it returned.
+ * The extended system, lhs, start, a_n and l_n are exactly mm_windowposteriors_f32's; frames counted from 1 here and from 0 in the
+ * arrays, f the phony final state:
+ *
+ *   b_len(i)     = 1                     end_mode_b == 0                                          (open)
+ *   b_len(i)     = T_hat(i, f)           end_mode_b != 0 and (end_mode_b != 2 or end_in == NULL)  (the final weights)
+ *   b_len(i)     = exp(end_in_b(i))      end_mode_b == 2 and end_in != NULL                       (carried), real i; f's entry is not read
+ *   b_n(i)       = sum_{j real} T_hat(i,j) lhs_{n+1}(j) b_{n+1}(j)                         n < len
+ *   gamma(n,p)   = sum_{j : pdf(j) = p} a_n(j) b_n(j) / sum_j a_n(j) b_n(j)
+ *   ttl          = ln sum_j a_len(j) b_len(j)
+ *   b_0(i)       = sum_{j real} T_hat(i,j) lhs_1(j) b_1(j)      for ALL i of the extended system (b_0(f) = 0)
+ *   lend         = ln max_i b_0(i)
+ *   end_out(i)   = ln b_0(i) - lend      the largest entry is 0; the entry of f is -inf
+ *
+ *   V, lens, N, state_in, gamma and its strides, ttl   as mm_windowposteriors_f32
+ *   end_mode     device int32[B]; NULL: every utterance is open
+ *   end_in, end_out   layout of state_in / state_out (natural log, element (b, s) at state_offset_b + s).  They may be one buffer: a
+ *                workgroup reads its segment before it writes it.  end_out NULL: not written
+ *   lend         device float[B], out (NULL: not written)
+ * gamma NULL: MM_ERR_INVALID; strides that cannot hold B x N x P distinct elements: MM_ERR_DIM; both are reported before the
+ * NULL-batch check.  MM_LOG batches only: Tropical and ProbSemiring batches return MM_ERR_UNSUPPORTED.
+ * Conventions (nothing is NaN): frames n >= len of gamma are exact zeros.  len = 0 gives gamma = 0, ttl = -inf, and end_out = the
+ * end vector the segment was given: carried -- a copy of end_in as given, its final entry included, lend = 0; open -- 0 on the real
+ * states and -inf on f, lend = 0; final -- ln T_hat(i, f) - its maximum, lend = that maximum (no final weight at all: all -inf and
+ * lend = -inf).  A segment without mass -- the alive mass dies at a frame <= len, a start or end vector has no live state, or the
+ * total is zero -- gives gamma = 0, ttl = -inf, end_out = -inf everywhere and lend = -inf: a dead utterance propagates backwards
+ * through the chunks.
+ * Consequences: (a) with end_in == NULL gamma and ttl are those of mm_windowposteriors_f32 with closed = end_mode.  (b) CHAINING IS
+ * EXACT: segment A on frames 1..L1, segment B on frames L1+1..L started from the filter's state_out after L1 frames, with any end;
+ * A with end_mode = 2 and end_in = B's end_out.  Then A has, on its frames, the gamma of the one call over 1..L with B's end, B has
+ * that gamma on its own frames, and ttl_A + lend_B = the one call's ttl.  (c) a constant added to all emissions of a frame changes
+ * gamma and end_out not at all, ttl and lend by that constant.  (d) a constant added to end_in_b changes ttl and lend by it (b_0 is
+ * linear in b_len) and nothing else.  (e) d ttl / d V(n,p) = gamma(n,p).  (f) end_out and lend do not depend on state_in, as long as the segment has mass.
+ * (g) no atomics: a repeated call returns the same bits.
+ * Runs on the item form of every FSM of every log batch, one workgroup per utterance: mm_window_fwd_kernel as the window entry
+ * launches it, then mm_segment_bwd_kernel (the window's backward loop; a carried end's total from the stored alpha~ row of frame len
+ * and the end vector; one more item pass behind frame 1 for end_out and lend).  Workspace: the window entry's, the alpha~ store for
+ * N frames.  Stream contract of mm_arcposteriors_f32: launches on `stream` only, no host synchronisation; it can be captured in a
+ * hipGraph once a first call has put the batch's item forms on the device and sized the workspace (a capture before that returns
+ * MM_ERR_INVALID). */
+int mm_segmentposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                             const float *state_in, const int32_t *end_mode, const float *end_in, float *end_out, float *lend,
+                             float *gamma, int64_t g_stride_b, int64_t g_stride_n, int64_t g_stride_p, float *ttl, void *stream);
 
 /* alpha-recursion(alpha_hat, T_hat', C_hat*V_hat) (src/inference.jl:62-74) as
  * called from pdfposteriors (:150-152): out is the reference's state_A, a

@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, viterbiwindow, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -438,6 +438,39 @@ function windowposteriors(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing; s
         pointer(state_out), pointer(lcommit), pointer(γ), 1, B * P, B, pointer(ttl),
         AMDGPU.stream().stream))
     γ, ttl, lcommit, state_out
+end
+
+"""
+    segmentposteriors(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing; state = nothing, end_mode = nothing, end_in = nothing) -> (γ, ttl, lend, end_out)
+
+Segment posteriors (mm_segmentposteriors_f32 in the header) of a log-semiring batch: the forward-backward over a segment of the audio
+that starts from `state` like a window and ends open (`end_mode[b] == 0`, or `end_mode === nothing`), on the carried end vector
+`end_in` (`end_mode[b] == 2`; the layout of `state`, natural log) or on the final weights (anything else).  `γ` (B × P × N), ttl =
+log Σ a_len b_len, and what the segment BEFORE this one ends on: `end_out` = log b₀ - `lend`, `lend` = log max b₀.  Chaining is
+exact: the exact smoothing posteriors of a long recording are `filterposteriors` over the chunks, which saves each chunk's start
+state, then this call over the chunks in reverse, each on the `end_out` of the chunk behind it -- in the workspace of one chunk.
+`end_mode` is a `ROCVector{Int32}` of length B.
+"""
+function segmentposteriors(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing; state = nothing, end_mode = nothing, end_in = nothing)
+    P, N, B = size(V)
+    P == b.P || throw(DimensionMismatch("V has $P pdfs, the FSMs $(b.P)"))
+    S = Int(ccall((:mm_batch_total_states, LIB), Int64, (Ptr{Cvoid},), b.handle))
+    state === nothing || length(state) == S || throw(DimensionMismatch("state has $(length(state)) entries, the batch $S states"))
+    end_in === nothing || length(end_in) == S || throw(DimensionMismatch("end_in has $(length(end_in)) entries, the batch $S states"))
+    γ = ROCArray{Float32}(undef, B, P, N)
+    ttl = ROCArray{Float32}(undef, B)
+    lend = ROCArray{Float32}(undef, B)
+    end_out = ROCArray{Float32}(undef, S)
+    ip(x) = x === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(x))
+    fp(x) = x === nothing ? Ptr{Float32}(C_NULL) : pointer(x)
+    check(ccall((:mm_segmentposteriors_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Float32}, Ptr{Int32}, Ptr{Float32},
+         Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int64, Int64, Int64, Ptr{Float32}, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, ip(lens), N,
+        fp(state), ip(end_mode), fp(end_in),
+        pointer(end_out), pointer(lend), pointer(γ), 1, B * P, B, pointer(ttl),
+        AMDGPU.stream().stream))
+    γ, ttl, lend, end_out
 end
 
 """

@@ -2,7 +2,7 @@
 
 Host-side mirror of the reference's hot-path interface (src/MarkovModels.jl:14-45:
 FSM, nstates, rawunion, CompiledFSM, batch, compile, expand, alpha-recursion,
-beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, windowbestpath, arcposteriors, weightedposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
+beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, chunkedposteriors, windowbestpath, arcposteriors, weightedposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
 The directory name contains a dot, so load it with
 ``__graft_entry__.load_package()`` (importlib) rather than a plain import.
 """
@@ -16,6 +16,7 @@ from .inference import (  # noqa: F401
     batch,
     bestpath,
     betarecursion,
+    chunkedposteriors,
     compile,
     compile_many,
     compiled_cache_clear,
@@ -45,5 +46,7 @@ from . import entropy  # noqa: F401
 from .entropy import conditional_entropy_loss, path_entropy  # noqa: F401
 from . import graphweights  # noqa: F401
 from .graphweights import graph_loglik, reestimate  # noqa: F401
+from . import longform  # noqa: F401
+from .longform import chunked_loglik  # noqa: F401
 from . import streaming  # noqa: F401
 from .streaming import FixedLagSmoother, ForwardFilter, OnlineViterbi  # noqa: F401

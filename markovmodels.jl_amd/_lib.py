@@ -55,6 +55,7 @@ SYMBOLS = [
     "mm_pathentropy_f32",
     "mm_filterposteriors_f32",
     "mm_windowposteriors_f32",
+    "mm_segmentposteriors_f32",
     "mm_weightedposteriors_f32",
     "mm_pdfposteriors_ex",
     "mm_statemap_create",
@@ -177,6 +178,8 @@ def _load():
     lib.mm_filterposteriors_f32.argtypes = [vp, fp, i64, i64, vp, i64, fp, fp, fp, i64, i64, i64, fp, i64, fp, vp]
     lib.mm_windowposteriors_f32.restype = C.c_int
     lib.mm_windowposteriors_f32.argtypes = [vp, fp, i64, i64, vp, i64, fp, vp, vp, fp, fp, fp, i64, i64, i64, fp, vp]
+    lib.mm_segmentposteriors_f32.restype = C.c_int
+    lib.mm_segmentposteriors_f32.argtypes = [vp, fp, i64, i64, vp, i64, fp, vp, fp, fp, fp, fp, i64, i64, i64, fp, vp]
     lib.mm_weightedposteriors_f32.restype = C.c_int
     lib.mm_weightedposteriors_f32.argtypes = [vp, fp, i64, i64, vp, i64, fp, i64, fp, i64, fp, i64, i64, i64, fp, i64, fp, i64, fp, vp]
     for name in ("mm_alpharecursion_f32", "mm_betarecursion_f32", "mm_maxstateposteriors_f32"):

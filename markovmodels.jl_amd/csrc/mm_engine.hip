@@ -438,7 +438,7 @@ static Geometry pick_geometry(mm_batch_t h) {
 }
 
 // ---- one plan per entry that runs on the item form: its launch geometry and where its state vectors live
-enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter, Window, VitWindow, Weighted };
+enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter, Window, VitWindow, Weighted, Segment };
 struct ItemPlan {
     ItemEntry e;
     int NW, NI;        // waves per workgroup, register-resident items per wave of the instance (8 or 0)
@@ -449,8 +449,8 @@ struct ItemPlan {
 };
 // The only source of the above.  The vectors are global when the entry's LDS plan (the item kernel's, with the stage rows for
 // all but the export modes, + the arc kernel's extra; Cost: cost_lds_plan; Leaky: leaky_lds_plan; Entropy: entropy_lds_plan; Filter:
-// filter_lds_plan, no larger than the export modes'; Window: window_lds_plan, the arc kernel's size) does not fit 160 KB, when
-// MM_BIGV asks for it, or for the arc, sampling, cost, leaky, entropy, filter and window kernels when NI = 0: they have no
+// filter_lds_plan, no larger than the export modes'; Window and Segment: window_lds_plan, the arc kernel's size) does not fit 160 KB, when
+// MM_BIGV asks for it, or for the arc, sampling, cost, leaky, entropy, filter, window and segment kernels when NI = 0: they have no
 // streamed-only instance with the vectors in LDS.  VitWindow (tropical batches): the tropical kernel's geometry, its LDS plan + the
 // arc kernel's extra.  Weighted: the arc kernel's size + one row of state posteriors (mm_weighted_lds_bytes), 8 waves like Arcs.
 // `global` never depends on max_items, nor does NI except Tropical's (8: the whole graph is register-resident): mm_batch_create
@@ -463,19 +463,19 @@ static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
         if (e == ItemEntry::Leaky) return mm_leaky_lds_bytes(S1p, P1p);
         if (e == ItemEntry::Entropy) return mm_entropy_lds_bytes(S1p, P1p);
         if (e == ItemEntry::Filter) return mm_filter_lds_bytes(S1p, P1p);
-        if (e == ItemEntry::Window) return mm_window_lds_bytes(S1p, P1p);
+        if (e == ItemEntry::Window || e == ItemEntry::Segment) return mm_window_lds_bytes(S1p, P1p);
         if (e == ItemEntry::VitWindow) return mm_vitwindow_lds_bytes(S1p, P1p);
         if (e == ItemEntry::Weighted) return mm_weighted_lds_bytes(S1p, P1p);
         return e == ItemEntry::Cost ? mm_cost_lds_bytes(S1p, P1p) : size_t(lds_plan(S1p, P1p, e != ItemEntry::Export).total) * 4;
     };
     const bool derived = e == ItemEntry::Arcs || e == ItemEntry::Sample || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy ||
-                         e == ItemEntry::Filter || e == ItemEntry::Window || e == ItemEntry::Weighted;
+                         e == ItemEntry::Filter || e == ItemEntry::Window || e == ItemEntry::Weighted || e == ItemEntry::Segment;
     ItemPlan pl{e, g.NW, g.NI, false, false, 0};
     pl.global = bytes(h->max_S1p) + (e == ItemEntry::Arcs ? MM_ARC_LDS_EXTRA : 0) > lds_max || h->dbg.bigv || (derived && g.NI == 0);
     pl.lds_bytes = bytes(pl.global ? 0 : h->max_S1p);
     // (8 items' arcs and their sums / the pair arithmetic / the leak term and its sums per wave: compiled for 8 waves per CU)
     if (e == ItemEntry::Arcs || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy || e == ItemEntry::Filter ||
-        e == ItemEntry::Window || e == ItemEntry::Weighted)
+        e == ItemEntry::Window || e == ItemEntry::Weighted || e == ItemEntry::Segment)
         pl.NW = std::min(g.NW, 8);
     if (e == ItemEntry::Sample) pl.stage = !pl.global && !h->dbg.sample_nostage && size_t(h->max_S1p) * 8 <= lds_max;
     if (e == ItemEntry::Tropical || e == ItemEntry::VitWindow) {
@@ -2638,6 +2638,13 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
         s = "mm_weights_kernel (the call's weight planes, init vectors and descriptors; not launched when W and W_init are NULL) + mm_log_kernel<MODE_FB," + ni +
             ",1> (forward, on the call's descriptors) + mm_weighted_bwd_kernel<" + ni + "," + where_of(pl.global) +
             "> (backward: the arcs' sums by their owning lanes, gamma per pdf) + mm_weighted_scatter_kernel; state vectors " + (pl.global ? "in global memory" : "in LDS");
+    } else if (entry == 13) {  // mm_segmentposteriors_f32
+        if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_segmentposteriors_f32 runs on log-semiring batches only");
+        const ItemPlan pl = item_plan(h, ItemEntry::Segment);
+        const std::string inst = "<" + std::to_string(pl.NI) + "," + where_of(pl.global) + ">";
+        s = "mm_window_fwd_kernel" + inst + " (forward from the carried start vector: alpha~ stored) + mm_segment_bwd_kernel" + inst +
+            " (backward from an open, a closed or a carried end: gamma per pdf, ttl, then the item pass behind frame 1: end_out and lend); state vectors " +
+            (pl.global ? "in global memory" : "in LDS");
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -3075,7 +3082,7 @@ static int item_entry_begin(mm_batch_t h, const char *who, ItemEntry e, const fl
 }
 
 // Where they keep what they keep in h->ws for N frames: byte offsets, each aligned to 256 bytes.  The alpha~ store (at 0) and
-// the per-frame offsets as the item kernel keeps them (all that Leaky and Window keep); Arcs: the float64 sums of all backward slots, the state posteriors of
+// the per-frame offsets as the item kernel keeps them (all that Leaky, Window and Segment keep); Arcs: the float64 sums of all backward slots, the state posteriors of
 // frame 1; Cost: the r store and its offsets, and for FSMs beyond the LDS the state vectors of both kernels ([B][8 * max S1p]
 // floats); Entropy: as Cost, the Hf store in the place of the r store -- and no such store for a value-only call (`store` false).
 // total: no less than what mm_pdfposteriors_f32 needs for as many frames.  (mm_batch_reserve does not cover it.)  Filter keeps
@@ -3382,6 +3389,39 @@ int mm_windowposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t v
     wp.commit = commit;
     wp.lcommit = lcommit;
     return mm_launch_window(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, p, wp, static_cast<hipStream_t>(stream));
+}
+
+// ---- segment posteriors: the forward-backward of a segment with a carried start and a carried end (mm_kernel_segment.hip)
+int mm_segmentposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, const float *state_in,
+                             const int32_t *end_mode, const float *end_in, float *end_out, float *lend, float *gamma, int64_t gsb,
+                             int64_t gsn, int64_t gsp, float *ttl, void *stream) {
+    // what the arguments alone show comes first (without a batch: the frames' own extent), then the batch's refusals
+    if (!gamma) return fail(MM_ERR_INVALID, "mm_segmentposteriors_f32: gamma is NULL");
+    {
+        const int64_t B = h ? h->B : 1, P = h ? h->max_P1 - 1 : 1;
+        if (!strides_hold(gsb, B, gsn, N, gsp, P))
+            return fail(MM_ERR_DIM, "mm_segmentposteriors_f32: g strides (" + std::to_string(gsb) + ", " + std::to_string(gsn) + ", " + std::to_string(gsp) +
+                                        ") cannot hold " + std::to_string(B) + " x " + std::to_string(N) + " x " + std::to_string(P) + " elements");
+    }
+    ItemPlan pl;
+    int rc = item_entry_begin(h, "mm_segmentposteriors_f32", ItemEntry::Segment, V, N, stream, []() { return int(MM_OK); }, &pl);
+    if (rc) return rc;
+    const ItemWs W = item_ws_layout(h, pl, N);
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    rc = item_ws_bind(h, pl, W, p, stream);
+    if (rc) return rc;
+    p.gamma = gamma;
+    p.gsb = gsb;
+    p.gsn = gsn;
+    p.gsp = gsp;
+    p.ttl = ttl;
+    SegmentParams sp{};
+    sp.state_in = state_in;
+    sp.end_mode = end_mode;
+    sp.end_in = end_in;
+    sp.end_out = end_out;
+    sp.lend = lend;
+    return mm_launch_segment(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, p, sp, static_cast<hipStream_t>(stream));
 }
 
 // ---- posteriors with call-time arc weights (mm_kernel_weighted.hip)

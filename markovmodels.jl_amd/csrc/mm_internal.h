@@ -294,6 +294,19 @@ struct WindowParams {
 // (NULL: not asked for) go where RunParams says
 int mm_launch_window(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, const RunParams &p, const WindowParams &wp, hipStream_t stream);
 size_t mm_window_lds_bytes(int S1p, int P1p);
+// the forward kernel alone (what mm_launch_window launches first): the alpha~ store and the open / closed total in ws_c[0]
+int mm_launch_window_fwd(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, const RunParams &p, const WindowParams &wp, hipStream_t stream);
+
+// ---- segment posteriors (mm_segment_tu.hip: mm_window_fwd_kernel as it stands, then mm_segment_bwd_kernel on the item form)
+struct SegmentParams {
+    const float *state_in;  // as FilterParams::state_in; NULL: the FSMs' own initial vectors
+    const int *end_mode;    // [B] 0: open; 2 with end_in given: the carried end vector; else: the final weights.  NULL: every segment ends open
+    const float *end_in;    // layout of state_in, natural log: b_len of a carried end (the final state's entry is not read); NULL: none
+    float *end_out;         // as end_in (may be the same buffer): ln b_0 - lend; NULL: not asked for
+    float *lend;            // [B] ln max b_0; NULL: not asked for
+};
+// lds_bytes: the window entry's (window_lds_plan); gamma and ttl (NULL: not asked for) go where RunParams says
+int mm_launch_segment(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, const RunParams &p, const SegmentParams &sp, hipStream_t stream);
 
 // ---- windowed best paths (mm_vitwindow_tu.hip: mm_vitwindow_fwd_kernel, mm_vitwindow_trace_kernel on the item form; tropical batches)
 struct VitWindowParams {

@@ -665,6 +665,113 @@ class BatchedFSM:
         res = (gamma, ttl, lcommit) + ((so,) if so is not None else ())
         return tuple(t.cpu().numpy() for t in res) if as_numpy else res
 
+    def segmentposteriors(self, V, lens=None, state=None, end_mode=None, end=None, out=None, want_end=False):
+        """Segment posteriors (mm_segmentposteriors_f32): the forward-backward over a SEGMENT of the audio that starts from a carried
+        vector like a window and ends open, on the final weights or on a carried END vector -- ``(gamma[B, N, P], ttl[B], lend[B])``,
+        plus ``end_out[total_states]`` when ``want_end``.  ``state`` as for ``filterposteriors`` (None: the FSMs' own initial
+        vectors).  ``end_mode`` (int32 ``[B]``, None: all open): 0 -- open, beta = 1 on every real state at the last frame; 2 with
+        ``end`` given -- the segment ends on ``end`` (float32 ``[total_states]``, natural log, the layout of ``state``: the
+        ``end_out`` of the segment behind this one; the final states' entries are not read); anything else -- the final weights.
+        ``end_out`` = ln b_0 - ``lend``, ``lend`` = ln max b_0, b_0 the backward vector one step ahead of the segment's first
+        frame: what the segment BEFORE this one ends on.  Chaining is exact: with segment A ending on segment B's ``end_out``
+        (B started from the filter's state behind A's frames), A and B have on their frames the gamma of one call over both, and
+        ``ttl_A + lend_B`` is that call's ttl (``chunkedposteriors`` keeps that book).  ``want_end`` may also be the tensor that
+        receives the end vector -- ``end`` itself included: a workgroup reads its segment before it writes it.  ``out`` as for
+        ``pdfposteriors``.  Frames beyond the lengths are zeros; ``lens[b] = 0`` hands the end vector the segment was given back;
+        a segment without mass has gamma = 0, ttl = lend = -inf and ``end_out`` = -inf everywhere.  d ttl / d V = gamma.  Log
+        batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        if out is not None:
+            # the kernels write through raw pointers and strides: a wrong buffer is memory corruption, not an exception
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != Vt.device:
+                raise TypeError("out must be a float32 tensor on V's device")
+            if out.dim() != 3 or tuple(out.shape) != (B, N, P):
+                raise _lib.DimensionMismatch(-2, f"out must be [B={B}, N={N}, P={P}], got {tuple(out.shape)}")
+
+        def vector(x, name):
+            if x is None:
+                return None
+            t = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).cuda() if not isinstance(x, torch.Tensor) else x
+            if t.dtype != torch.float32 or t.device != Vt.device:
+                raise TypeError(f"{name} must be a float32 tensor on V's device")
+            if t.dim() != 1 or t.numel() != self.total_states or not t.is_contiguous():
+                raise _lib.DimensionMismatch(-2, f"{name} must be a contiguous [{self.total_states}] vector, got {tuple(t.shape)}")
+            return t
+
+        st, ei = vector(state, "state"), vector(end, "end")
+        em = None
+        if end_mode is not None:
+            em = end_mode.to(device=Vt.device, dtype=torch.int32) if isinstance(end_mode, torch.Tensor) else torch.as_tensor(np.asarray(end_mode, dtype=np.int32)).to(Vt.device)
+            if em.dim() != 1 or em.numel() != B:
+                raise _lib.DimensionMismatch(-2, f"end_mode must be a [{B}] vector, got {tuple(em.shape)}")
+            em = em.contiguous()
+        gamma = out if out is not None else torch.empty((B, N, P), dtype=torch.float32, device=Vt.device)
+        ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        lend = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        eo = None
+        if isinstance(want_end, torch.Tensor):
+            eo = vector(want_end, "the end buffer")
+        elif want_end:
+            eo = torch.empty(self.total_states, dtype=torch.float32, device=Vt.device)
+        check(lib.mm_segmentposteriors_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
+                                           lt.data_ptr() if lt is not None else None, N,
+                                           st.data_ptr() if st is not None else None, em.data_ptr() if em is not None else None,
+                                           ei.data_ptr() if ei is not None else None, eo.data_ptr() if eo is not None else None,
+                                           lend.data_ptr(), gamma.data_ptr(), gamma.stride(0), gamma.stride(1), gamma.stride(2),
+                                           ttl.data_ptr(), self._stream(torch)))
+        res = (gamma, ttl, lend) + ((eo,) if eo is not None else ())
+        return tuple(t.cpu().numpy() for t in res) if as_numpy else res
+
+    def chunkedposteriors(self, V, lens=None, chunk=1024, out=None):
+        """The exact smoothing posteriors of long recordings in the workspace of ONE chunk: ``(gamma[B, N, P], ttl[B])``, the gamma
+        and log Z of ``pdfposteriors`` (of ``windowposteriors`` closed), computed in two passes over chunks of ``chunk`` frames.
+        Pass 1 is ``filterposteriors(want_filt=False)`` per chunk -- no frame kept, no workspace --, which saves the start state of
+        every chunk (``K x total_states`` floats) and gives ttl by the filter's book, the sum of ``incr`` + the last state's final
+        entries.  Pass 2 is ``segmentposteriors`` over the chunks in reverse: chunk k runs ``lens_k = clamp(lens - k chunk, 0,
+        chunk)`` frames from its saved state and ends on the final weights where the utterance ends in it or before it
+        (``lens <= (k + 1) chunk``), else on the end vector chunk k + 1 handed back; a chunk wholly behind an utterance's end has
+        no frame and hands the final weights on.  gamma is written chunk by chunk into ``out``.  No call sees more than ``chunk``
+        frames, so the alpha~ store is that of ``chunk`` frames whatever N; ``chunk >= N`` is one segment call.  Launches on the
+        caller's stream only, no host synchronisation.  An utterance without an accepting path has gamma = 0 and ttl = -inf."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError("chunk must be at least one frame")
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != Vt.device:
+                raise TypeError("out must be a float32 tensor on V's device")
+            if out.dim() != 3 or tuple(out.shape) != (B, N, P):
+                raise _lib.DimensionMismatch(-2, f"out must be [B={B}, N={N}, P={P}], got {tuple(out.shape)}")
+        dev = Vt.device
+        gamma = out if out is not None else torch.empty((B, N, P), dtype=torch.float32, device=dev)
+        if lt is None:
+            lt = torch.full((B,), N, dtype=torch.int32, device=dev)
+        if chunk >= N:
+            _, ttl, _ = self.segmentposteriors(Vt, lt, end_mode=torch.ones(B, dtype=torch.int32, device=dev), out=gamma)
+            return (gamma.cpu().numpy(), ttl.cpu().numpy()) if as_numpy else (gamma, ttl)
+        K = (N + chunk - 1) // chunk
+        lens_k = [torch.clamp(lt - k * chunk, 0, chunk).to(torch.int32) for k in range(K)]
+        # pass 1: states[k] is the state behind chunk k, the start of chunk k + 1 (chunk 0 starts from the FSMs' own vectors)
+        states = torch.empty((K, self.total_states), dtype=torch.float32, device=dev)
+        loglik = torch.zeros(B, dtype=torch.float64, device=dev)
+        for k in range(K):
+            _, incr, _, _ = self.filterposteriors(Vt[:, k * chunk : (k + 1) * chunk], lens_k[k], state=states[k - 1] if k else None,
+                                                  want_state=states[k], want_filt=False)
+            loglik += incr.sum(dim=1, dtype=torch.float64)
+        final = self.__dict__.get("_final_entries")  # (uploaded once per batch and device: no copy from the host in later calls)
+        if final is None or final.device != dev:
+            final = self._final_entries = torch.as_tensor(self.state_offsets[1:] - 1, dtype=torch.int64, device=dev)
+        ttl = (loglik + states[K - 1][final].double()).float()
+        # pass 2: the end vector travels backwards in one buffer, read and written in place
+        endv = torch.empty(self.total_states, dtype=torch.float32, device=dev)
+        for k in range(K - 1, -1, -1):
+            mode = torch.where(lt <= (k + 1) * chunk, 1, 2).to(torch.int32)
+            self.segmentposteriors(Vt[:, k * chunk : (k + 1) * chunk], lens_k[k], state=states[k - 1] if k else None, end_mode=mode,
+                                   end=endv if k < K - 1 else None, out=gamma[:, k * chunk : (k + 1) * chunk], want_end=endv if k else False)
+        return (gamma.cpu().numpy(), ttl.cpu().numpy()) if as_numpy else (gamma, ttl)
+
     def maxstateposteriors(self, V, lens=None):
         """Max-marginals of the tropical semiring, (sum S1) x (N+1), computed on the device."""
         return self._export(lib.mm_maxstateposteriors_f32, V, lens)
@@ -749,11 +856,11 @@ class BatchedFSM:
         """The kernels the engine launches for this batch (informational): "log" = pdfposteriors, "tropical" = bestpath, "export" =
         alpharecursion / betarecursion, "arcs" = arcposteriors, "sample" = samplepaths, "cost" = expectedcost, "leaky" =
         leakyposteriors, "entropy" = pathentropy, "filter" = filterposteriors, "window" = windowposteriors,
-        "vitwindow" = viterbiwindow (tropical batches), "weighted" = weightedposteriors."""
+        "vitwindow" = viterbiwindow (tropical batches), "weighted" = weightedposteriors, "segment" = segmentposteriors."""
         import ctypes
 
         buf = ctypes.create_string_buffer(1024)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12}[semiring], buf, 1024))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13}[semiring], buf, 1024))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -1176,6 +1283,30 @@ def windowposteriors(fsm, Vhats, Chats=None, seqlengths=None, closed=None):
     Vh = [np.asarray(v.cpu() if hasattr(v, "cpu") else v) for v in Vhats]
     V, lens = _need_expanded(Vh, bf.semiring)
     g, ttl, _ = bf.windowposteriors(V, lens, closed=closed)
+    return np.ascontiguousarray(g.transpose(0, 2, 1)), ttl
+
+
+def chunkedposteriors(fsm, Vhats, Chats=None, seqlengths=None, chunk=1024):
+    """The exact smoothing posteriors in the workspace of one chunk -- see ``BatchedFSM.chunkedposteriors`` -- in ``pdfposteriors``'
+    call shape: ``fsm`` the rawunion of the batch with its state maps, or a BatchedFSM / CompiledFSM (log semiring, Float32);
+    V_hats what ``expand`` makes.  Returns (gamma[B, P, N] probabilities, ttl[B]): NumPy arrays for host inputs, device tensors for
+    float32 V_hats on the HIP device given with their ``seqlengths``."""
+    if not hasattr(Vhats, "dim"):  # (a generator is read once)
+        Vhats = list(Vhats)
+    bf = _as_batch(fsm, Chats)
+    Vd = _device_vhats(Vhats)
+    if Vd is not None and seqlengths is not None:
+        torch = _torch()
+        B, P1, N1 = Vd.shape
+        if B != bf.B:
+            raise _lib.DimensionMismatch(-2, f"{B} matrices V_hat for a batch of {bf.B} FSMs")
+        lens = torch.as_tensor(seqlengths, dtype=torch.int32, device=Vd.device)
+        g, ttl = bf.chunkedposteriors(Vd[:, : P1 - 1, : N1 - 1].transpose(1, 2).contiguous(), lens, chunk=chunk)
+        return g.transpose(1, 2), ttl
+    # (device V_hats without their lengths: to the host, as pdfposteriors moves them, where the phony row gives the lengths)
+    Vh = [np.asarray(v.cpu() if hasattr(v, "cpu") else v) for v in Vhats]
+    V, lens = _need_expanded(Vh, bf.semiring)
+    g, ttl = bf.chunkedposteriors(V, lens, chunk=chunk)
     return np.ascontiguousarray(g.transpose(0, 2, 1)), ttl
 
 
