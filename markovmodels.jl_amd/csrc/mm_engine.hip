@@ -3249,6 +3249,12 @@ static bool strides_hold(int64_t sb, int64_t B, int64_t sn, int64_t N, int64_t s
     }
     return true;
 }
+// the three strides of output `name` of entry `who` hold B x N x P elements, or MM_ERR_DIM with the message
+static int check_strides(const std::string &who, const char *name, int64_t sb, int64_t B, int64_t sn, int64_t N, int64_t sp, int64_t P) {
+    if (strides_hold(sb, B, sn, N, sp, P)) return MM_OK;
+    return fail(MM_ERR_DIM, who + ": " + name + " strides (" + std::to_string(sb) + ", " + std::to_string(sn) + ", " + std::to_string(sp) +
+                                ") cannot hold " + std::to_string(B) + " x " + std::to_string(N) + " x " + std::to_string(P) + " elements");
+}
 
 int mm_expectedcost_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, const float *cost,
                         int64_t csb, int64_t csn, float *risk, float *grad, float *gamma, int64_t gsb, int64_t gsn, int64_t gsp, float *ttl,
@@ -3258,9 +3264,7 @@ int mm_expectedcost_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, 
         if (!cost || !risk || !grad) return fail(MM_ERR_INVALID, "mm_expectedcost_f32: cost / risk / grad is NULL");
         const int64_t P = h->max_P1 - 1;
         if (csn < P) return fail(MM_ERR_DIM, "mm_expectedcost_f32: c_stride_n " + std::to_string(csn) + " < " + std::to_string(P) + " pdfs");
-        if (!strides_hold(gsb, h->B, gsn, N, gsp, P))
-            return fail(MM_ERR_DIM, "mm_expectedcost_f32: g strides (" + std::to_string(gsb) + ", " + std::to_string(gsn) + ", " + std::to_string(gsp) +
-                                        ") cannot hold " + std::to_string(h->B) + " x " + std::to_string(N) + " x " + std::to_string(P) + " elements");
+        if (const int rc = check_strides("mm_expectedcost_f32", "g", gsb, h->B, gsn, N, gsp, P)) return rc;
         return int(MM_OK);
     }, &pl);
     if (rc) return rc;
@@ -3297,9 +3301,10 @@ int mm_pathentropy_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, c
     int rc = item_entry_begin(h, "mm_pathentropy_f32", ItemEntry::Entropy, V, N, stream, [&]() {
         if (!entropy) return fail(MM_ERR_INVALID, "mm_pathentropy_f32: entropy is NULL");
         const int64_t P = h->max_P1 - 1;
-        if (backward && !strides_hold(gsb, h->B, gsn, N, gsp, P))
-            return fail(MM_ERR_DIM, "mm_pathentropy_f32: g strides (" + std::to_string(gsb) + ", " + std::to_string(gsn) + ", " + std::to_string(gsp) +
-                                        ") cannot hold " + std::to_string(h->B) + " x " + std::to_string(N) + " x " + std::to_string(P) + " elements");
+        if (backward) {
+            const int rc = check_strides("mm_pathentropy_f32", "g", gsb, h->B, gsn, N, gsp, P);
+            if (rc) return rc;
+        }
         return int(MM_OK);
     }, &pl);
     if (rc) return rc;
@@ -3334,9 +3339,10 @@ int mm_filterposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t v
     if (incr && isb < N) return fail(MM_ERR_DIM, "mm_filterposteriors_f32: i_stride_b " + std::to_string(isb) + " < " + std::to_string(N) + " frames");
     {
         const int64_t B = h ? h->B : 1, P = h ? h->max_P1 - 1 : 1;
-        if (filt && !strides_hold(fsb, B, fsn, N, fsp, P))
-            return fail(MM_ERR_DIM, "mm_filterposteriors_f32: f strides (" + std::to_string(fsb) + ", " + std::to_string(fsn) + ", " + std::to_string(fsp) +
-                                        ") cannot hold " + std::to_string(B) + " x " + std::to_string(N) + " x " + std::to_string(P) + " elements");
+        if (filt) {
+            const int rc = check_strides("mm_filterposteriors_f32", "f", fsb, B, fsn, N, fsp, P);
+            if (rc) return rc;
+        }
     }
     ItemPlan pl;
     int rc = item_entry_begin(h, "mm_filterposteriors_f32", ItemEntry::Filter, V, N, stream, []() { return int(MM_OK); }, &pl);
@@ -3366,9 +3372,7 @@ int mm_windowposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t v
     if (!gamma) return fail(MM_ERR_INVALID, "mm_windowposteriors_f32: gamma is NULL");
     {
         const int64_t B = h ? h->B : 1, P = h ? h->max_P1 - 1 : 1;
-        if (!strides_hold(gsb, B, gsn, N, gsp, P))
-            return fail(MM_ERR_DIM, "mm_windowposteriors_f32: g strides (" + std::to_string(gsb) + ", " + std::to_string(gsn) + ", " + std::to_string(gsp) +
-                                        ") cannot hold " + std::to_string(B) + " x " + std::to_string(N) + " x " + std::to_string(P) + " elements");
+        if (const int rc = check_strides("mm_windowposteriors_f32", "g", gsb, B, gsn, N, gsp, P)) return rc;
     }
     ItemPlan pl;
     int rc = item_entry_begin(h, "mm_windowposteriors_f32", ItemEntry::Window, V, N, stream, []() { return int(MM_OK); }, &pl);
@@ -3399,9 +3403,7 @@ int mm_segmentposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t 
     if (!gamma) return fail(MM_ERR_INVALID, "mm_segmentposteriors_f32: gamma is NULL");
     {
         const int64_t B = h ? h->B : 1, P = h ? h->max_P1 - 1 : 1;
-        if (!strides_hold(gsb, B, gsn, N, gsp, P))
-            return fail(MM_ERR_DIM, "mm_segmentposteriors_f32: g strides (" + std::to_string(gsb) + ", " + std::to_string(gsn) + ", " + std::to_string(gsp) +
-                                        ") cannot hold " + std::to_string(B) + " x " + std::to_string(N) + " x " + std::to_string(P) + " elements");
+        if (const int rc = check_strides("mm_segmentposteriors_f32", "g", gsb, B, gsn, N, gsp, P)) return rc;
     }
     ItemPlan pl;
     int rc = item_entry_begin(h, "mm_segmentposteriors_f32", ItemEntry::Segment, V, N, stream, []() { return int(MM_OK); }, &pl);
@@ -3512,9 +3514,7 @@ int mm_weightedposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t
         return fail(MM_ERR_DIM, std::string(who) + ": w_stride_b " + std::to_string(wsb) + " / wi_stride_b " + std::to_string(wisb) + " is negative");
     if (gamma) {
         const int64_t B = h ? h->B : 1, P = h ? h->max_P1 - 1 : 1;
-        if (!strides_hold(gsb, B, gsn, N, gsp, P))
-            return fail(MM_ERR_DIM, std::string(who) + ": g strides (" + std::to_string(gsb) + ", " + std::to_string(gsn) + ", " + std::to_string(gsp) +
-                                        ") cannot hold " + std::to_string(B) + " x " + std::to_string(N) + " x " + std::to_string(P) + " elements");
+        if (const int rc = check_strides(who, "g", gsb, B, gsn, N, gsp, P)) return rc;
     }
     if (h && h->semiring == MM_LOG) {  // (the batch's own numbers need no device either)
         bool same = true;
@@ -3616,9 +3616,7 @@ int mm_leakyposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vs
         if (!gamma || !ttl) return fail(MM_ERR_INVALID, "mm_leakyposteriors_f32: gamma / ttl is NULL");
         if (!(leak >= 0.f) || !std::isfinite(leak)) return fail(MM_ERR_INVALID, "mm_leakyposteriors_f32: the leak coefficient must be finite and >= 0");
         const int64_t P = h->max_P1 - 1;
-        if (!strides_hold(gsb, h->B, gsn, N, gsp, P))
-            return fail(MM_ERR_DIM, "mm_leakyposteriors_f32: g strides (" + std::to_string(gsb) + ", " + std::to_string(gsn) + ", " + std::to_string(gsp) +
-                                        ") cannot hold " + std::to_string(h->B) + " x " + std::to_string(N) + " x " + std::to_string(P) + " elements");
+        if (const int rc = check_strides("mm_leakyposteriors_f32", "g", gsb, h->B, gsn, N, gsp, P)) return rc;
         return int(MM_OK);
     }, &pl);
     if (rc) return rc;

@@ -8,18 +8,15 @@ namespace mm {
 
 size_t mm_entropy_lds_bytes(int S1p, int P1p) { return size_t(entropy_lds_plan(S1p, P1p).total) * 4; }
 
-template <int NI, bool BIGV>
-static int launch_entropy_ni(int64_t B, int NW, size_t lds, bool backward, const RunParams &p, const EntropyParams &ep, hipStream_t stream) {
-    const int rc = mm_launch(mm_entropy_fwd_kernel<NI, BIGV>, dim3(unsigned(B)), dim3(64 * NW), lds, stream, p, ep);
-    return rc || !backward ? rc : mm_launch(mm_entropy_bwd_kernel<NI, BIGV>, dim3(unsigned(B)), dim3(64 * NW), lds, stream, p, ep);
-}
-
 int mm_launch_entropy(int64_t B, int NW, int NI, bool bigv, size_t lds, bool backward, const RunParams &p, const EntropyParams &ep,
                       hipStream_t stream) {
-    if (NI == 8)
-        return bigv ? launch_entropy_ni<8, true>(B, NW, lds, backward, p, ep, stream) : launch_entropy_ni<8, false>(B, NW, lds, backward, p, ep, stream);
-    if (NI == 0 && bigv) return launch_entropy_ni<0, true>(B, NW, lds, backward, p, ep, stream);
-    return mm_fail(MM_ERR_UNSUPPORTED, "path entropy: no instance for this geometry");
+    const dim3 grid{unsigned(B)}, block{unsigned(64 * NW)};
+    return item_instance("path entropy", NI, bigv, [&](auto I) {
+        constexpr int NI_ = decltype(I)::NI;
+        constexpr bool BIGV = decltype(I)::BIGV;
+        const int rc = mm_launch(mm_entropy_fwd_kernel<NI_, BIGV>, grid, block, lds, stream, p, ep);
+        return rc || !backward ? rc : mm_launch(mm_entropy_bwd_kernel<NI_, BIGV>, grid, block, lds, stream, p, ep);
+    });
 }
 
 }  // namespace mm

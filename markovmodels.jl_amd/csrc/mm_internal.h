@@ -39,6 +39,21 @@ static int mm_launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_byt
     return MM_OK;
 }
 
+// The instances of an item-form entry's kernels: NI = 8 register-resident items per wave with the state vectors in LDS or in global
+// memory (bigv), NI = 0 (FSMs of more than 65534 states) with global vectors only.  f(ItemInstance<NI, BIGV>{}) launches the
+// entry's kernels of the instance; no instance: MM_ERR_UNSUPPORTED in the entry's name.
+template <int NI_, bool BIGV_>
+struct ItemInstance {
+    static constexpr int NI = NI_;
+    static constexpr bool BIGV = BIGV_;
+};
+template <class F>
+static int item_instance(const char *entry, int NI, bool bigv, F &&f) {
+    if (NI == 8) return bigv ? f(ItemInstance<8, true>{}) : f(ItemInstance<8, false>{});
+    if (NI == 0 && bigv) return f(ItemInstance<0, true>{});
+    return mm_fail(MM_ERR_UNSUPPORTED, std::string(entry) + ": no instance for this geometry");
+}
+
 #define MM_ROW_RS 8192  // LDS bytes of one copy of the linear vector (row kernels) / half a pair vector (pair kernels)
 #define MM_PAIR_KA 44   // arc slots per lane of the pair kernels
 // pdfs (+ 1) of the pair / split pair / float64 pair kernels: passes of 64 lanes of their service waves (the NJ of the instances),

@@ -14,7 +14,7 @@
 // the counts in the caller's entry order, adds the phony self-loop's N - len_b frames, and writes ttl = log Z.
 #pragma once
 #include "mm_internal.h"
-#include "mm_kernels.hip"
+#include "mm_item_parts.hip"
 
 namespace mm {
 
@@ -23,28 +23,12 @@ namespace mm {
 template <int NI, bool BIGV>
 __global__ void __launch_bounds__(512) mm_arc_kernel(RunParams p, ArcParams ap) {
     extern __shared__ float lds[];
-    const int b = blockIdx.x;
-    const UttDesc &u = p.utts[b];
-    const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), NW = NT >> 6;
-    const int S1p = u.S1p, P1 = u.P1, P = P1 - 1, P1p = (P1 + 3) & ~3;
-    const int fstate = u.S1 - 1;
-    int len = p.lens ? p.lens[b] : p.N;
-    len = len < 0 ? 0 : (len > p.N ? p.N : len);
-    const int NF = len + 1;
+    MM_ITEM_PROLOGUE(BIGV);
     const LdsPlan L = lds_plan(BIGV ? 0 : S1p, P1p, true);
     float *em = lds + L.em, *part = lds + L.part;
     float *psum = lds + L.total;  // [2][MM_MAX_WAVES] the waves' sums of the state posteriors of a frame (LDS behind the plan)
     float *buf = BIGV ? p.ws_big + (long long)b * p.big_stride : lds + L.buf;
     float *stage = BIGV ? buf + 2 * S1p : lds + L.stage;
-    auto vsync = [&]() {
-        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __syncthreads();
-        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    };
-    const float *Vb = p.V + (long long)b * p.vsb;
-    const float *wsA = p.ws_alpha + u.s1p_prefix * (long long)(p.N + 1);
-    const double *wsC = p.ws_c + (long long)b * (p.N + 2);
     const GraphDev gb = u.g[1];
     double *acc = ap.acc + ap.arcs[b].slot_off;
     float *post1 = ap.post1 + u.s1p_prefix;
@@ -52,15 +36,11 @@ __global__ void __launch_bounds__(512) mm_arc_kernel(RunParams p, ArcParams ap) 
     if (!(logZ2 > -1e300) || len < 1) return;  // no accepting path, or no frame: mm_arc_scatter_kernel writes what is known
 
     for (int q = tid; q < 2 * S1p; q += NT) buf[q] = MM_NINF;
-    for (int s = tid; s < u.S1; s += NT) post1[s] = 0.f;  // (rows without arcs have no item)
+    for (int s = tid; s < S1; s += NT) post1[s] = 0.f;  // (rows without arcs have no item)
     vsync();
     if (tid == 0) buf[(NF & 1) * S1p + fstate] = 0.f;
     stage_em(em + (len & 1) * P1p, Vb, p.vsn, len, len, P, tid, NT, MM_LOG2E);
-    {
-        const float4 *src = reinterpret_cast<const float4 *>(wsA + (long long)len * S1p);
-        float4 *dst = reinterpret_cast<float4 *>(stage + (len & 1) * S1p);
-        for (int q = tid; q < (S1p >> 2); q += NT) dst[q] = src[q];
-    }
+    copy_row(stage + (len & 1) * S1p, wsA + (long long)len * S1p, S1p >> 2, tid, NT);
     vsync();
     ItemRegs<NI> rg;
     load_item_regs<NI>(rg, gb, wave, NW, lane);
@@ -89,7 +69,7 @@ __global__ void __launch_bounds__(512) mm_arc_kernel(RunParams p, ArcParams ap) 
         const float M = (n == len) ? 0.f : part_max_dpp(part + ((n + 1) & 1) * MM_MAX_WAVES, NW, lane);
         D += (double)M;
         if (n < len) {
-            float s = 0.f;
+            float s = 0.f;  // (not part_sum: the waves' sums are added one after the other, and these are the bits the counts carry)
             for (int w = 0; w < NW; ++w) s += psum[((n + 1) & 1) * MM_MAX_WAVES + w];
             if (s > 0.f) corr += fast_log2(s);
         }
@@ -98,17 +78,8 @@ __global__ void __launch_bounds__(512) mm_arc_kernel(RunParams p, ArcParams ap) 
         const float kappa = (float)(logZ2 - Cn - D + (double)corr);
         const float sh = -M - kappa;  // arc term of slot k of row i: 2^(alpha~_n[i] + sh + x_k), x_k = w_k + y_{n+1}[col_k]
         if (n - 1 >= 1) {  // frame n-1 into the buffers frame n+1 has left (as mm_log_kernel's PASS 2)
-            if (tid <= P) em[((n - 1) & 1) * P1p + tid] = em_value(evp, n - 1, len, P, tid);
-            if (P >= NT) stage_em(em + ((n - 1) & 1) * P1p + NT, Vb + NT, p.vsn, n - 1, len, P - NT, tid, NT, MM_LOG2E);
-            const float4 *src = reinterpret_cast<const float4 *>(wsA + (long long)(n - 1) * S1p);
-            if constexpr (BIGV) {
-                float4 *dst = reinterpret_cast<float4 *>(stage + ((n - 1) & 1) * S1p);
-                for (int q = tid; q < n4; q += NT) dst[q] = src[q];
-            } else {
-                const unsigned dst = lds_addr_of(stage + ((n - 1) & 1) * S1p);
-                for (int q0 = wave * 64; q0 < n4; q0 += NT)
-                    if (q0 + lane < n4) dma_b128(src + q0 + lane, dst + 16u * (unsigned)q0);
-            }
+            stage_em_ahead<em_value>(em + ((n - 1) & 1) * P1p, evp, Vb, p.vsn, n - 1, len, P, tid, NT, MM_LOG2E);
+            stage_row<BIGV>(stage + ((n - 1) & 1) * S1p, wsA + (long long)(n - 1) * S1p, n4, tid, NT, wave, lane);
             Cn = Cpre;
             if (n - 2 >= 1) prefetch(n - 2);
         }
@@ -196,7 +167,7 @@ __global__ void __launch_bounds__(512) mm_arc_kernel(RunParams p, ArcParams ap) 
         part_put(part + (n & 1) * MM_MAX_WAVES, wave, lane, wm);
         qs = wave_sum(qs);
         if (lane == 0) psum[(n & 1) * MM_MAX_WAVES + wave] = qs;
-        if constexpr (!BIGV) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's part of alpha~ of frame n - 1 is in LDS
+        stage_row_wait<BIGV>();  // this wave's part of alpha~ of frame n - 1 is in LDS
         vsync();
     }
 }

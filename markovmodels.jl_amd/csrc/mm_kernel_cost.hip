@@ -28,7 +28,7 @@
 // every sum it enters and carries r' = t' = 0 (0 / 0 := 0), so a finite cost never meets an infinity.
 #pragma once
 #include "mm_internal.h"
-#include "mm_kernels.hip"
+#include "mm_item_parts.hip"
 
 namespace mm {
 
@@ -61,15 +61,9 @@ __device__ __forceinline__ void stage_cost(float *dst, const float *Cb, long lon
     for (int q = tid; q <= P; q += NT) dst[q] = (q < P && n <= len) ? Cb[(long long)(n - 1) * csn + q] : 0.f;
 }
 
-// the sum over the first 16 lanes (a wave's per-wave partials, lane < NW), the same bits in every wave
-__device__ __forceinline__ float part_sum16(const float *part, int NW, int lane) {
-    float v = (lane < NW) ? part[lane] : 0.f;
-    v = grp_sum(v, 4);
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
 // mean = (sum of weight x value) / (sum of weights) of the frame whose partials are at ps; 0 where no weight is left
 __device__ __forceinline__ float frame_mean(const float *ps, int NW, int lane) {
-    const float sw = part_sum16(ps, NW, lane), swv = part_sum16(ps + MM_MAX_WAVES, NW, lane);
+    const float sw = part_sum(ps, NW, lane), swv = part_sum(ps + MM_MAX_WAVES, NW, lane);
     const float m = swv * __builtin_amdgcn_rcpf(sw);
     return (sw > 0.f && fabsf(m) < 1e30f) ? m : 0.f;
 }
@@ -180,39 +174,20 @@ __device__ __forceinline__ void for_items_pair(const ItemRegs<NI> &rg, const Gra
     }
 }
 
-#define MM_COST_PROLOGUE                                                                                          \
-    extern __shared__ float4 cost_lds4[];                                                                         \
-    float *lds = reinterpret_cast<float *>(cost_lds4);                                                            \
-    const int b = blockIdx.x;                                                                                     \
-    const UttDesc &u = p.utts[b];                                                                                 \
-    const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63;                                                \
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), NW = NT >> 6;                                      \
-    const int S1 = u.S1, S1p = u.S1p, P1 = u.P1, P = P1 - 1, P1p = (P1 + 3) & ~3;                                 \
-    const int fstate = S1 - 1;                                                                                    \
-    int len = p.lens ? p.lens[b] : p.N;                                                                           \
-    len = len < 0 ? 0 : (len > p.N ? p.N : len);                                                                  \
-    const int NF = len + 1;                                                                                       \
-    const CostLds L = cost_lds_plan(BIGV ? 0 : S1p, P1p);                                                         \
-    float *em = lds + L.em, *cs = lds + L.cs, *part = lds + L.part, *psum = lds + L.psum;                         \
-    float *big = BIGV ? cp.ws_big + (long long)b * cp.big_stride : nullptr;                                       \
-    float2 *buf = reinterpret_cast<float2 *>(BIGV ? big : lds + L.buf);                                           \
-    auto vsync = [&]() {                                                                                          \
-        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");                                    \
-        __syncthreads();                                                                                          \
-        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                                    \
-    };                                                                                                            \
-    const float *Vb = p.V + (long long)b * p.vsb;                                                                 \
-    const float *Cb = cp.cost + (long long)b * cp.csb;                                                            \
-    float *wsA = p.ws_alpha + u.s1p_prefix * (long long)(p.N + 1);                                                \
-    float *wsR = cp.ws_r + u.s1p_prefix * (long long)(p.N + 1);                                                   \
-    double *wsC = p.ws_c + (long long)b * (p.N + 2);                                                              \
-    double *wsO = cp.ws_o + (long long)b * (p.N + 2)
-
 // forward: alpha~ rows, C_n, log2 Z (wsC[0]) as the item kernel's forward half, the r' rows, O_n, risk (wsO[0]).
 // grid = B workgroups (one utterance each), block = 64 * NW threads, NW <= 8.
 template <int NI, bool BIGV>
 __global__ void __launch_bounds__(512) mm_cost_fwd_kernel(RunParams p, CostParams cp) {
-    MM_COST_PROLOGUE;
+    extern __shared__ float4 cost_lds4[];
+    float *lds = reinterpret_cast<float *>(cost_lds4);
+    MM_ITEM_PROLOGUE(BIGV);
+    const CostLds L = cost_lds_plan(BIGV ? 0 : S1p, P1p);
+    float *em = lds + L.em, *cs = lds + L.cs, *part = lds + L.part, *psum = lds + L.psum;
+    float *big = BIGV ? cp.ws_big + (long long)b * cp.big_stride : nullptr;
+    float2 *buf = reinterpret_cast<float2 *>(BIGV ? big : lds + L.buf);
+    const float *Cb = cp.cost + (long long)b * cp.csb;
+    float *wsR = cp.ws_r + u.s1p_prefix * (long long)(p.N + 1);
+    double *wsO = cp.ws_o + (long long)b * (p.N + 2);
     stage_em(em + 1 * P1p, Vb, p.vsn, 1, len, P, tid, NT, MM_LOG2E);
     stage_cost(cs + 1 * P1p, Cb, cp.csn, 1, len, P, tid, NT);
     for (int q = tid; q < 2 * S1p; q += NT) buf[q] = make_float2(MM_NINF, 0.f);
@@ -264,14 +239,9 @@ __global__ void __launch_bounds__(512) mm_cost_fwd_kernel(RunParams p, CostParam
             wsO[n] = O;
         }
         if (n + 1 <= NF) {
-            if (tid <= P) {
-                em[((n + 1) & 1) * P1p + tid] = em_value(evp, n + 1, len, P, tid);
-                cs[((n + 1) & 1) * P1p + tid] = cost_value(cvp, n + 1, len, P, tid);
-            }
-            if (P >= NT) {
-                stage_em(em + ((n + 1) & 1) * P1p + NT, Vb + NT, p.vsn, n + 1, len, P - NT, tid, NT, MM_LOG2E);
-                stage_cost(cs + ((n + 1) & 1) * P1p + NT, Cb + NT, cp.csn, n + 1, len, P - NT, tid, NT);
-            }
+            stage_em_ahead<em_value>(em + ((n + 1) & 1) * P1p, evp, Vb, p.vsn, n + 1, len, P, tid, NT, MM_LOG2E);
+            if (tid <= P) cs[((n + 1) & 1) * P1p + tid] = cost_value(cvp, n + 1, len, P, tid);
+            if (P >= NT) stage_cost(cs + ((n + 1) & 1) * P1p + NT, Cb + NT, cp.csn, n + 1, len, P - NT, tid, NT);
         }
         evp = em_load_raw(Vb, p.vsn, n + 2, p.N, P, tid);
         cvp = cost_load_raw(Cb, cp.csn, n + 2, len, P, tid);
@@ -309,8 +279,16 @@ __global__ void __launch_bounds__(512) mm_cost_fwd_kernel(RunParams p, CostParam
 // backward: gamma, grad, risk, ttl.  Same grid and block as the forward kernel.
 template <int NI, bool BIGV>
 __global__ void __launch_bounds__(512) mm_cost_bwd_kernel(RunParams p, CostParams cp) {
-    MM_COST_PROLOGUE;
-    (void)wsR;
+    extern __shared__ float4 cost_lds4[];
+    float *lds = reinterpret_cast<float *>(cost_lds4);
+    MM_ITEM_PROLOGUE(BIGV);
+    const CostLds L = cost_lds_plan(BIGV ? 0 : S1p, P1p);
+    float *em = lds + L.em, *cs = lds + L.cs, *part = lds + L.part, *psum = lds + L.psum;
+    float *big = BIGV ? cp.ws_big + (long long)b * cp.big_stride : nullptr;
+    float2 *buf = reinterpret_cast<float2 *>(BIGV ? big : lds + L.buf);
+    const float *Cb = cp.cost + (long long)b * cp.csb;
+    float *wsR = cp.ws_r + u.s1p_prefix * (long long)(p.N + 1);
+    double *wsO = cp.ws_o + (long long)b * (p.N + 2);
     float *bins = lds + L.bins, *gbins = lds + L.gbins;
     float *sta = BIGV ? big + 4 * S1p : lds + L.sta;
     float *str = BIGV ? big + 6 * S1p : lds + L.str;
@@ -324,6 +302,7 @@ __global__ void __launch_bounds__(512) mm_cost_bwd_kernel(RunParams p, CostParam
     }
     // frames without a result: all of them without an accepting path, else those beyond the length
     const int z0 = ok ? len : 0;
+    // (not zero_gamma_from: two outputs on one walk, its 64-bit index arithmetic once)
     for (long long q = tid; q < (long long)(p.N - z0) * P; q += NT) {
         const long long o = gbase + (z0 + q / P) * cp.gsn + (q % P) * cp.gsp;
         cp.grad[o] = 0.f;
@@ -336,15 +315,7 @@ __global__ void __launch_bounds__(512) mm_cost_bwd_kernel(RunParams p, CostParam
     if (tid == 0) buf[(NF & 1) * S1p + fstate] = make_float2(0.f, 0.f);  // frame len + 1: the final state alone, nothing to come
     stage_em(em + (len & 1) * P1p, Vb, p.vsn, len, len, P, tid, NT, MM_LOG2E);
     stage_cost(cs + (len & 1) * P1p, Cb, cp.csn, len, len, P, tid, NT);
-    {
-        const float4 *sa = reinterpret_cast<const float4 *>(wsA + (long long)len * S1p);
-        const float4 *sr = reinterpret_cast<const float4 *>(wsR + (long long)len * S1p);
-        float4 *da = reinterpret_cast<float4 *>(sta + (len & 1) * S1p), *dr = reinterpret_cast<float4 *>(str + (len & 1) * S1p);
-        for (int q = tid; q < (S1p >> 2); q += NT) {
-            da[q] = sa[q];
-            dr[q] = sr[q];
-        }
-    }
+    copy_row_pair(sta + (len & 1) * S1p, wsA + (long long)len * S1p, str + (len & 1) * S1p, wsR + (long long)len * S1p, S1p >> 2, tid, NT);
     vsync();
     ItemRegs<NI> rg;
     load_item_regs<NI>(rg, gb, wave, NW, lane);
@@ -358,7 +329,7 @@ __global__ void __launch_bounds__(512) mm_cost_bwd_kernel(RunParams p, CostParam
         Cpre = wsC[f];
         Opre = wsO[f];
     };
-    // gamma and grad of frame f from its per-pdf sums (one wave)
+    // gamma and grad of frame f from its per-pdf sums (one wave).  Not finalise_gamma: two sums per pdf, the second with the frame's mean taken out
     auto finalise = [&](int f) {
         const float *bf = bins + (f & 1) * P1p, *gf = gbins + (f & 1) * P1p;
         float s = 0.f, gs = 0.f;
@@ -395,30 +366,11 @@ __global__ void __launch_bounds__(512) mm_cost_bwd_kernel(RunParams p, CostParam
         const float off = (float)(On + Q - risk);  // E[A | s_n = j] - risk = r'_n(j) + s'_n(j) + off
         if (n < len && wave == NW - 1) finalise(n + 1);
         if (n - 1 >= 1) {  // frame n - 1 into the buffers frame n + 1 has left (as mm_log_kernel's PASS 2)
-            if (tid <= P) {
-                em[((n - 1) & 1) * P1p + tid] = em_value(evp, n - 1, len, P, tid);
-                cs[((n - 1) & 1) * P1p + tid] = cost_value(cvp, n - 1, len, P, tid);
-            }
-            if (P >= NT) {
-                stage_em(em + ((n - 1) & 1) * P1p + NT, Vb + NT, p.vsn, n - 1, len, P - NT, tid, NT, MM_LOG2E);
-                stage_cost(cs + ((n - 1) & 1) * P1p + NT, Cb + NT, cp.csn, n - 1, len, P - NT, tid, NT);
-            }
-            const float4 *sa = reinterpret_cast<const float4 *>(wsA + (long long)(n - 1) * S1p);
-            const float4 *sr = reinterpret_cast<const float4 *>(wsR + (long long)(n - 1) * S1p);
-            if constexpr (BIGV) {
-                float4 *da = reinterpret_cast<float4 *>(sta + ((n - 1) & 1) * S1p), *dr = reinterpret_cast<float4 *>(str + ((n - 1) & 1) * S1p);
-                for (int q = tid; q < n4; q += NT) {
-                    da[q] = sa[q];
-                    dr[q] = sr[q];
-                }
-            } else {
-                const unsigned da = lds_addr_of(sta + ((n - 1) & 1) * S1p), dr = lds_addr_of(str + ((n - 1) & 1) * S1p);
-                for (int q0 = wave * 64; q0 < n4; q0 += NT)
-                    if (q0 + lane < n4) {
-                        dma_b128(sa + q0 + lane, da + 16u * (unsigned)q0);
-                        dma_b128(sr + q0 + lane, dr + 16u * (unsigned)q0);
-                    }
-            }
+            stage_em_ahead<em_value>(em + ((n - 1) & 1) * P1p, evp, Vb, p.vsn, n - 1, len, P, tid, NT, MM_LOG2E);
+            if (tid <= P) cs[((n - 1) & 1) * P1p + tid] = cost_value(cvp, n - 1, len, P, tid);
+            if (P >= NT) stage_cost(cs + ((n - 1) & 1) * P1p + NT, Cb + NT, cp.csn, n - 1, len, P - NT, tid, NT);
+            stage_row_pair<BIGV>(sta + ((n - 1) & 1) * S1p, wsA + (long long)(n - 1) * S1p, str + ((n - 1) & 1) * S1p,
+                                 wsR + (long long)(n - 1) * S1p, n4, tid, NT, wave, lane);
             Cn = Cpre;
             On = Opre;
             if (n - 2 >= 1) prefetch(n - 2);
@@ -439,29 +391,15 @@ __global__ void __launch_bounds__(512) mm_cost_bwd_kernel(RunParams p, CostParam
         });
         part_put(part + (n & 1) * MM_MAX_WAVES, wave, lane, wm);
         frame_mean_put(psum + (n & 1) * 2 * MM_MAX_WAVES, wave, lane, sq, sqt);
-        if constexpr (!BIGV) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's part of frame n - 1 is in LDS
+        stage_row_wait<BIGV>();  // this wave's part of frame n - 1 is in LDS
         vsync();
         // per pdf, over the pdf's states in pdf_rows: 8 lanes add the two products in a fixed order, a 3-step DPP reduction ends
         // it (mm_log_kernel's deterministic mode).  The second barrier also guards the staging buffers.
-        float *bn = bins + (n & 1) * P1p, *gn = gbins + (n & 1) * P1p;
-        for (int p0 = wave * 8; p0 < P1; p0 += NW * 8) {
-            const int pdf = p0 + (lane >> 3);
-            float sacc = 0.f, gacc = 0.f;
-            if (pdf < P1) {
-                const int e0 = u.pdf_ptr[pdf], e1 = u.pdf_ptr[pdf + 1];
-                for (int k = e0 + (lane & 7); k < e1; k += 8) {
-                    const int row = u.pdf_rows[k];
-                    sacc += ast[row];
-                    gacc += rst[row];
-                }
-            }
-            sacc = grp_sum(sacc, 3);
-            gacc = grp_sum(gacc, 3);
-            if (pdf < P1 && (lane & 7) == 0) {
-                bn[pdf] = sacc;
-                gn[pdf] = gacc;
-            }
-        }
+        for_pdf_rows<2>(u, P1, wave, NW, lane, {bins + (n & 1) * P1p, gbins + (n & 1) * P1p}, [](int) { return 0; },
+                        [&](int row, int, float(&acc)[2]) {
+                            acc[0] += ast[row];
+                            acc[1] += rst[row];
+                        });
         vsync();
     }
     if (wave == 0) finalise(1);

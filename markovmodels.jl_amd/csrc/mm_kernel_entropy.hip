@@ -31,8 +31,8 @@
 // exponent the row leader exponentiates for q anyway.
 #pragma once
 #include "mm_internal.h"
-#include "mm_kernels.hip"
-#include "mm_kernel_cost.hip"  // part_sum16, frame_mean, frame_mean_put: the frame means behind the offsets (no kernel of it is instantiated here)
+#include "mm_item_parts.hip"
+#include "mm_kernel_cost.hip"  // frame_mean, frame_mean_put: the frame means behind the offsets (no kernel of it is instantiated here)
 
 namespace mm {
 
@@ -165,39 +165,38 @@ __device__ __forceinline__ void for_items_entropy(const ItemRegs<NI> &rg, const 
     }
 }
 
-#define MM_ENTROPY_PROLOGUE                                                                                       \
-    extern __shared__ float4 entropy_lds4[];                                                                      \
-    float *lds = reinterpret_cast<float *>(entropy_lds4);                                                         \
-    const int b = blockIdx.x;                                                                                     \
-    const UttDesc &u = p.utts[b];                                                                                 \
-    const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63;                                                \
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), NW = NT >> 6;                                      \
-    const int S1 = u.S1, S1p = u.S1p, P1 = u.P1, P = P1 - 1, P1p = (P1 + 3) & ~3;                                 \
-    const int fstate = S1 - 1;                                                                                    \
-    int len = p.lens ? p.lens[b] : p.N;                                                                           \
-    len = len < 0 ? 0 : (len > p.N ? p.N : len);                                                                  \
-    const int NF = len + 1;                                                                                       \
-    const EntropyLds L = entropy_lds_plan(BIGV ? 0 : S1p, P1p);                                                   \
-    float *em = lds + L.em, *part = lds + L.part, *psum = lds + L.psum;                                           \
-    float *big = BIGV ? ep.ws_big + (long long)b * ep.big_stride : nullptr;                                       \
-    float2 *buf = reinterpret_cast<float2 *>(BIGV ? big : lds + L.buf);                                           \
-    auto vsync = [&]() {                                                                                          \
-        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");                                    \
-        __syncthreads();                                                                                          \
-        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                                    \
-    };                                                                                                            \
-    const float *Vb = p.V + (long long)b * p.vsb;                                                                 \
-    float *wsA = p.ws_alpha + u.s1p_prefix * (long long)(p.N + 1);                                                \
-    float *wsH = ep.ws_h ? ep.ws_h + u.s1p_prefix * (long long)(p.N + 1) : nullptr;                               \
-    double *wsC = p.ws_c + (long long)b * (p.N + 2);                                                              \
-    double *wsO = ep.ws_o + (long long)b * (p.N + 2)
-
 // forward: log2 Z (wsC[0]) and H (wsO[0]), entropy and ttl; with a store to fill (ep.ws_h) also the alpha~ rows and C_n as the
 // item kernel's forward half leaves them, the Hf' rows and O_n.
 // grid = B workgroups (one utterance each), block = 64 * NW threads, NW <= 8.
+// (Written out, prologue included, none of the parts of mm_item_parts.hip: the value-only call is this kernel alone, and moved onto the
+// parts it measured 0.5 - 1.3 % slower.)
 template <int NI, bool BIGV>
 __global__ void __launch_bounds__(512) mm_entropy_fwd_kernel(RunParams p, EntropyParams ep) {
-    MM_ENTROPY_PROLOGUE;
+    extern __shared__ float4 entropy_lds4[];
+    float *lds = reinterpret_cast<float *>(entropy_lds4);
+    const int b = blockIdx.x;
+    const UttDesc &u = p.utts[b];
+    const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), NW = NT >> 6;
+    const int S1 = u.S1, S1p = u.S1p, P1 = u.P1, P = P1 - 1, P1p = (P1 + 3) & ~3;
+    const int fstate = S1 - 1;
+    int len = p.lens ? p.lens[b] : p.N;
+    len = len < 0 ? 0 : (len > p.N ? p.N : len);
+    const int NF = len + 1;
+    const EntropyLds L = entropy_lds_plan(BIGV ? 0 : S1p, P1p);
+    float *em = lds + L.em, *part = lds + L.part, *psum = lds + L.psum;
+    float *big = BIGV ? ep.ws_big + (long long)b * ep.big_stride : nullptr;
+    float2 *buf = reinterpret_cast<float2 *>(BIGV ? big : lds + L.buf);
+    auto vsync = [&]() {
+        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        __syncthreads();
+        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    };
+    const float *Vb = p.V + (long long)b * p.vsb;
+    float *wsA = p.ws_alpha + u.s1p_prefix * (long long)(p.N + 1);
+    float *wsH = ep.ws_h ? ep.ws_h + u.s1p_prefix * (long long)(p.N + 1) : nullptr;
+    double *wsC = p.ws_c + (long long)b * (p.N + 2);
+    double *wsO = ep.ws_o + (long long)b * (p.N + 2);
     const bool store = wsH != nullptr;  // (uniform: a value-only call keeps no frame)
     stage_em(em + 1 * P1p, Vb, p.vsn, 1, len, P, tid, NT, MM_LOG2E);
     for (int q = tid; q < 2 * S1p; q += NT) buf[q] = make_float2(MM_NINF, 0.f);
@@ -282,7 +281,15 @@ __global__ void __launch_bounds__(512) mm_entropy_fwd_kernel(RunParams p, Entrop
 // backward: gamma and grad (either may be NULL).  Same grid and block as the forward kernel.
 template <int NI, bool BIGV>
 __global__ void __launch_bounds__(512) mm_entropy_bwd_kernel(RunParams p, EntropyParams ep) {
-    MM_ENTROPY_PROLOGUE;
+    extern __shared__ float4 entropy_lds4[];
+    float *lds = reinterpret_cast<float *>(entropy_lds4);
+    MM_ITEM_PROLOGUE(BIGV);
+    const EntropyLds L = entropy_lds_plan(BIGV ? 0 : S1p, P1p);
+    float *em = lds + L.em, *part = lds + L.part, *psum = lds + L.psum;
+    float *big = BIGV ? ep.ws_big + (long long)b * ep.big_stride : nullptr;
+    float2 *buf = reinterpret_cast<float2 *>(BIGV ? big : lds + L.buf);
+    float *wsH = ep.ws_h ? ep.ws_h + u.s1p_prefix * (long long)(p.N + 1) : nullptr;
+    double *wsO = ep.ws_o + (long long)b * (p.N + 2);
     float *bins = lds + L.bins, *gbins = lds + L.gbins;
     float *sta = BIGV ? big + 4 * S1p : lds + L.sta;
     float *str = BIGV ? big + 6 * S1p : lds + L.str;
@@ -292,6 +299,7 @@ __global__ void __launch_bounds__(512) mm_entropy_bwd_kernel(RunParams p, Entrop
     const bool ok = logZ2 > -1e300;
     // frames without a result: all of them without an accepting path, else those beyond the length
     const int z0 = ok ? len : 0;
+    // (not zero_gamma_from: two outputs on one walk, its 64-bit index arithmetic once)
     for (long long q = tid; q < (long long)(p.N - z0) * P; q += NT) {
         const long long o = gbase + (z0 + q / P) * ep.gsn + (q % P) * ep.gsp;
         if (ep.grad) ep.grad[o] = 0.f;
@@ -303,15 +311,7 @@ __global__ void __launch_bounds__(512) mm_entropy_bwd_kernel(RunParams p, Entrop
     vsync();
     if (tid == 0) buf[(NF & 1) * S1p + fstate] = make_float2(0.f, 0.f);  // frame len + 1: the final state alone, no suffix
     stage_em(em + (len & 1) * P1p, Vb, p.vsn, len, len, P, tid, NT, MM_LOG2E);
-    {
-        const float4 *sa = reinterpret_cast<const float4 *>(wsA + (long long)len * S1p);
-        const float4 *sh = reinterpret_cast<const float4 *>(wsH + (long long)len * S1p);
-        float4 *da = reinterpret_cast<float4 *>(sta + (len & 1) * S1p), *dh = reinterpret_cast<float4 *>(str + (len & 1) * S1p);
-        for (int q = tid; q < (S1p >> 2); q += NT) {
-            da[q] = sa[q];
-            dh[q] = sh[q];
-        }
-    }
+    copy_row_pair(sta + (len & 1) * S1p, wsA + (long long)len * S1p, str + (len & 1) * S1p, wsH + (long long)len * S1p, S1p >> 2, tid, NT);
     vsync();
     ItemRegs<NI> rg;
     load_item_regs<NI>(rg, gb, wave, NW, lane);
@@ -324,7 +324,7 @@ __global__ void __launch_bounds__(512) mm_entropy_bwd_kernel(RunParams p, Entrop
         Cpre = wsC[f];
         Opre = wsO[f];
     };
-    // gamma and grad of frame f from its per-pdf sums (one wave)
+    // gamma and grad of frame f from its per-pdf sums (one wave).  Not finalise_gamma: two sums per pdf, the second with the frame's mean taken out
     auto finalise = [&](int f) {
         const float *bf = bins + (f & 1) * P1p, *gf = gbins + (f & 1) * P1p;
         float s = 0.f, gs = 0.f;
@@ -361,24 +361,9 @@ __global__ void __launch_bounds__(512) mm_entropy_bwd_kernel(RunParams p, Entrop
         const float off = (float)(On + Q - H);  // Hf_n(j) + Hb_n(j) - H = Hf'_n(j) + Hb'_n(j) + off
         if (n < len && wave == NW - 1) finalise(n + 1);
         if (n - 1 >= 1) {  // frame n - 1 into the buffers frame n + 1 has left (as mm_log_kernel's PASS 2)
-            if (tid <= P) em[((n - 1) & 1) * P1p + tid] = em_value(evp, n - 1, len, P, tid);
-            if (P >= NT) stage_em(em + ((n - 1) & 1) * P1p + NT, Vb + NT, p.vsn, n - 1, len, P - NT, tid, NT, MM_LOG2E);
-            const float4 *sa = reinterpret_cast<const float4 *>(wsA + (long long)(n - 1) * S1p);
-            const float4 *sh = reinterpret_cast<const float4 *>(wsH + (long long)(n - 1) * S1p);
-            if constexpr (BIGV) {
-                float4 *da = reinterpret_cast<float4 *>(sta + ((n - 1) & 1) * S1p), *dh = reinterpret_cast<float4 *>(str + ((n - 1) & 1) * S1p);
-                for (int q = tid; q < n4; q += NT) {
-                    da[q] = sa[q];
-                    dh[q] = sh[q];
-                }
-            } else {
-                const unsigned da = lds_addr_of(sta + ((n - 1) & 1) * S1p), dh = lds_addr_of(str + ((n - 1) & 1) * S1p);
-                for (int q0 = wave * 64; q0 < n4; q0 += NT)
-                    if (q0 + lane < n4) {
-                        dma_b128(sa + q0 + lane, da + 16u * (unsigned)q0);
-                        dma_b128(sh + q0 + lane, dh + 16u * (unsigned)q0);
-                    }
-            }
+            stage_em_ahead<em_value>(em + ((n - 1) & 1) * P1p, evp, Vb, p.vsn, n - 1, len, P, tid, NT, MM_LOG2E);
+            stage_row_pair<BIGV>(sta + ((n - 1) & 1) * S1p, wsA + (long long)(n - 1) * S1p, str + ((n - 1) & 1) * S1p,
+                                 wsH + (long long)(n - 1) * S1p, n4, tid, NT, wave, lane);
             Cn = Cpre;
             On = Opre;
             if (n - 2 >= 1) prefetch(n - 2);
@@ -399,29 +384,15 @@ __global__ void __launch_bounds__(512) mm_entropy_bwd_kernel(RunParams p, Entrop
         });
         part_put(part + (n & 1) * MM_MAX_WAVES, wave, lane, wm);
         frame_mean_put(psum + (n & 1) * 2 * MM_MAX_WAVES, wave, lane, sq, sqh);
-        if constexpr (!BIGV) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's part of frame n - 1 is in LDS
+        stage_row_wait<BIGV>();  // this wave's part of frame n - 1 is in LDS
         vsync();
         // per pdf, over the pdf's states in pdf_rows: 8 lanes add the two products in a fixed order, a 3-step DPP reduction ends
         // it (mm_log_kernel's deterministic mode).  The second barrier also guards the staging buffers.
-        float *bn = bins + (n & 1) * P1p, *gn = gbins + (n & 1) * P1p;
-        for (int p0 = wave * 8; p0 < P1; p0 += NW * 8) {
-            const int pdf = p0 + (lane >> 3);
-            float sacc = 0.f, gacc = 0.f;
-            if (pdf < P1) {
-                const int e0 = u.pdf_ptr[pdf], e1 = u.pdf_ptr[pdf + 1];
-                for (int k = e0 + (lane & 7); k < e1; k += 8) {
-                    const int row = u.pdf_rows[k];
-                    sacc += ast[row];
-                    gacc += hst[row];
-                }
-            }
-            sacc = grp_sum(sacc, 3);
-            gacc = grp_sum(gacc, 3);
-            if (pdf < P1 && (lane & 7) == 0) {
-                bn[pdf] = sacc;
-                gn[pdf] = gacc;
-            }
-        }
+        for_pdf_rows<2>(u, P1, wave, NW, lane, {bins + (n & 1) * P1p, gbins + (n & 1) * P1p}, [](int) { return 0; },
+                        [&](int row, int, float(&acc)[2]) {
+                            acc[0] += ast[row];
+                            acc[1] += hst[row];
+                        });
         vsync();
     }
     if (wave == 0) finalise(1);

@@ -26,7 +26,7 @@
 // from there on, state_out = -inf, ttl = -inf; nothing is divided by it.
 #pragma once
 #include "mm_internal.h"
-#include "mm_kernels.hip"
+#include "mm_item_parts.hip"
 
 namespace mm {
 
@@ -45,49 +45,21 @@ __host__ __device__ inline FilterLds filter_lds_plan(int S1p, int P1p) {
     return l;
 }
 
-// the largest emission of the real pdfs of a staged frame (0 for a frame without one), the same bits in every wave
-__device__ __forceinline__ float filter_emax(const float *emn, int P, int lane) {
-    float m = MM_NINF;
-    for (int q = lane; q < P; q += 64) m = fmaxf(m, emn[q]);
-    m = wave_max_rl(m);
-    return (m > MM_NINF) ? m : 0.f;
-}
-// a frame's emissions as the kernel stages them: natural log, unscaled (stage_em with scale 1, em_value without its scaling)
-__device__ __forceinline__ float filter_em_value(float raw, int n, int len, int P, int q) {
-    if (q < P) return (n <= len) ? raw : MM_NINF;
-    return (n <= len) ? MM_NINF : 0.f;
-}
-
 // grid = B workgroups (one utterance each), block = 64 * NW threads, NW <= 8.
 template <int NI, bool BIGV>
 __global__ void __launch_bounds__(512) mm_filter_kernel(RunParams p, FilterParams fp) {
     extern __shared__ float4 filter_lds4[];
     float *lds = reinterpret_cast<float *>(filter_lds4);
-    const int b = blockIdx.x;
-    const UttDesc &u = p.utts[b];
-    const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), NW = NT >> 6;
-    const int S1 = u.S1, S1p = u.S1p, P1 = u.P1, P = P1 - 1, P1p = (P1 + 3) & ~3;
-    const int fstate = S1 - 1;
-    int len = p.lens ? p.lens[b] : p.N;
-    len = len < 0 ? 0 : (len > p.N ? p.N : len);
-    const int NF = len + 1;
+    MM_ITEM_PROLOGUE(BIGV);
     const FilterLds L = filter_lds_plan(BIGV ? 0 : S1p, P1p);
     float *em = lds + L.em, *part = lds + L.part, *bins = lds + L.bins, *fin = lds + L.fin;
     float *buf = BIGV ? p.ws_big + (long long)b * p.big_stride : lds + L.buf;
-    auto vsync = [&]() {
-        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __syncthreads();
-        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    };
-    const float *Vb = p.V + (long long)b * p.vsb;
     const float *sin = fp.state_in ? fp.state_in + u.state_off : nullptr;
     float *sout = fp.state_out ? fp.state_out + u.state_off : nullptr;
     float *fb = fp.filt ? fp.filt + (long long)b * fp.fsb : nullptr;
     float *ib = fp.incr ? fp.incr + (long long)b * fp.isb : nullptr;
     // the frames beyond len: exact zeros
-    if (fb)
-        for (long long q = tid; q < (long long)(p.N - len) * P; q += NT) fb[(len + q / P) * fp.fsn + (q % P) * fp.fsp] = 0.f;
+    if (fb) zero_gamma_from(fb, fp.fsn, fp.fsp, len, p.N, P, tid, NT);
     if (ib)
         for (int q = len + tid; q < p.N; q += NT) ib[q] = 0.f;
     if (len == 0) {  // nothing to filter: the state passes through (NULL in: ln alpha_hat, the vector NULL stands for)
@@ -107,7 +79,7 @@ __global__ void __launch_bounds__(512) mm_filter_kernel(RunParams p, FilterParam
         float wm = MM_NINF;
         float *a1 = buf + 1 * S1p;
         const float *e1 = em + 1 * P1p;
-        Ec = filter_emax(e1, P, lane);
+        Ec = frame_emax(e1, P, lane);
         for (int s = tid; s < S1; s += NT) {
             const float st = sin ? (s < fstate ? sin[s] * MM_LOG2E : MM_NINF) : u.init[s];
             const float v = st + (e1[u.s2p[s]] - Ec) * MM_LOG2E;
@@ -126,6 +98,7 @@ __global__ void __launch_bounds__(512) mm_filter_kernel(RunParams p, FilterParam
     float M = 0.f, Mp = 0.f;     // the maxima of the step and of the step before: frame n - 1's and frame n - 2's own
     float ltp = 0.f;             // (finishing wave) log2 tot of the frame finished last; l_0 = 0
     bool alive = true;           // (finishing wave) no frame so far without a live state
+    // (not finalise_gamma: a frame without mass ends every frame behind it, and the sum also gives incr)
     // frame f from its per-pdf sums (one wave): Mf = the maximum of a~_f, what the sums were taken relative to
     auto finalise = [&](int f, float Mf, float Ef) {
         const float *bf = bins + (f & 1) * P1p;
@@ -152,28 +125,14 @@ __global__ void __launch_bounds__(512) mm_filter_kernel(RunParams p, FilterParam
         M = part_max_dpp(part + ((n - 1) & 1) * MM_MAX_WAVES, NW, lane);
         E2 = E1;
         E1 = Ec;
-        Ec = filter_emax(emn, P, lane);  // (the last step: no real emission, 0)
+        Ec = frame_emax(emn, P, lane);  // (the last step: no real emission, 0)
         C += (double)M + (double)Ec * 1.4426950408889634;
         if (n >= 3 && wave == NW - 1) finalise(n - 2, Mp, E2);
-        if (n + 1 <= NF) {
-            if (tid <= P) em[((n + 1) & 1) * P1p + tid] = filter_em_value(evp, n + 1, len, P, tid);
-            if (P >= NT) stage_em(em + ((n + 1) & 1) * P1p + NT, Vb + NT, p.vsn, n + 1, len, P - NT, tid, NT, 1.f);
-        }
+        if (n + 1 <= NF) stage_em_ahead<em_value_nat>(em + ((n + 1) & 1) * P1p, evp, Vb, p.vsn, n + 1, len, P, tid, NT, 1.f);
         evp = em_load_raw(Vb, p.vsn, n + 2, p.N, P, tid);
-        {   // frame n - 1 per pdf, over the pdf's states in pdf_rows (the phony pdf's list holds the final state alone: -inf up
-            // to frame len, left out)
-            float *bn = bins + ((n - 1) & 1) * P1p;
-            for (int p0 = wave * 8; p0 < P; p0 += NW * 8) {
-                const int pdf = p0 + (lane >> 3);
-                float sacc = 0.f;
-                if (pdf < P) {
-                    const int e0 = u.pdf_ptr[pdf], e1 = u.pdf_ptr[pdf + 1];
-                    for (int k = e0 + (lane & 7); k < e1; k += 8) sacc += fast_exp2(ap[u.pdf_rows[k]] - M);
-                }
-                sacc = grp_sum(sacc, 3);
-                if (pdf < P && (lane & 7) == 0) bn[pdf] = sacc;
-            }
-        }
+        // frame n - 1 per pdf, over the pdf's states (the phony pdf's list holds the final state alone: -inf up to frame len, left out)
+        for_pdf_rows<1>(u, P, wave, NW, lane, {bins + ((n - 1) & 1) * P1p}, [](int) { return 0; },
+                        [&](int row, int, float(&acc)[1]) { acc[0] += fast_exp2(ap[row] - M); });
         float wm = MM_NINF;
         const bool last = n == NF;
         for_items<NI>(rg, gf, wave, NW, lane, ap, emn, [&](float v, int row, int, float e) {

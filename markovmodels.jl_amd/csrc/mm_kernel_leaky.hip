@@ -27,7 +27,7 @@
 // loses its leak: the result there is the unleaked one, never a NaN.
 #pragma once
 #include "mm_internal.h"
-#include "mm_kernels.hip"
+#include "mm_item_parts.hip"
 
 namespace mm {
 
@@ -50,22 +50,10 @@ __host__ __device__ inline LeakLds leaky_lds_plan(int S1p, int P1p) {
     return l;
 }
 
-// the sum of the waves' partial sums (lane < NW <= 16), the same bits in every wave
-__device__ __forceinline__ float leak_part_sum(const float *ps, int NW, int lane) {
-    float v = (lane < NW) ? ps[lane] : 0.f;
-    v = grp_sum(v, 4);
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
+// a wave's partial sum where part_sum reads it
 __device__ __forceinline__ void leak_part_put(float *ps, int wave, int lane, float s) {
     s = wave_sum(s);
     if (lane == 0) ps[wave] = s;
-}
-// the largest emission of the real pdfs of a staged frame (0 for a frame without one), the same bits in every wave
-__device__ __forceinline__ float frame_emax(const float *emn, int P, int lane) {
-    float m = MM_NINF;
-    for (int q = lane; q < P; q += 64) m = fmaxf(m, emn[q]);
-    m = wave_max_rl(m);
-    return (m > MM_NINF) ? m : 0.f;
 }
 __device__ __forceinline__ float logaddexp2(float a, float b) {
     const float m = fmaxf(a, b);
@@ -129,35 +117,16 @@ __device__ __forceinline__ void for_items_leak(const ItemRegs<NI> &rg, const Gra
     }
 }
 
-#define MM_LEAKY_PROLOGUE                                                                                         \
-    extern __shared__ float4 leaky_lds4[];                                                                        \
-    float *lds = reinterpret_cast<float *>(leaky_lds4);                                                           \
-    const int b = blockIdx.x;                                                                                     \
-    const UttDesc &u = p.utts[b];                                                                                 \
-    const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63;                                                \
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), NW = NT >> 6;                                      \
-    const int S1 = u.S1, S1p = u.S1p, P1 = u.P1, P = P1 - 1, P1p = (P1 + 3) & ~3;                                 \
-    const int fstate = S1 - 1;                                                                                    \
-    int len = p.lens ? p.lens[b] : p.N;                                                                           \
-    len = len < 0 ? 0 : (len > p.N ? p.N : len);                                                                  \
-    const int NF = len + 1;                                                                                       \
-    const LeakLds L = leaky_lds_plan(BIGV ? 0 : S1p, P1p);                                                        \
-    float *em = lds + L.em, *part = lds + L.part, *psum = lds + L.psum;                                           \
-    float *buf = BIGV ? p.ws_big + (long long)b * p.big_stride : lds + L.buf;                                     \
-    auto vsync = [&]() {                                                                                          \
-        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");                                    \
-        __syncthreads();                                                                                          \
-        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                                    \
-    };                                                                                                            \
-    const float *Vb = p.V + (long long)b * p.vsb;                                                                 \
-    float *wsA = p.ws_alpha + u.s1p_prefix * (long long)(p.N + 1);                                                \
-    double *wsC = p.ws_c + (long long)b * (p.N + 2)
-
 // forward: alpha~ rows, C_n and log2 Z (wsC[0]) in the workspace, laid out as the item kernel's forward half leaves them.
 // grid = B workgroups (one utterance each), block = 64 * NW threads, NW <= 8.
 template <int NI, bool BIGV>
 __global__ void __launch_bounds__(512) mm_leaky_fwd_kernel(RunParams p, LeakParams lp) {
-    MM_LEAKY_PROLOGUE;
+    extern __shared__ float4 leaky_lds4[];
+    float *lds = reinterpret_cast<float *>(leaky_lds4);
+    MM_ITEM_PROLOGUE(BIGV);
+    const LeakLds L = leaky_lds_plan(BIGV ? 0 : S1p, P1p);
+    float *em = lds + L.em, *part = lds + L.part, *psum = lds + L.psum;
+    float *buf = BIGV ? p.ws_big + (long long)b * p.big_stride : lds + L.buf;
     const float *rho = stage_rowc<BIGV>(lds + L.rowc, lp.rows[b].rho, S1, tid, NT);
     stage_em(em + 1 * P1p, Vb, p.vsn, 1, len, P, tid, NT, MM_LOG2E);
     for (int q = tid; q < 2 * S1p; q += NT) buf[q] = MM_NINF;
@@ -194,21 +163,14 @@ __global__ void __launch_bounds__(512) mm_leaky_fwd_kernel(RunParams p, LeakPara
         const float *emn = em + (n & 1) * P1p;
         const float M = part_max_dpp(part + ((n - 1) & 1) * MM_MAX_WAVES, NW, lane);
         // log2 (eps tot_{n-1}) in the normalisation of alpha~_{n-1}.  (The final state is in the sum: it is -inf up to frame len.)
-        const float add = lp.leps2 + fast_log2(leak_part_sum(psum + ((n - 1) & 1) * MM_MAX_WAVES, NW, lane)) - (MM_LEAK_BIAS - eprev);
+        const float add = lp.leps2 + fast_log2(part_sum(psum + ((n - 1) & 1) * MM_MAX_WAVES, NW, lane)) - (MM_LEAK_BIAS - eprev);
         eprev = frame_emax(emn, P, lane);
         const float sb = MM_LEAK_BIAS - eprev;
         C += (double)M;
         if (tid == 0) wsC[n] = C;
-        if (n + 1 <= NF) {
-            if (tid <= P) em[((n + 1) & 1) * P1p + tid] = em_value(evp, n + 1, len, P, tid);
-            if (P >= NT) stage_em(em + ((n + 1) & 1) * P1p + NT, Vb + NT, p.vsn, n + 1, len, P - NT, tid, NT, MM_LOG2E);
-        }
+        if (n + 1 <= NF) stage_em_ahead<em_value>(em + ((n + 1) & 1) * P1p, evp, Vb, p.vsn, n + 1, len, P, tid, NT, MM_LOG2E);
         evp = em_load_raw(Vb, p.vsn, n + 2, p.N, P, tid);
-        {   // frame n - 1 leaves the chip once (coalesced), while frame n is computed
-            float4 *dst = reinterpret_cast<float4 *>(wsA + (long long)(n - 1) * S1p);
-            const float4 *src = reinterpret_cast<const float4 *>(ap);
-            for (int q = tid; q < (S1p >> 2); q += NT) dst[q] = src[q];
-        }
+        copy_row(wsA + (long long)(n - 1) * S1p, ap, S1p >> 2, tid, NT);  // frame n - 1 leaves the chip once, while frame n is computed
         float wm = MM_NINF, sw = 0.f;
         for_items_leak<NI, true>(rg, gf, rho, add, wave, NW, lane, ap, emn, [&](float v, float, int row, int, float e) {
             v = v + e - M;
@@ -226,14 +188,19 @@ __global__ void __launch_bounds__(512) mm_leaky_fwd_kernel(RunParams p, LeakPara
 // backward: gamma and ttl.  Same grid and block as the forward kernel.
 template <int NI, bool BIGV>
 __global__ void __launch_bounds__(512) mm_leaky_bwd_kernel(RunParams p, LeakParams lp) {
-    MM_LEAKY_PROLOGUE;
+    extern __shared__ float4 leaky_lds4[];
+    float *lds = reinterpret_cast<float *>(leaky_lds4);
+    MM_ITEM_PROLOGUE(BIGV);
+    const LeakLds L = leaky_lds_plan(BIGV ? 0 : S1p, P1p);
+    float *em = lds + L.em, *part = lds + L.part, *psum = lds + L.psum;
+    float *buf = BIGV ? p.ws_big + (long long)b * p.big_stride : lds + L.buf;
     float *bins = lds + L.bins;
     float *stage = BIGV ? buf + 2 * S1p : lds + L.stage;
     const GraphDev gb = u.g[1];
     const double logZ2 = wsC[0];
-    const long long gbase = (long long)b * p.gsb;
+    float *gam = p.gamma + (long long)b * p.gsb;
     if (!(logZ2 > -1e300)) {  // no path even with the leak: gamma = 0, ttl = -inf
-        for (long long q = tid; q < (long long)p.N * P; q += NT) p.gamma[gbase + (q / P) * p.gsn + (q % P) * p.gsp] = 0.f;
+        zero_gamma_from(gam, p.gsn, p.gsp, 0, p.N, P, tid, NT);
         if (tid == 0) p.ttl[b] = MM_NINF;
         return;
     }
@@ -243,11 +210,7 @@ __global__ void __launch_bounds__(512) mm_leaky_bwd_kernel(RunParams p, LeakPara
     vsync();
     if (tid == 0) buf[(NF & 1) * S1p + fstate] = 0.f;  // frame len + 1: the final state alone
     stage_em(em + (len & 1) * P1p, Vb, p.vsn, len, len, P, tid, NT, MM_LOG2E);
-    {
-        const float4 *src = reinterpret_cast<const float4 *>(wsA + (long long)len * S1p);
-        float4 *dst = reinterpret_cast<float4 *>(stage + (len & 1) * S1p);
-        for (int q = tid; q < (S1p >> 2); q += NT) dst[q] = src[q];
-    }
+    copy_row(stage + (len & 1) * S1p, wsA + (long long)len * S1p, S1p >> 2, tid, NT);
     vsync();
     ItemRegs<NI> rg;
     load_item_regs<NI>(rg, gb, wave, NW, lane);
@@ -260,14 +223,15 @@ __global__ void __launch_bounds__(512) mm_leaky_bwd_kernel(RunParams p, LeakPara
         evp = em_load_raw(Vb, p.vsn, f, p.N, P, tid);
         Cpre = wsC[f];
     };
-    // gamma of frame f from its per-pdf sums (one wave)
+    // gamma of frame f from its per-pdf sums (one wave).  Not finalise_gamma: the phony pdf's bin is in the sum, which the leak keeps
+    // positive (no guard), and the sum also gives the frame's ttl
     auto finalise = [&](int f) {
         const float *bf = bins + (f & 1) * P1p;
         float s = 0.f;
         for (int q = lane; q < P1; q += 64) s += bf[q];
         s = wave_sum(s);
         const float inv = 1.f / s;
-        float *gp = p.gamma + gbase + (long long)(f - 1) * p.gsn;
+        float *gp = gam + (long long)(f - 1) * p.gsn;
         for (int q = lane; q < P; q += 64) gp[q * p.gsp] = bf[q] * inv;
         tmin = fminf(tmin, (float)(logZ2 + (double)fast_log2(s)));
     };
@@ -282,17 +246,8 @@ __global__ void __launch_bounds__(512) mm_leaky_bwd_kernel(RunParams p, LeakPara
         const float kappa = (float)(logZ2 - Cn - D);
         if (n < len && wave == NW - 1) finalise(n + 1);
         if (n - 1 >= 1) {  // frame n - 1 into the buffers frame n + 1 has left (as mm_log_kernel's PASS 2)
-            if (tid <= P) em[((n - 1) & 1) * P1p + tid] = em_value(evp, n - 1, len, P, tid);
-            if (P >= NT) stage_em(em + ((n - 1) & 1) * P1p + NT, Vb + NT, p.vsn, n - 1, len, P - NT, tid, NT, MM_LOG2E);
-            const float4 *src = reinterpret_cast<const float4 *>(wsA + (long long)(n - 1) * S1p);
-            if constexpr (BIGV) {
-                float4 *dst = reinterpret_cast<float4 *>(stage + ((n - 1) & 1) * S1p);
-                for (int q = tid; q < n4; q += NT) dst[q] = src[q];
-            } else {
-                const unsigned dst = lds_addr_of(stage + ((n - 1) & 1) * S1p);
-                for (int q0 = wave * 64; q0 < n4; q0 += NT)
-                    if (q0 + lane < n4) dma_b128(src + q0 + lane, dst + 16u * (unsigned)q0);
-            }
+            stage_em_ahead<em_value>(em + ((n - 1) & 1) * P1p, evp, Vb, p.vsn, n - 1, len, P, tid, NT, MM_LOG2E);
+            stage_row<BIGV>(stage + ((n - 1) & 1) * S1p, wsA + (long long)(n - 1) * S1p, n4, tid, NT, wave, lane);
             Cn = Cpre;
             if (n - 2 >= 1) prefetch(n - 2);
         }
@@ -304,39 +259,27 @@ __global__ void __launch_bounds__(512) mm_leaky_bwd_kernel(RunParams p, LeakPara
             cw += fast_exp2(pik + z + MM_LEAK_BIAS);
         });
         leak_part_put(psum, wave, lane, cw);
-        if constexpr (!BIGV) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's part of alpha~ of frame n - 1 is in LDS
+        stage_row_wait<BIGV>();  // this wave's part of alpha~ of frame n - 1 is in LDS
         vsync();
         // Per pdf, over the pdf's states in pdf_rows (every state is in one list; the phony pdf's holds the final state, which does
         // not leak): beta_n = z_n (+) eps c_n, the posterior, y_n = beta_n + e over z_n, the frame's maximum; 8 lanes add a pdf's
         // posteriors in a fixed order, a 3-step DPP reduction ends it.  The second barrier also guards the staging buffers.
-        const float lc = lp.leps2 + fast_log2(leak_part_sum(psum, NW, lane)) - MM_LEAK_BIAS;
-        float *bn = bins + (n & 1) * P1p;
+        const float lc = lp.leps2 + fast_log2(part_sum(psum, NW, lane)) - MM_LEAK_BIAS;
         float wm = MM_NINF;
-        for (int p0 = wave * 8; p0 < P1; p0 += NW * 8) {
-            const int pdf = p0 + (lane >> 3);
-            float sacc = 0.f;
-            if (pdf < P1) {
-                const float e = emn[pdf];
-                const float lcp = pdf < P ? lc : MM_NINF;
-                const int e0 = u.pdf_ptr[pdf], e1 = u.pdf_ptr[pdf + 1];
-                for (int k = e0 + (lane & 7); k < e1; k += 8) {
-                    const int row = u.pdf_rows[k];
-                    const float beta = logaddexp2(yn[row], lcp);
-                    sacc += fast_exp2(ast[row] + beta - kappa);
-                    const float y = beta + e;
-                    yn[row] = y;
-                    wm = fmaxf(wm, y);
-                }
-            }
-            sacc = grp_sum(sacc, 3);
-            if (pdf < P1 && (lane & 7) == 0) bn[pdf] = sacc;
-        }
+        for_pdf_rows<1>(u, P1, wave, NW, lane, {bins + (n & 1) * P1p}, [&](int pdf) { return make_float2(emn[pdf], pdf < P ? lc : MM_NINF); },
+                        [&](int row, float2 c, float(&acc)[1]) {
+                            const float beta = logaddexp2(yn[row], c.y);
+                            acc[0] += fast_exp2(ast[row] + beta - kappa);
+                            const float y = beta + c.x;
+                            yn[row] = y;
+                            wm = fmaxf(wm, y);
+                        });
         part_put(part + (n & 1) * MM_MAX_WAVES, wave, lane, wm);
         vsync();
     }
     if (wave == 0) finalise(1);
     // zero the frames beyond len, reduce ttl
-    for (long long q = tid; q < (long long)(p.N - len) * P; q += NT) p.gamma[gbase + (len + q / P) * p.gsn + (q % P) * p.gsp] = 0.f;
+    zero_gamma_from(gam, p.gsn, p.gsp, len, p.N, P, tid, NT);
     vsync();  // part[] is free again
     if (lane == 0) part[wave] = tmin;
     vsync();

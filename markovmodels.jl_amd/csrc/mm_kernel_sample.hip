@@ -21,7 +21,7 @@
 // are computed 64 at a time, a frame and a chain per lane).  Results leave through vector stores, the paths 64 frames at a time.
 #pragma once
 #include "mm_internal.h"
-#include "mm_kernels.hip"
+#include "mm_item_parts.hip"
 
 namespace mm {
 
@@ -87,6 +87,7 @@ __device__ __forceinline__ SampleRec load_sample_rec(const SampleRec *p) {
 template <bool STAGE, int CW>
 __global__ void __launch_bounds__(64 * (MM_SAMPLE_NW + 1)) mm_sample_kernel(RunParams p, SampleParams sp) {
     extern __shared__ float lds[];
+    // (not MM_ITEM_PROLOGUE: the block's shape is a compile-time constant here, and a workgroup is a set of chains, not an utterance)
     constexpr int NW = MM_SAMPLE_NW, NT = 64 * (NW + 1);  // NW waves for the chains + one that only stages
     constexpr int FR = 64 / CW;                           // frames whose random words one vector evaluation of the generator makes
     const int b = blockIdx.x;
@@ -121,15 +122,12 @@ __global__ void __launch_bounds__(64 * (MM_SAMPLE_NW + 1)) mm_sample_kernel(RunP
     // but at the frame's barrier (its own loads share vmcnt with whatever DMA it issued)
     const int sn = NW + 1 - nact, sw = wave - nact;
     const int n4 = S1p >> 2;
-    auto stage_row = [&](int f) {  // alpha~ of frame f into its half of the LDS
-        const float4 *src = reinterpret_cast<const float4 *>(wsA + (long long)f * S1p);
-        const unsigned dst = lds_addr_of(lds + (f & 1) * S1p);
-        for (int q0 = sw * 64; q0 < n4; q0 += sn * 64)
-            if (q0 + lane < n4) dma_b128(src + q0 + lane, dst + 16u * (unsigned)q0);
+    auto stage_frame = [&](int f) {  // alpha~ of frame f into its half of the LDS, by the sn waves without a chain
+        stage_row<false>(lds + (f & 1) * S1p, wsA + (long long)f * S1p, n4, tid, sn * 64, sw, lane);
     };
     if constexpr (STAGE) {
-        if (sw >= 0) stage_row(len);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (sw >= 0) stage_frame(len);
+        stage_row_wait<false>();
         __syncthreads();
     }
     // the chains' state: the state drawn last (the final state to begin with) as its in-list, the path's last 64 frames (lane
@@ -170,7 +168,7 @@ __global__ void __launch_bounds__(64 * (MM_SAMPLE_NW + 1)) mm_sample_kernel(RunP
             }
         }
         if constexpr (STAGE)
-            if (n > 1 && sw >= 0) stage_row(n - 1);
+            if (n > 1 && sw >= 0) stage_frame(n - 1);
         if (wave < nact) {
 #pragma unroll
             for (int c = 0; c < CW; ++c) {
@@ -235,7 +233,7 @@ __global__ void __launch_bounds__(64 * (MM_SAMPLE_NW + 1)) mm_sample_kernel(RunP
             }
         }
         if constexpr (STAGE) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's part of alpha~ of frame n - 1 is in LDS
+            stage_row_wait<false>();  // this wave's part of alpha~ of frame n - 1 is in LDS
             __syncthreads();
         }
     }

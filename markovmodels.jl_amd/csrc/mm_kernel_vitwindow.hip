@@ -22,7 +22,7 @@
 // under its 1024-thread bound; the others none.)
 #pragma once
 #include "mm_internal.h"
-#include "mm_kernels.hip"
+#include "mm_item_parts.hip"
 
 namespace mm {
 
@@ -33,27 +33,17 @@ __host__ __device__ inline int vitwindow_lds_floats(int S1p, int P1p) { return l
 // LDS of the trace kernel, in bytes: two flag vectors of S1p bytes (flags_global: none)
 __host__ __device__ inline size_t vitwindow_trace_lds_bytes(int S1p, bool flags_global) { return flags_global ? 0 : 2 * size_t(S1p); }
 
-#define MM_VITWINDOW_PROLOGUE                                                                                     \
-    const int b = blockIdx.x;                                                                                     \
-    const UttDesc &u = p.utts[b];                                                                                 \
-    const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63;                                                \
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), NW = NT >> 6;                                      \
-    const int S1 = u.S1, S1p = u.S1p, fstate = S1 - 1;                                                            \
-    int len = p.lens ? p.lens[b] : p.N;                                                                           \
-    len = len < 0 ? 0 : (len > p.N ? p.N : len);                                                                  \
-    const bool closed = wp.closed ? __builtin_amdgcn_readfirstlane(wp.closed[b]) != 0 : false;                    \
-    const long long wsrow = u.s1p_prefix * (long long)(p.N + 1);                                                  \
-    int *wsBP = wp.ws_bp + wsrow;                                                                                 \
-    float *wsBest = wp.ws_best + wsrow;                                                                           \
-    float *wsM = wp.ws_m + (long long)b * (p.N + 2)
-
 // forward: rows 1..len of the back-pointers (row r: frame r + 1) and of `best` (row r: step r + 1), row 0 of the back-pointers: the
 // flags of A_len; m_1..m_len, the end state and the score.  grid = B workgroups (one utterance each), block = 64 * NW threads.
 template <int NI, bool BIGV>
 __global__ void __launch_bounds__(1024) mm_vitwindow_fwd_kernel(RunParams p, VitWindowParams wp) {
     extern __shared__ float lds[];
-    MM_VITWINDOW_PROLOGUE;
-    const int P1 = u.P1, P = P1 - 1, P1p = (P1 + 3) & ~3;
+    MM_ITEM_PROLOGUE(BIGV);  // (the prologue alone: the recursion is tropical, its parts are mm_tropical_kernel's)
+    const bool closed = wp.closed ? __builtin_amdgcn_readfirstlane(wp.closed[b]) != 0 : false;
+    const long long wsrow = u.s1p_prefix * (long long)(p.N + 1);
+    int *wsBP = wp.ws_bp + wsrow;
+    float *wsBest = wp.ws_best + wsrow;
+    float *wsM = wp.ws_m + (long long)b * (p.N + 2);
     if (len == 0) {  // no frame: no path (the trace kernel passes the start vector through)
         if (tid == 0) {
             p.score[b] = MM_NINF;
@@ -61,19 +51,12 @@ __global__ void __launch_bounds__(1024) mm_vitwindow_fwd_kernel(RunParams p, Vit
         }
         return;
     }
-    const int NF = len + 1;
     const LdsPlan L = lds_plan(BIGV ? 0 : S1p, P1p, true);
     float *em = lds + L.em, *part = lds + L.part;
     float *rbest = lds + L.total;
     int *rarg = reinterpret_cast<int *>(lds + L.total + MM_MAX_WAVES);
     float *buf = BIGV ? p.ws_big + (long long)b * p.big_stride : lds + L.buf;  // (BIGV: see mm_log_kernel)
-    auto vsync = [&]() {
-        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __syncthreads();
-        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    };
     int *bpbuf = reinterpret_cast<int *>(BIGV ? buf + 2 * S1p : lds + L.stage);  // [2][S1p]
-    const float *Vb = p.V + (long long)b * p.vsb;
     const float *sin = wp.state_in ? wp.state_in + u.state_off : nullptr;
     const GraphDev gf = u.g[0];
     ItemRegs<NI> rg;
@@ -241,13 +224,11 @@ template <bool GF>
 __global__ void __launch_bounds__(256) mm_vitwindow_trace_kernel(RunParams p, VitWindowParams wp) {
     extern __shared__ float lds[];
     __shared__ int cnt[2][4];
-    MM_VITWINDOW_PROLOGUE;
-    (void)closed;
-    auto vsync = [&]() {
-        if constexpr (GF) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        __syncthreads();
-        if constexpr (GF) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    };
+    MM_ITEM_PROLOGUE(GF);
+    const long long wsrow = u.s1p_prefix * (long long)(p.N + 1);
+    int *wsBP = wp.ws_bp + wsrow;
+    float *wsBest = wp.ws_best + wsrow;
+    float *wsM = wp.ws_m + (long long)b * (p.N + 2);
     int *path = p.path + (long long)b * p.path_stride_b;
     for (int n = len + tid; n < p.N; n += NT) path[n] = -1;
     const bool ok = p.score[b] > MM_NINF;  // (the forward kernel's: -inf for a window without a frame or without a path)

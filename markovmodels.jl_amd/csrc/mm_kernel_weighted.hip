@@ -70,6 +70,8 @@ __global__ void __launch_bounds__(256) mm_weights_kernel(RunParams p, WeightedPa
     }
 }
 
+// (Written out, none of the parts of mm_item_parts.hip: measured, every way of moving this kernel onto them costs the entry up to 1 % of
+// a call -- it sits at the register ceiling with 210 spilled scalars, and the compiler lays the whole time loop out anew.)
 template <int NI, bool BIGV>
 __global__ void __launch_bounds__(512) mm_weighted_bwd_kernel(RunParams p, WeightedParams wp) {
     extern __shared__ float lds[];

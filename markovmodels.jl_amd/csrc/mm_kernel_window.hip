@@ -22,7 +22,7 @@
 // finite) never enters the backward loop: gamma = 0, ttl = -inf.
 #pragma once
 #include "mm_internal.h"
-#include "mm_kernel_filter.hip"
+#include "mm_item_parts.hip"
 
 namespace mm {
 
@@ -44,45 +44,18 @@ __host__ __device__ inline WindowLds window_lds_plan(int S1p, int P1p) {
     return l;
 }
 
-// the sum of the waves' partial sums (lane < NW <= 16) in a fixed order, the same bits in every wave
-__device__ __forceinline__ float window_part_sum(const float *ps, int NW, int lane) {
-    float v = (lane < NW) ? ps[lane] : 0.f;
-    v = grp_sum(v, 4);
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-
-#define MM_WINDOW_PROLOGUE                                                                                        \
-    extern __shared__ float4 window_lds4[];                                                                       \
-    float *lds = reinterpret_cast<float *>(window_lds4);                                                          \
-    const int b = blockIdx.x;                                                                                     \
-    const UttDesc &u = p.utts[b];                                                                                 \
-    const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63;                                                \
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), NW = NT >> 6;                                      \
-    const int S1 = u.S1, S1p = u.S1p, P1 = u.P1, P = P1 - 1, P1p = (P1 + 3) & ~3;                                 \
-    const int fstate = S1 - 1;                                                                                    \
-    int len = p.lens ? p.lens[b] : p.N;                                                                           \
-    len = len < 0 ? 0 : (len > p.N ? p.N : len);                                                                  \
-    const int NF = len + 1;                                                                                       \
-    const bool closed = wp.closed ? __builtin_amdgcn_readfirstlane(wp.closed[b]) != 0 : false;                    \
-    const WindowLds L = window_lds_plan(BIGV ? 0 : S1p, P1p);                                                     \
-    float *em = lds + L.em, *part = lds + L.part;                                                                 \
-    float *buf = BIGV ? p.ws_big + (long long)b * p.big_stride : lds + L.buf;                                     \
-    float *stage = BIGV ? buf + 2 * S1p : lds + L.stage;                                                          \
-    auto vsync = [&]() {                                                                                          \
-        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");                                    \
-        __syncthreads();                                                                                          \
-        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                                    \
-    };                                                                                                            \
-    const float *Vb = p.V + (long long)b * p.vsb;                                                                 \
-    float *wsA = p.ws_alpha + u.s1p_prefix * (long long)(p.N + 1);                                                \
-    double *wsC = p.ws_c + (long long)b * (p.N + 2)
-
 // forward: the a~ rows of frames 1..len and C_n in the workspace (laid out as the item kernel's forward half leaves them), log2 of
 // the window's total in wsC[0]; state_out and lcommit.  grid = B workgroups (one utterance each), block = 64 * NW threads, NW <= 8.
 template <int NI, bool BIGV>
 __global__ void __launch_bounds__(512) mm_window_fwd_kernel(RunParams p, WindowParams wp) {
-    MM_WINDOW_PROLOGUE;
-    float *psum = lds + L.psum;
+    extern __shared__ float4 window_lds4[];
+    float *lds = reinterpret_cast<float *>(window_lds4);
+    MM_ITEM_PROLOGUE(BIGV);
+    const bool closed = wp.closed ? __builtin_amdgcn_readfirstlane(wp.closed[b]) != 0 : false;
+    const WindowLds L = window_lds_plan(BIGV ? 0 : S1p, P1p);
+    float *em = lds + L.em, *part = lds + L.part, *psum = lds + L.psum;
+    float *buf = BIGV ? p.ws_big + (long long)b * p.big_stride : lds + L.buf;
+    float *stage = BIGV ? buf + 2 * S1p : lds + L.stage;
     const float *sin = wp.state_in ? wp.state_in + u.state_off : nullptr;
     float *sout = wp.state_out ? wp.state_out + u.state_off : nullptr;
     int c = wp.commit ? __builtin_amdgcn_readfirstlane(wp.commit[b]) : len;
@@ -108,7 +81,7 @@ __global__ void __launch_bounds__(512) mm_window_fwd_kernel(RunParams p, WindowP
         float wm = MM_NINF;
         float *a1 = buf + 1 * S1p;
         const float *e1 = em + 1 * P1p;
-        Ec = filter_emax(e1, P, lane);
+        Ec = frame_emax(e1, P, lane);
         for (int s = tid; s < S1; s += NT) {
             const float st = sin ? (s < fstate ? sin[s] * MM_LOG2E : MM_NINF) : u.init[s];
             const float v = st + (e1[u.s2p[s]] - Ec) * MM_LOG2E;
@@ -136,19 +109,12 @@ __global__ void __launch_bounds__(512) mm_window_fwd_kernel(RunParams p, WindowP
         const bool at_c = n - 1 == c, at_len = n == NF;
         if (at_c) Cc = C + (double)M;
         if (at_len) Cl = C + (double)M;
-        Ec = filter_emax(emn, P, lane);  // (the last step: no real emission, 0)
+        Ec = frame_emax(emn, P, lane);  // (the last step: no real emission, 0)
         C += (double)M + (double)Ec * 1.4426950408889634;
         if (tid == 0) wsC[n] = C;
-        if (n + 1 <= NF) {
-            if (tid <= P) em[((n + 1) & 1) * P1p + tid] = filter_em_value(evp, n + 1, len, P, tid);
-            if (P >= NT) stage_em(em + ((n + 1) & 1) * P1p + NT, Vb + NT, p.vsn, n + 1, len, P - NT, tid, NT, 1.f);
-        }
+        if (n + 1 <= NF) stage_em_ahead<em_value_nat>(em + ((n + 1) & 1) * P1p, evp, Vb, p.vsn, n + 1, len, P, tid, NT, 1.f);
         evp = em_load_raw(Vb, p.vsn, n + 2, p.N, P, tid);
-        {   // frame n - 1 leaves the chip once (coalesced), while frame n is computed
-            float4 *dst = reinterpret_cast<float4 *>(wsA + (long long)(n - 1) * S1p);
-            const float4 *src = reinterpret_cast<const float4 *>(ap);
-            for (int q = tid; q < (S1p >> 2); q += NT) dst[q] = src[q];
-        }
+        copy_row(wsA + (long long)(n - 1) * S1p, ap, S1p >> 2, tid, NT);  // frame n - 1 leaves the chip once, while frame n is computed
         if (at_c || at_len) {  // the total of frame n - 1 over the real states, relative to the frame's own maximum
             float sw = 0.f;
             for (int s = tid; s < fstate; s += NT) sw += fast_exp2(ap[s] - M);
@@ -170,9 +136,9 @@ __global__ void __launch_bounds__(512) mm_window_fwd_kernel(RunParams p, WindowP
         vsync();
     }
     // (the barrier of the last step: the waves' sums, sv and the final state's row are visible)
-    const float tl = window_part_sum(psum + 1 * MM_MAX_WAVES, NW, lane);
+    const float tl = part_sum(psum + 1 * MM_MAX_WAVES, NW, lane);
     if (c >= 1) {
-        const float tc = window_part_sum(psum + 0 * MM_MAX_WAVES, NW, lane);
+        const float tc = part_sum(psum + 0 * MM_MAX_WAVES, NW, lane);
         const bool ok = tc > 0.f;  // mass at frame c: every frame up to c is alive
         const float lt = fast_log2(tc);
         if (sout)
@@ -190,9 +156,34 @@ __global__ void __launch_bounds__(512) mm_window_fwd_kernel(RunParams p, WindowP
 }
 
 // backward: gamma and ttl.  Same grid and block as the forward kernel.
+// (Written out, prologue included, none of the parts and not segment_bwd_body, the segment kernel's loop on the parts: as one body with
+// the segment kernel, this kernel's <8,lds> instance measured 0.3 - 0.6 % slower on the large batches in three sessions.)
 template <int NI, bool BIGV>
 __global__ void __launch_bounds__(512) mm_window_bwd_kernel(RunParams p, WindowParams wp) {
-    MM_WINDOW_PROLOGUE;
+    extern __shared__ float4 window_lds4[];
+    float *lds = reinterpret_cast<float *>(window_lds4);
+    const int b = blockIdx.x;
+    const UttDesc &u = p.utts[b];
+    const int tid = threadIdx.x, NT = blockDim.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), NW = NT >> 6;
+    const int S1 = u.S1, S1p = u.S1p, P1 = u.P1, P = P1 - 1, P1p = (P1 + 3) & ~3;
+    const int fstate = S1 - 1;
+    int len = p.lens ? p.lens[b] : p.N;
+    len = len < 0 ? 0 : (len > p.N ? p.N : len);
+    const int NF = len + 1;
+    const bool closed = wp.closed ? __builtin_amdgcn_readfirstlane(wp.closed[b]) != 0 : false;
+    const WindowLds L = window_lds_plan(BIGV ? 0 : S1p, P1p);
+    float *em = lds + L.em, *part = lds + L.part;
+    float *buf = BIGV ? p.ws_big + (long long)b * p.big_stride : lds + L.buf;
+    float *stage = BIGV ? buf + 2 * S1p : lds + L.stage;
+    auto vsync = [&]() {
+        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        __syncthreads();
+        if constexpr (BIGV) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    };
+    const float *Vb = p.V + (long long)b * p.vsb;
+    float *wsA = p.ws_alpha + u.s1p_prefix * (long long)(p.N + 1);
+    double *wsC = p.ws_c + (long long)b * (p.N + 2);
     float *bins = lds + L.bins;
     const GraphDev gb = u.g[1];
     const double logZ2 = wsC[0];
@@ -242,12 +233,12 @@ __global__ void __launch_bounds__(512) mm_window_bwd_kernel(RunParams p, WindowP
         const float *emn = em + (n & 1) * P1p;
         const float M = (n == len) ? 0.f : part_max_dpp(part + ((n + 1) & 1) * MM_MAX_WAVES, NW, lane);
         D += (double)M + (double)Enext * 1.4426950408889634;
-        const float En = filter_emax(emn, P, lane);
+        const float En = frame_emax(emn, P, lane);
         Enext = En;
         const float kappa = (float)(logZ2 - Cn - D);
         if (n < len && wave == NW - 1) finalise(n + 1);
         if (n - 1 >= 1) {  // frame n - 1 into the buffers frame n + 1 has left (as mm_log_kernel's PASS 2)
-            if (tid <= P) em[((n - 1) & 1) * P1p + tid] = filter_em_value(evp, n - 1, len, P, tid);
+            if (tid <= P) em[((n - 1) & 1) * P1p + tid] = em_value_nat(evp, n - 1, len, P, tid);
             if (P >= NT) stage_em(em + ((n - 1) & 1) * P1p + NT, Vb + NT, p.vsn, n - 1, len, P - NT, tid, NT, 1.f);
             const float4 *src = reinterpret_cast<const float4 *>(wsA + (long long)(n - 1) * S1p);
             if constexpr (BIGV) {

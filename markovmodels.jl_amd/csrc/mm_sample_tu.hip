@@ -6,11 +6,6 @@
 
 namespace mm {
 
-template <int NI, bool BIGV>
-static int launch_sample_fwd(int64_t B, int NW, size_t lds, const RunParams &p, hipStream_t stream) {
-    return mm_launch(mm_log_kernel<MODE_FB, NI, 1, false, BIGV>, dim3(unsigned(B)), dim3(64 * NW), lds, stream, p);
-}
-
 template <bool STAGE, int CW>
 static int launch_sample_walk(int64_t B, int max_S1p, const RunParams &p, const SampleParams &sp, hipStream_t stream) {
     const size_t lds = STAGE ? size_t(2) * size_t(max_S1p) * sizeof(float) : 0;
@@ -38,10 +33,9 @@ static int launch_sample_cw(int cw, int64_t B, int max_S1p, const RunParams &p, 
 
 int mm_launch_sample(int64_t B, int NW, int NI, bool bigv, size_t lds, bool stage, int max_S1p, int n_cus, const RunParams &p, const SampleParams &sp,
                      hipStream_t stream) {
-    int rc;
-    if (NI == 8) rc = bigv ? launch_sample_fwd<8, true>(B, NW, lds, p, stream) : launch_sample_fwd<8, false>(B, NW, lds, p, stream);
-    else if (NI == 0 && bigv) rc = launch_sample_fwd<0, true>(B, NW, lds, p, stream);
-    else return mm_fail(MM_ERR_UNSUPPORTED, "path sampling: no instance for this geometry");
+    const int rc = item_instance("path sampling", NI, bigv, [&](auto I) {
+        return mm_launch(mm_log_kernel<MODE_FB, decltype(I)::NI, 1, false, decltype(I)::BIGV>, dim3(unsigned(B)), dim3(64 * NW), lds, stream, p);
+    });
     if (rc) return rc;
     const int cw = sample_cw(B, sp.K, n_cus);
     return stage ? launch_sample_cw<true>(cw, B, max_S1p, p, sp, stream) : launch_sample_cw<false>(cw, B, max_S1p, p, sp, stream);

@@ -7,22 +7,16 @@
 
 namespace mm {
 
-template <int NI, bool BIGV>
-static int launch_segment_bwd_ni(int64_t B, int NW, size_t lds, const RunParams &p, const SegmentParams &sp, hipStream_t stream) {
-    return mm_launch(mm_segment_bwd_kernel<NI, BIGV>, dim3(unsigned(B)), dim3(64 * NW), lds, stream, p, sp);
-}
-
 int mm_launch_segment(int64_t B, int NW, int NI, bool bigv, size_t lds, const RunParams &p, const SegmentParams &sp, hipStream_t stream) {
-    if (!(NI == 8 || (NI == 0 && bigv))) return mm_fail(MM_ERR_UNSUPPORTED, "segment posteriors: no instance for this geometry");
-    // the forward half: no commit frame, no state_out; its total in ws_c[0] is the open one (end_mode 0) or the closed one (the
-    // backward kernel takes a carried end's total itself)
-    WindowParams wp{};
-    wp.state_in = sp.state_in;
-    wp.closed = sp.end_mode;
-    int rc = mm_launch_window_fwd(B, NW, NI, bigv, lds, p, wp, stream);
-    if (rc) return rc;
-    if (NI == 8) return bigv ? launch_segment_bwd_ni<8, true>(B, NW, lds, p, sp, stream) : launch_segment_bwd_ni<8, false>(B, NW, lds, p, sp, stream);
-    return launch_segment_bwd_ni<0, true>(B, NW, lds, p, sp, stream);
+    return item_instance("segment posteriors", NI, bigv, [&](auto I) {
+        // the forward half: no commit frame, no state_out; its total in ws_c[0] is the open one (end_mode 0) or the closed one (the
+        // backward kernel takes a carried end's total itself)
+        WindowParams wp{};
+        wp.state_in = sp.state_in;
+        wp.closed = sp.end_mode;
+        const int rc = mm_launch_window_fwd(B, NW, NI, bigv, lds, p, wp, stream);
+        return rc ? rc : mm_launch(mm_segment_bwd_kernel<decltype(I)::NI, decltype(I)::BIGV>, dim3(unsigned(B)), dim3(64 * NW), lds, stream, p, sp);
+    });
 }
 
 }  // namespace mm

@@ -9,24 +9,22 @@ namespace mm {
 
 size_t mm_weighted_lds_bytes(int S1p, int P1p) { return size_t(lds_plan(S1p, P1p, true).total + 2 * MM_MAX_WAVES + S1p) * 4; }
 
-template <int NI, bool BIGV>
-static int launch_weighted_ni(int64_t B, int NW, size_t lds_fwd, size_t lds_bwd, const RunParams &p, const WeightedParams &wp, hipStream_t stream) {
-    const int rc = mm_launch(mm_log_kernel<MODE_FB, NI, 1, false, BIGV>, dim3(unsigned(B)), dim3(64 * NW), lds_fwd, stream, p);
-    return rc ? rc : mm_launch(mm_weighted_bwd_kernel<NI, BIGV>, dim3(unsigned(B)), dim3(64 * NW), lds_bwd, stream, p, wp);
-}
-
 int mm_launch_weighted(int64_t B, int NW, int NI, bool bigv, size_t lds_fwd, size_t lds_bwd, const RunParams &p0, const WeightedParams &wp,
                        hipStream_t stream) {
-    if (!(NI == 8 || (NI == 0 && bigv))) return mm_fail(MM_ERR_UNSUPPORTED, "weighted posteriors: no instance for this geometry");
+    const dim3 grid{unsigned(B)}, block{unsigned(64 * NW)};
     RunParams p = p0;
-    int rc = MM_OK;
-    if (wp.utts_call) {
-        rc = mm_launch(mm_weights_kernel, dim3(unsigned(B), 16), dim3(256), 0, stream, p, wp);
-        if (rc) return rc;
-        p.utts = wp.utts_call;
-    }
-    if (NI == 8) rc = bigv ? launch_weighted_ni<8, true>(B, NW, lds_fwd, lds_bwd, p, wp, stream) : launch_weighted_ni<8, false>(B, NW, lds_fwd, lds_bwd, p, wp, stream);
-    else rc = launch_weighted_ni<0, true>(B, NW, lds_fwd, lds_bwd, p, wp, stream);
+    const int rc = item_instance("weighted posteriors", NI, bigv, [&](auto I) {
+        constexpr int NI_ = decltype(I)::NI;
+        constexpr bool BIGV = decltype(I)::BIGV;
+        int rc = MM_OK;
+        if (wp.utts_call) {
+            rc = mm_launch(mm_weights_kernel, dim3(unsigned(B), 16), dim3(256), 0, stream, p, wp);
+            if (rc) return rc;
+            p.utts = wp.utts_call;
+        }
+        rc = mm_launch(mm_log_kernel<MODE_FB, NI_, 1, false, BIGV>, grid, block, lds_fwd, stream, p);
+        return rc ? rc : mm_launch(mm_weighted_bwd_kernel<NI_, BIGV>, grid, block, lds_bwd, stream, p, wp);
+    });
     if (rc || !(wp.counts || wp.init_counts || wp.ttl)) return rc;
     return mm_launch(mm_weighted_scatter_kernel, dim3(unsigned(B), 4), dim3(256), 0, stream, p, wp);
 }

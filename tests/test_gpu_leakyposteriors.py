@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import leaky_reference as lr
-from test_gpu_parity import check_gamma
+from test_gpu_parity import _with_env, check_gamma
 from test_leakyposteriors import restart_case
 
 pytestmark = pytest.mark.gpu
@@ -81,6 +81,20 @@ def test_random_graph_lengths_and_no_path(mm, wl, torch, eps):
     bf = _batch(mm, wl, gs)
     gamma, ttl = bf.leakyposteriors(V, lens, leak=eps)
     _check(gamma, ttl, gs, V, lens, eps)
+    for b in (3, 4):  # len = 0; a frame whose emissions are all -inf
+        assert np.isneginf(ttl[b]) and (gamma[b] == 0).all()
+    assert np.isfinite(ttl[[0, 1, 2]]).all()
+
+
+def test_streamed_instance(mm, wl, torch):
+    """No item in registers (MM_NITEMS=0): every item streamed, the vectors in global memory -- the instance FSMs of more than 65534
+    states run, on the graph of test_random_graph_lengths_and_no_path and with its bars."""
+    gs, V, lens = case_random40(wl)
+    bf = _with_env({"MM_DEBUG": "1", "MM_NITEMS": "0"}, lambda: _batch(mm, wl, gs))
+    k = bf.kernels("leaky")
+    assert "mm_leaky_fwd_kernel<0,global>" in k and "mm_leaky_bwd_kernel<0,global>" in k, k
+    gamma, ttl = bf.leakyposteriors(V, lens, leak=0.1)
+    _check(gamma, ttl, gs, V, lens, 0.1)
     for b in (3, 4):  # len = 0; a frame whose emissions are all -inf
         assert np.isneginf(ttl[b]) and (gamma[b] == 0).all()
     assert np.isfinite(ttl[[0, 1, 2]]).all()
