@@ -111,7 +111,8 @@ int mm_batch_destroy(mm_batch_t batch);
 /* Sum over the batch of S1 (rows of the block-diagonal system). */
 int64_t mm_batch_total_states(mm_batch_t batch);
 /* Names of the kernels a run entry launches for this batch (the engine picks them from the graphs' sizes and
- * shapes): entry 0 = mm_pdfposteriors_f32, 1 = mm_viterbi_f32, 2 = what the last mm_pdfposteriors_ex call on the batch launched
+ * shapes): entry 0 = mm_pdfposteriors_f32, 1 = mm_viterbi_f32 (on the row-lane form: mm_vit_kernel<N4,N2,NJ> +
+ * mm_vit_backtrace_kernel<csr in LDS|global memory, R=frames per buffer of its ring>, else the item kernel), 2 = what the last mm_pdfposteriors_ex call on the batch launched
  * (the recursion kernel; for ProbSemiring FSMs in float32 with general state maps, the emission GEMM C_hat * V_hat on the matrix
  * cores before it), 3 = mm_alpharecursion_f32 / mm_betarecursion_f32, 4 = mm_arcposteriors_f32 (log batches only),
  * 5 = mm_samplepaths_f32 (log batches only), 6 = mm_expectedcost_f32 (log batches only), 7 = mm_leakyposteriors_f32 (log batches

@@ -2564,6 +2564,18 @@ static std::string fb_kernels(mm_batch_t h) {
 }
 
 static bool export_on_pairs(mm_batch_t h, int dir);
+// what mm_launch_viterbi is told about a batch whose FSMs all have the Viterbi form (h->vit_ok)
+static VitLaunch vit_launch_of(mm_batch_t h) {
+    VitLaunch vl;
+    vl.B = h->B;
+    vl.n4 = h->vit_n4;
+    vl.n2 = h->vit_n2;
+    vl.max_P1 = h->max_P1;
+    vl.max_S1p = h->max_S1p;
+    vl.max_arcs = h->vit_arcs;
+    vl.bp_row = int((size_t(h->max_S1p) + 255) & ~size_t(255));  // bytes of a row of one-byte back-pointers, padded to 256
+    return vl;
+}
 int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
     if (!h || !buf || n < 2) return fail(MM_ERR_INVALID, "mm_batch_kernels: bad argument");
     if (entry == 0) h = twin_of(h);  // (ProbSemiring: the fast entry runs the log twins' kernels)
@@ -2574,8 +2586,15 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
         s = fb_kernels(h);
     } else if (entry == 1) {  // mm_viterbi_f32
         const std::string t = tropical_kernel(h);
-        s = h->vit_ok ? "mm_vit_kernel + mm_vit_backtrace_kernel (" + t + " + mm_backtrace_kernel when the int32 back-pointers are asked for)"
-                      : t + " + mm_backtrace_kernel";
+        s = t + " + mm_backtrace_kernel";
+        if (h->vit_ok) {  // (the instance and the back-trace's plan: what mm_launch_viterbi launches, mm_vit_plan)
+            VitPlan pl;
+            const int rc = mm_vit_plan(vit_launch_of(h), &pl);
+            if (rc) return rc;
+            s = "mm_vit_kernel<" + std::to_string(h->vit_n4) + "," + std::to_string(h->vit_n2) + "," + std::to_string(pl.nj) + "> + mm_vit_backtrace_kernel<csr in " +
+                (pl.csrl ? "LDS" : "global memory") + ", R=" + std::to_string(pl.R) + "> with " + std::to_string(pl.lds) + " bytes of LDS (" + t +
+                " + mm_backtrace_kernel when the int32 back-pointers are asked for)";
+        }
     } else if (entry == 3) {  // mm_alpharecursion_f32 / mm_betarecursion_f32
         const bool xa = export_on_pairs(h, 0), xb = export_on_pairs(h, 1);
         const std::string fast = (h->pair_H > 1 ? "mm_fbsx_kernel<2," + std::to_string(h->pair_H) + "> (phase A of one direction over all frames, teams of " + std::to_string(h->pair_H) + " workgroups) + "
@@ -2728,7 +2747,7 @@ size_t mm_batch_workspace_bytes(mm_batch_t h, int64_t N) {
 
 // Viterbi on the row-lane form (mm_kernel_vit.hip): one-byte back-pointers [B][N + 1][row], rows padded to 256 bytes, + the
 // KB the back-trace's last DMA may read past the end
-static size_t vit_bp_row(mm_batch_t h) { return (size_t(h->max_S1p) + 255) & ~size_t(255); }
+static size_t vit_bp_row(mm_batch_t h) { return size_t(vit_launch_of(h).bp_row); }
 static size_t ws_vit_bytes(mm_batch_t h, int64_t N) {
     if (h->semiring != MM_TROPICAL) return 0;
     return h->vit_ok ? size_t(h->B) * size_t(N + 1) * vit_bp_row(h) + 1024 : align_up(size_t(h->total_states) * size_t(N + 1) * 4, 256);
@@ -3936,14 +3955,7 @@ int mm_viterbi_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const
     p.score = score;
     bind_stamps(h, p);
     if (h->vit_ok && p.stop_at_len) {  // (internal back-pointers: the compact form)
-        VitLaunch vl;
-        vl.B = h->B;
-        vl.n4 = h->vit_n4;
-        vl.n2 = h->vit_n2;
-        vl.max_P1 = h->max_P1;
-        vl.max_S1p = h->max_S1p;
-        vl.max_arcs = h->vit_arcs;
-        vl.bp_row = int(vit_bp_row(h));  // bytes of a row of one-byte back-pointers, padded to 256
+        const VitLaunch vl = vit_launch_of(h);
         RunParams q = p;
         q.bp_stride_n = vl.bp_row;
         return mm_launch_viterbi(vl, q, static_cast<hipStream_t>(stream));

@@ -170,6 +170,15 @@ struct VitLaunch {
     int64_t B = 0;
     int n4 = 0, n2 = 0, max_P1 = 0, max_S1p = 0, max_arcs = 0, bp_row = 0;  // n4 x n2: wide / narrow positions per wave
 };
+// What mm_launch_viterbi launches for a batch: the forward instance mm_vit_kernel<n4,n2,nj> and the back-trace's plan -- csrl: the
+// graph's row pointers and sources sit in LDS next to the ring (mm_vit_backtrace_kernel<true>), R: frames per buffer of the ring,
+// lds: the back-trace's dynamic LDS bytes.  One owner of the arithmetic: the launcher and mm_batch_kernels both ask here.
+struct VitPlan {
+    int nj = 0, R = 0;
+    bool csrl = false;
+    size_t lds = 0;
+};
+int mm_vit_plan(const VitLaunch &vl, VitPlan *pl);  // MM_ERR_UNSUPPORTED: no instance, or no room for one row of back-pointers
 int mm_launch_viterbi(const VitLaunch &vl, const RunParams &p, hipStream_t stream);
 
 // ---- quad kernels (mm_quad_tu.hip)

@@ -181,7 +181,9 @@ def test_viterbi_bit_exact(mm, wl, oracle, torch, name):
         rng = np.random.default_rng(5)
         N = 37
         lens = [37, 20, 1]
-        # quantised scores make exact ties frequent, so the lowest-index rule is exercised
+        # (emissions on a grid of 0.5.  The arc weights are continuous, so two arcs into a state still never tie: by the float32
+        # reference no live cell of these graphs has two maximisers, and the lowest-source rule is not exercised here.  It is in
+        # tests/test_gpu_viterbi_rows.py, whose weights are on the grid too: tests/test_viterbi_inputs.py counts the ties.)
         Vs = (np.round(rng.standard_normal((3, N, g.P)) * 2) / 2).astype(np.float32)
     f = wl.to_fsm(mm, g, semiring="tropical")
     of = graphs.to_oracle(o, g, "tropical", np.float32)
