@@ -2519,7 +2519,7 @@ static std::string fb_kernels(mm_batch_t h) {
         return "mm_wave_kernel<" + std::to_string(h->wave_nseg <= 2 ? 2 : 4) + "," + std::to_string(h->max_P1 <= 128 ? 2 : 4) +
             (h->wave_nseg <= 2 && h->B > h->n_cus ? ",two per CU>" : ">");
     case Fb::Stream:
-        return "mm_stream_kernel (forward and backward recursions as workgroups of one grid" +
+        return "mm_stream_kernel<" + std::to_string(mm_stream_nj(h->max_P1)) + "," + std::to_string(h->stream_H) + "> (forward and backward recursions as workgroups of one grid" +
             (h->stream_H > 1 ? ", teams of " + std::to_string(h->stream_H) + " workgroups per utterance and direction" : std::string()) +
             "; arcs streamed from L2, the vector in LDS as wide-exponent "
             "32-bit values), mm_stream_combine_kernel, mm_stream_finish_kernel, then for marked utterances only " + redo;

@@ -153,6 +153,9 @@ int mm_launch_lane(int64_t B, int max_S, const RunParams &p, hipStream_t stream)
 // the vector in LDS as wide-exponent 32-bit values, one utterance per workgroup, forward launch then backward launch
 struct StreamForm;
 size_t mm_stream_lds_bytes(int S1, int P1);
+// NJ of mm_stream_kernel<NJ, H>: 64-lane passes over the P1 = P + 1 pdfs of a batch.  One owner of the arithmetic: the launcher, the
+// LDS layout and mm_batch_kernels all ask here.
+int mm_stream_nj(int P1);
 // (H: workgroups of a team per utterance and direction -- 1, 2 or 4; the rows of a direction dealt to H sets)
 int mm_stream_build(int64_t S1, int32_t P1, const int64_t *const rowptr[2], const int32_t *const col[2], const float *const val[2],
                     const float *init, const int32_t *s2p, bool upload, int H, StreamForm **out);  // *out NULL: does not fit

@@ -86,11 +86,11 @@ static unsigned w_hi_of(double v) {  // high dword, 20 mantissa bits rounded to 
     return unsigned((b + 0x80000000ull) >> 32);
 }
 
-static int stream_nj(int P1) { return P1 <= 128 ? 2 : (P1 <= 256 ? 4 : (P1 <= 512 ? 8 : 16)); }  // 64-lane passes over the pdfs
+int mm_stream_nj(int P1) { return P1 <= 128 ? 2 : (P1 <= 256 ? 4 : (P1 <= 512 ? 8 : 16)); }  // 64-lane passes over the pdfs
 size_t mm_stream_lds_bytes(int S1, int P1) {
     // (+ 12: the regions of up to four sets are padded to multiples of 4 positions)
     const size_t vb = (size_t(4) * (size_t(S1) + 12 + 1) + 255) & ~size_t(255);
-    const size_t pc = size_t(64) * size_t(stream_nj(P1));
+    const size_t pc = size_t(64) * size_t(mm_stream_nj(P1));
     return 2 * vb + 8 * pc /* EM: 2 x 4 bytes per pdf */ + 256;
 }
 
@@ -861,7 +861,7 @@ int mm_launch_stream(int64_t B, int n_cus, int max_S1, int max_P1, int H, const 
         if (H == 4) return launch_stream_nj<NJ_, 4>(B, n_cus, lds, p, st);           \
         if (H == 2) return launch_stream_nj<NJ_, 2>(B, n_cus, lds, p, st);           \
         return launch_stream_nj<NJ_, 1>(B, n_cus, lds, p, st);
-    switch (stream_nj(max_P1)) {
+    switch (mm_stream_nj(max_P1)) {
         MM_STREAM_CASE(2)
         MM_STREAM_CASE(4)
         MM_STREAM_CASE(8)

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import graphs
+import stream_cases
 
 
 def test_fsm_constructor_matches_oracle(mm, wl, oracle):
@@ -422,7 +423,7 @@ def test_compiled_graph_cache_is_keyed_by_content(mm, wl):
     assert inf.compiled_cache_stats()["bytes_estimate"] == 0
 
 
-@pytest.mark.parametrize("gname", ["rand300", "wide", "den_wsj", "big"])
+@pytest.mark.parametrize("gname", ["rand300", "wide", "den_wsj", "big", "midrows", "limit16370"])
 def test_stream_form_product(mm, wl, gname):
     """The stream form (mm_stream.hip: arcs as 8-byte records streamed per frame, rows in segments of 64 sorted by length, rows of
     more than 128 arcs on a whole wave) evaluates the same semiring products as the packed item form, in both directions: the
@@ -430,7 +431,9 @@ def test_stream_form_product(mm, wl, gname):
     7000-state / 900-pdf graph of config 3's family that no register-resident form takes."""
     g = {"rand300": lambda: wl.random_fsm(300, 11, 4.0, seed=9), "wide": lambda: wl.wide_row_fsm(700, 11),
          "den_wsj": lambda: wl.load_npz_graph(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "den_fsm_wsj.npz")),
-         "big": lambda: wl.lfmmi_denominator(7000, 900, seed=3)}[gname]()
+         "big": lambda: wl.lfmmi_denominator(7000, 900, seed=3),
+         # (tests/stream_cases.py: rows of every lane-group width in both directions; the most states the form holds)
+         "midrows": lambda: stream_cases.mid_row_graph(wl), "limit16370": lambda: stream_cases.limit_graph(wl, stream_cases.S1_LIMIT)}[gname]()
     cf = mm.compile(wl.to_fsm(mm, g), mm.statemap(g.state2pdf, g.P))
     rng = np.random.default_rng(1)
     x = rng.standard_normal(cf.S1).astype(np.float32)
@@ -449,3 +452,13 @@ def test_stream_form_product(mm, wl, gname):
             elif gname == "big":  # the most loaded wave of a team carries less than the lone workgroup's (bounded below by the longest
                 # segment: 64 rows of up to 128 arcs go to ONE wave whatever the team)
                 assert stats[3] <= (0.85 if H == 2 else 0.82) * slots1, (gname, d, H, stats[3], slots1)
+
+
+def test_stream_form_refuses_a_state_beyond_its_limit(mm, wl):
+    """One state more than the 16-bit LDS byte offsets of the records can name (S1 = 16371): no stream form, for any team."""
+    g = stream_cases.limit_graph(wl, stream_cases.S1_LIMIT + 1)
+    cf = mm.compile(wl.to_fsm(mm, g), mm.statemap(g.state2pdf, g.P))
+    assert cf.S1 == stream_cases.S1_LIMIT + 1
+    for H in (1, 2, 4):
+        with pytest.raises(mm.MarkovModelsAMDError, match="does not fit the stream form"):
+            cf.stream_product(np.zeros(cf.S1, dtype=np.float32), 0, H)
