@@ -124,6 +124,8 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * 12 = mm_weightedposteriors_f32 (log batches only): mm_weights_kernel + mm_log_kernel<MODE_FB,NI,1> + mm_weighted_bwd_kernel<NI,lds|global>
  * + mm_weighted_scatter_kernel.
  * 13 = mm_segmentposteriors_f32 (log batches only): mm_window_fwd_kernel<NI,lds|global> + mm_segment_bwd_kernel<...>.
+ * 14 = mm_arcclassposteriors_f32 (log batches only): mm_log_kernel<MODE_FB,NI,1> + mm_arcclass_kernel<NI,lds|global>; the text ends
+ * in where the current class plan's term rows live ("terms in LDS" / "terms in global memory" / "no classes set").
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -531,6 +533,45 @@ int mm_windowposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b
 int mm_segmentposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
                              const float *state_in, const int32_t *end_mode, const float *end_in, float *end_out, float *lend,
                              float *gamma, int64_t g_stride_b, int64_t g_stride_n, int64_t g_stride_p, float *ttl, void *stream);
+
+/* Per-frame arc-class posteriors: Baum-Welch's xi_n (L. E. Baum et al., "A maximization technique occurring in the statistical
+ * analysis of probabilistic functions of Markov chains", 1970; Rabiner 1989, eq. 37), summed over classes of arcs instead of over
+ * the frames.  mm_batch_set_arc_classes gives every stored entry k = (i_k -> j_k) of an FSM's T_hat -- the phony-final column and
+ * the phony self-loop included, in the order mm_arcposteriors_f32 reports them -- a class cls[k] in {-1, 0, ..., C-1}; -1: not
+ * counted.  For utterance b of length len, frames 1-based inside the formula, t = 0 .. N-1:
+ *
+ *   xi[b, c, t] = sum_{k : cls[k] = c}  alpha_{t+1}(i_k) * T_hat_{i_k j_k} * lhs_{t+2}(j_k) * beta_{t+2}(j_k) / Z_b
+ *
+ * with Z_b the normaliser of mm_pdfposteriors_f32.  So: for t < len-1 the terms are real arcs; at t = len-1 they are the arcs into
+ * the phony final state; for t >= len only the phony self-loop is alive -- its class, if it has one, gets exactly 1.0f and every
+ * other class exactly 0.0f.  If every entry has a class, sum_c xi[b, c, t] = 1 for every t < N.  sum_t xi[b, c, t] = the sum of
+ * mm_arcposteriors_f32's counts over the entries of class c.  With cls[k] = the pdf of the source state i_k, xi[b, p, t] =
+ * gamma[b, p, t] for t < len; with cls[k] = the pdf of the destination j_k (the phony pdf = P, so C = P + 1), xi[b, p, t] =
+ * gamma[b, p, t+1] for t+1 < len, and class P holds the final arcs at t = len-1 and the phony loop behind it.  An utterance with
+ * no accepting path gets xi = 0 everywhere and ttl = -inf; len = 0 with a path: every frame is the phony loop's (as the counts of
+ * mm_arcposteriors_f32).  No gradient of xi is offered (it is second order).
+ *
+ * mm_batch_set_arc_classes: host arrays, not retained.  offsets NULL: one array of nnz ids for a batch of ONE shared FSM; else
+ * offsets[B + 1] into cls, utterance b's nnz_b ids at cls[offsets[b]] (a wrong slice length: MM_ERR_DIM).  C < 1, an id outside
+ * [-1, C), a batch of several FSMs without offsets: MM_ERR_INVALID.  Host work only: the classified entries are ranked by (class,
+ * entry index) per distinct (FSM, class array); the first mm_arcclassposteriors_f32 call behind it puts the plan on the device in
+ * one allocation and one copy (never during a stream capture: MM_ERR_INVALID).  Calling it again replaces the plan.
+ * mm_batch_arc_class_info: cap = the most classified entries of one utterance whose per-frame terms the kernel keeps in LDS for
+ * this batch (beyond it they live in the workspace), max_M = the most any utterance of the current plan has (-1: no plan), C.
+ *
+ *   V, lens, N   as mm_pdfposteriors_f32
+ *   xi           device, out: element (b, c, t) at xi[b*x_stride_b + t*x_stride_n + c*x_stride_c]; strides that cannot hold
+ *                B x N x C elements: MM_ERR_DIM.  NULL: MM_ERR_INVALID
+ *   ttl          device float[B], out (NULL: not written): log Z_b
+ * MM_LOG batches only (others: MM_ERR_UNSUPPORTED); no classes set: MM_ERR_INVALID.  Runs on the item form of every FSM: the
+ * forward half of the item kernel, then mm_arcclass_kernel: the beta~ recursion of the arc entry with its per-frame correction,
+ * one owning thread per classified entry and frame, class sums in a fixed order -- no atomics, a repeated call returns the same
+ * bits, and relabelling the classes permutes the rows of xi bit for bit.  Stream contract of mm_arcposteriors_f32: launches on
+ * `stream` only; it can be captured in a hipGraph once a first call has put the plan on the device and sized the workspace. */
+int mm_batch_set_arc_classes(mm_batch_t batch, const int32_t *cls, const int64_t *offsets, int32_t C);
+int mm_batch_arc_class_info(mm_batch_t batch, int64_t *cap, int64_t *max_M, int32_t *C);
+int mm_arcclassposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                              float *xi, int64_t x_stride_b, int64_t x_stride_n, int64_t x_stride_c, float *ttl, void *stream);
 
 /* alpha-recursion(alpha_hat, T_hat', C_hat*V_hat) (src/inference.jl:62-74) as
  * called from pdfposteriors (:150-152): out is the reference's state_A, a

@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, set_arc_classes!, arc_class_info, arcclassposteriors, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -238,6 +238,56 @@ function arcposteriors(b::ROCBatch, V::ROCArray{Float32,3}, fsms::AbstractVector
     mats = [SparseMatrixCSC(size(T, 1), size(T, 2), copy(T.colptr), copy(T.rowval), c[1:nnz(T), u]) for (u, T) in enumerate(Ts)]
     inits = [SparseVector(length(a), copy(SparseArrays.nonzeroinds(a)), iv[1:nnz(a), u]) for (u, a) in enumerate(αs)]
     mats, inits, Array(ttl)
+end
+
+"""
+    set_arc_classes!(b::ROCBatch, classes, C = nothing) -> C
+
+The class of every stored entry of `T̂` for `arcclassposteriors` (mm_batch_set_arc_classes in the header): `classes` is one
+`Vector{<:Integer}` of `nnz` ids for a batch of one shared FSM, or a vector with one such vector per utterance; ids in `-1:C-1`
+(0-based, -1: not counted), in the CSC entry order of `SparseMatrixCSC(fsm.T̂)`.  Host work only; calling it again replaces the plan.
+"""
+function set_arc_classes!(b::ROCBatch, classes::AbstractVector, C = nothing)
+    shared = !(eltype(classes) <: AbstractVector)
+    parts = shared ? [classes] : classes
+    flat = Int32[]
+    offs = Int64[0]
+    for c in parts
+        append!(flat, Int32.(c))
+        push!(offs, length(flat))
+    end
+    nc = C === nothing ? max(1, Int(maximum(flat; init = Int32(0))) + 1) : Int(C)
+    op = shared ? Ptr{Int64}(C_NULL) : pointer(offs)
+    GC.@preserve flat offs check(ccall((:mm_batch_set_arc_classes, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int64}, Int32),
+        b.handle, pointer(flat), op, Int32(nc)))
+    nc
+end
+
+"(cap, max_M, C) of the batch's arc-class plan (mm_batch_arc_class_info): the most classified entries whose terms stay in LDS, the most one utterance of the plan has (-1: no plan), the classes"
+function arc_class_info(b::ROCBatch)
+    cap, m, c = Ref{Int64}(0), Ref{Int64}(0), Ref{Int32}(0)
+    check(ccall((:mm_batch_arc_class_info, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Int32}), b.handle, cap, m, c))
+    (cap = cap[], max_M = m[], C = Int(c[]))
+end
+
+"""
+    arcclassposteriors(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing) -> (ξ, ttl)
+
+Per-frame arc-class posteriors (mm_arcclassposteriors_f32 in the header; Baum-Welch's ξₙ summed by the classes of
+`set_arc_classes!`): `ξ[c, t, u]` (a `C × N × B` array on the device) is the posterior probability that utterance u takes an arc
+of class c - 1 between frames t and t + 1; frames beyond an utterance's length belong to the phony self-loop.
+"""
+function arcclassposteriors(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing)
+    P, N, B = size(V)
+    P == b.P || throw(DimensionMismatch("V has $P pdfs, the FSMs $(b.P)"))
+    nc = max(1, arc_class_info(b).C)
+    ξ = ROCArray{Float32}(undef, nc, N, B)
+    ttl = ROCArray{Float32}(undef, B)
+    lp = lens === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(lens))
+    check(ccall((:mm_arcclassposteriors_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Float32}, Int64, Int64, Int64, Ptr{Float32}, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, lp, N, pointer(ξ), nc * N, nc, 1, pointer(ttl), AMDGPU.stream().stream))
+    ξ, ttl
 end
 
 """

@@ -2,16 +2,17 @@
 
 Host-side mirror of the reference's hot-path interface (src/MarkovModels.jl:14-45:
 FSM, nstates, rawunion, CompiledFSM, batch, compile, expand, alpha-recursion,
-beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, chunkedposteriors, windowbestpath, arcposteriors, weightedposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
+beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, chunkedposteriors, windowbestpath, arcposteriors, arcclassposteriors, weightedposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
 The directory name contains a dot, so load it with
 ``__graft_entry__.load_package()`` (importlib) rather than a plain import.
 """
 from ._lib import LIB_PATH, SYMBOLS, DimensionMismatch, MarkovModelsAMDError  # noqa: F401
-from .fsm import FSM, GeneralStateMap, StateMap, nstates, rawunion, statemap  # noqa: F401
+from .fsm import FSM, GeneralStateMap, StateMap, arc_classes_by_destination, boundary_classes, nstates, rawunion, statemap  # noqa: F401
 from .inference import (  # noqa: F401
     BatchedFSM,
     CompiledFSM,
     alpharecursion,
+    arcclassposteriors,
     arcposteriors,
     batch,
     bestpath,

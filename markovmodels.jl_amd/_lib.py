@@ -49,6 +49,9 @@ SYMBOLS = [
     "mm_svdv",
     "mm_pdfposteriors_f32",
     "mm_arcposteriors_f32",
+    "mm_batch_set_arc_classes",
+    "mm_batch_arc_class_info",
+    "mm_arcclassposteriors_f32",
     "mm_samplepaths_f32",
     "mm_expectedcost_f32",
     "mm_leakyposteriors_f32",
@@ -166,6 +169,12 @@ def _load():
     lib.mm_pdfposteriors_f32.argtypes = [vp, fp, i64, i64, vp, i64, fp, i64, i64, i64, fp, vp]
     lib.mm_arcposteriors_f32.restype = C.c_int
     lib.mm_arcposteriors_f32.argtypes = [vp, fp, i64, i64, vp, i64, fp, i64, fp, i64, fp, vp]
+    lib.mm_batch_set_arc_classes.restype = C.c_int
+    lib.mm_batch_set_arc_classes.argtypes = [vp, vp, vp, i32]
+    lib.mm_batch_arc_class_info.restype = C.c_int
+    lib.mm_batch_arc_class_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]
+    lib.mm_arcclassposteriors_f32.restype = C.c_int
+    lib.mm_arcclassposteriors_f32.argtypes = [vp, fp, i64, i64, vp, i64, fp, i64, i64, i64, fp, vp]
     lib.mm_samplepaths_f32.restype = C.c_int
     lib.mm_samplepaths_f32.argtypes = [vp, fp, i64, i64, vp, i64, i64, i64, vp, i64, i64, fp, i64, fp, vp]
     lib.mm_expectedcost_f32.restype = C.c_int

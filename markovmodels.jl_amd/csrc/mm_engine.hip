@@ -356,6 +356,14 @@ struct mm_batch_s {
     // first call), the slots of all their forward / backward item forms (what a weight plane per utterance holds)
     DevMem d_wforms;
     int64_t w_slots[2] = {0, 0};
+    // arc-class posteriors (mm_arcclassposteriors_f32): the class plan mm_batch_set_arc_classes made on the host -- the utterances'
+    // ClassDev descriptors (pointers as byte offsets into the image until it is uploaded) in front of the records and class
+    // pointers of every distinct (FSM, class array) --, its copy on the device (made by the first call behind a new plan), the
+    // classes, the most ranks of one utterance and the ranks of all
+    std::vector<char> cls_image;
+    DevMem d_cls;
+    int cls_C = 0;
+    int64_t cls_max_M = 0, cls_terms = 0;
 };
 
 static bool on_pairs(mm_batch_t h) { return h->fb == Fb::Pairs || h->fb == Fb::Split; }
@@ -438,13 +446,14 @@ static Geometry pick_geometry(mm_batch_t h) {
 }
 
 // ---- one plan per entry that runs on the item form: its launch geometry and where its state vectors live
-enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter, Window, VitWindow, Weighted, Segment };
+enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter, Window, VitWindow, Weighted, Segment, ArcClass };
 struct ItemPlan {
     ItemEntry e;
     int NW, NI;        // waves per workgroup, register-resident items per wave of the instance (8 or 0)
     bool global;       // the state vectors in global memory (BIGV), else in LDS
     bool stage;        // (Sample) mm_sample_kernel keeps two alpha~ rows in LDS, else it gathers them from global memory
-    size_t lds_bytes;  // dynamic LDS of the chosen placement (Arcs: of the forward kernel; mm_arc_kernel adds MM_ARC_LDS_EXTRA;
+    size_t lds_bytes;  // dynamic LDS of the chosen placement (Arcs, ArcClass: of the forward kernel; mm_arc_kernel adds MM_ARC_LDS_EXTRA,
+                       // mm_arcclass_kernel that and its term rows;
                        // Weighted: of mm_weighted_bwd_kernel -- its forward launch takes the item kernel's plan, as the arc entry's)
 };
 // The only source of the above.  The vectors are global when the entry's LDS plan (the item kernel's, with the stage rows for
@@ -453,6 +462,7 @@ struct ItemPlan {
 // MM_BIGV asks for it, or for the arc, sampling, cost, leaky, entropy, filter, window and segment kernels when NI = 0: they have no
 // streamed-only instance with the vectors in LDS.  VitWindow (tropical batches): the tropical kernel's geometry, its LDS plan + the
 // arc kernel's extra.  Weighted: the arc kernel's size + one row of state posteriors (mm_weighted_lds_bytes), 8 waves like Arcs.
+// ArcClass: the arc entry's plan (its term rows take what LDS the plan leaves, or the workspace: arcclass_cap).
 // `global` never depends on max_items, nor does NI except Tropical's (8: the whole graph is register-resident): mm_batch_create
 // asks before the item forms are up, and ensure_item_forms raises max_items later -- only NW follows it.
 static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
@@ -469,13 +479,13 @@ static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
         return e == ItemEntry::Cost ? mm_cost_lds_bytes(S1p, P1p) : size_t(lds_plan(S1p, P1p, e != ItemEntry::Export).total) * 4;
     };
     const bool derived = e == ItemEntry::Arcs || e == ItemEntry::Sample || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy ||
-                         e == ItemEntry::Filter || e == ItemEntry::Window || e == ItemEntry::Weighted || e == ItemEntry::Segment;
+                         e == ItemEntry::Filter || e == ItemEntry::Window || e == ItemEntry::Weighted || e == ItemEntry::Segment || e == ItemEntry::ArcClass;
     ItemPlan pl{e, g.NW, g.NI, false, false, 0};
-    pl.global = bytes(h->max_S1p) + (e == ItemEntry::Arcs ? MM_ARC_LDS_EXTRA : 0) > lds_max || h->dbg.bigv || (derived && g.NI == 0);
+    pl.global = bytes(h->max_S1p) + (e == ItemEntry::Arcs || e == ItemEntry::ArcClass ? MM_ARC_LDS_EXTRA : 0) > lds_max || h->dbg.bigv || (derived && g.NI == 0);
     pl.lds_bytes = bytes(pl.global ? 0 : h->max_S1p);
     // (8 items' arcs and their sums / the pair arithmetic / the leak term and its sums per wave: compiled for 8 waves per CU)
     if (e == ItemEntry::Arcs || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy || e == ItemEntry::Filter ||
-        e == ItemEntry::Window || e == ItemEntry::Weighted || e == ItemEntry::Segment)
+        e == ItemEntry::Window || e == ItemEntry::Weighted || e == ItemEntry::Segment || e == ItemEntry::ArcClass)
         pl.NW = std::min(g.NW, 8);
     if (e == ItemEntry::Sample) pl.stage = !pl.global && !h->dbg.sample_nostage && size_t(h->max_S1p) * 8 <= lds_max;
     if (e == ItemEntry::Tropical || e == ItemEntry::VitWindow) {
@@ -501,6 +511,11 @@ static void bind_big(mm_batch_t h, const ItemPlan &pl, RunParams &p) {
     p.big_stride = 4ll * h->max_S1p;
 }
 static const char *where_of(bool global) { return global ? "global" : "lds"; }
+// the most ranks of one utterance whose two term rows mm_arcclass_kernel keeps in LDS, behind the arc kernel's plan
+static int64_t arcclass_cap(const ItemPlan &pl) {
+    const size_t used = pl.lds_bytes + MM_ARC_LDS_EXTRA;
+    return used >= MM_LDS_MAX ? 0 : int64_t((MM_LDS_MAX - used) / (2 * sizeof(float)));
+}
 
 // item / tropical kernels: `kernel` keeps the state vectors in LDS; `big` is the same kernel with the vectors in global
 // memory, for FSMs beyond the LDS (the reference has no size limit: src/linalg.jl:170-181)
@@ -2664,6 +2679,13 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
         s = "mm_window_fwd_kernel" + inst + " (forward from the carried start vector: alpha~ stored) + mm_segment_bwd_kernel" + inst +
             " (backward from an open, a closed or a carried end: gamma per pdf, ttl, then the item pass behind frame 1: end_out and lend); state vectors " +
             (pl.global ? "in global memory" : "in LDS");
+    } else if (entry == 14) {  // mm_arcclassposteriors_f32
+        if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_arcclassposteriors_f32 runs on log-semiring batches only");
+        const ItemPlan pl = item_plan(h, ItemEntry::ArcClass);
+        const std::string ni = std::to_string(pl.NI);
+        s = "mm_log_kernel<MODE_FB," + ni + ",1> (forward) + mm_arcclass_kernel<" + ni + "," + where_of(pl.global) +
+            "> (backward: the classified arcs' terms by rank, a row of class sums per frame); state vectors " + (pl.global ? "in global memory" : "in LDS") +
+            (h->cls_image.empty() ? "; no classes set" : h->cls_max_M > arcclass_cap(pl) ? "; terms in global memory" : "; terms in LDS");
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -3105,8 +3127,9 @@ static int item_entry_begin(mm_batch_t h, const char *who, ItemEntry e, const fl
 // frame 1; Cost: the r store and its offsets, and for FSMs beyond the LDS the state vectors of both kernels ([B][8 * max S1p]
 // floats); Entropy: as Cost, the Hf store in the place of the r store -- and no such store for a value-only call (`store` false).
 // total: no less than what mm_pdfposteriors_f32 needs for as many frames.  (mm_batch_reserve does not cover it.)  Filter keeps
-// nothing: its offsets stay in registers, total = 0 whatever N -- the workspace is neither grown nor touched.
-struct ItemWs { size_t c = 0, acc = 0, post1 = 0, r = 0, o = 0, big = 0, plane[2] = {0, 0}, initp = 0, utts = 0, total = 0; };
+// nothing: its offsets stay in registers, total = 0 whatever N -- the workspace is neither grown nor touched.  ArcClass: what Leaky
+// keeps, and the two term rows of every utterance when the plan has more ranks than the LDS holds.
+struct ItemWs { size_t c = 0, acc = 0, post1 = 0, r = 0, o = 0, big = 0, plane[2] = {0, 0}, initp = 0, utts = 0, terms = 0, total = 0; };
 // Weighted: the arc entry's areas, then what the call's weights need (wplanes / wiplanes: 0 none given, 1 one vector for the batch
 // -- the planes of ONE FSM --, 2 a vector per utterance): the {col, w} planes of both item forms, the dense init vectors, the call's
 // descriptors.
@@ -3131,6 +3154,9 @@ static ItemWs item_ws_layout(mm_batch_t h, const ItemPlan &pl, int64_t N, bool s
             W.utts = W.total;
             W.total += align_up(size_t(h->B) * sizeof(UttDesc), 256);
         }
+    } else if (pl.e == ItemEntry::ArcClass) {
+        W.terms = W.total;
+        W.total += h->cls_max_M > arcclass_cap(pl) ? align_up(size_t(h->cls_terms) * 2 * sizeof(float), 256) : 0;
     } else if (ws_holds_big(pl.e)) {
         W.r = W.total;
         W.o = W.r + (store ? rows : 0);
@@ -3253,6 +3279,162 @@ int mm_arcposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
     ap.isb = isb;
     ap.ttl = ttl;
     return mm_launch_arcs(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, p, ap, static_cast<hipStream_t>(stream));
+}
+
+static int check_strides(const std::string &who, const char *name, int64_t sb, int64_t B, int64_t sn, int64_t N, int64_t sp, int64_t P);
+
+// ---- per-frame arc-class posteriors (mm_kernel_arcclass.hip)
+// One class plan: the classified entries of FSM f under the class array cls (f->nnz ids in [-1, C)) ranked by (class, entry), a
+// record each, and the classes' rank ranges.  An entry without a slot (a row without an item: no path takes it) has no rank.
+struct ClassPlanHost {
+    std::vector<ClassRec> recs;
+    std::vector<int32_t> cptr;
+    int cphony = -1;
+};
+static ClassPlanHost make_class_plan(mm_fsm_s &f, const int32_t *cls, int32_t C) {
+    ensure_packed(&f);
+    const Packed &pk = f.packed[1];
+    const std::vector<int32_t> k2slot = pack_k2slot(f);
+    std::vector<int32_t> slot2row(pk.slots.size(), -1);
+    for (size_t it = 0; it < pk.items.size(); ++it)
+        for (int lane = 0; lane < 64; ++lane) {
+            const int32_t row = pk.rowinfo[it * 64 + size_t(lane)].row;
+            for (int k = 0; row >= 0 && k < int(pk.items[it].R); ++k) slot2row[(size_t(pk.items[it].slot_row) + size_t(k)) * 64 + size_t(lane)] = row;
+        }
+    ClassPlanHost pl;
+    pl.cptr.assign(size_t(C) + 1, 0);
+    for (int64_t k = 0; k < f.nnz; ++k)
+        if (cls[k] >= 0 && k2slot[size_t(k)] >= 0) ++pl.cptr[size_t(cls[k]) + 1];
+    for (int32_t c = 0; c < C; ++c) pl.cptr[size_t(c) + 1] += pl.cptr[size_t(c)];
+    pl.recs.resize(size_t(pl.cptr[size_t(C)]));
+    std::vector<int32_t> cur(pl.cptr.begin(), pl.cptr.end() - 1);
+    for (int64_t k = 0; k < f.nnz; ++k) {  // (k ascending: a class's ranks follow the caller's entry order)
+        const int32_t s = k2slot[size_t(k)];
+        if (cls[k] < 0 || s < 0) continue;
+        const Slot &sl = pk.slots[size_t(s)];
+        pl.recs[size_t(cur[size_t(cls[k])]++)] = ClassRec{slot2row[size_t(s)], int(sl.col), sl.w, int(k)};
+    }
+    if (f.kphony >= 0) pl.cphony = cls[f.kphony];
+    return pl;
+}
+
+int mm_batch_set_arc_classes(mm_batch_t h, const int32_t *cls, const int64_t *offsets, int32_t C) {
+    const std::string who = "mm_batch_set_arc_classes";
+    if (!h || !cls) return fail(MM_ERR_INVALID, who + ": NULL argument");
+    if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, who + ": log-semiring batches only");
+    if (C < 1) return fail(MM_ERR_INVALID, who + ": need C >= 1 classes, got " + std::to_string(C));
+    const size_t B = size_t(h->B);
+    for (size_t b = 0; b < B; ++b) {
+        const mm_fsm_s &f = *h->fsms[b];
+        if (f.nnz > INT32_MAX) return fail(MM_ERR_UNSUPPORTED, who + ": more than 2^31 - 1 arcs in one FSM");
+        if (!offsets && h->fsms[b] != h->fsms[0]) return fail(MM_ERR_INVALID, who + ": one class array (offsets NULL) needs a batch of one shared FSM");
+        if (offsets && offsets[b + 1] - offsets[b] != f.nnz)
+            return fail(MM_ERR_DIM, who + ": utterance " + std::to_string(b) + " has " + std::to_string(offsets[b + 1] - offsets[b]) + " class ids for " +
+                                        std::to_string(f.nnz) + " entries");
+        const int32_t *cb = cls + (offsets ? offsets[b] : 0);
+        for (int64_t k = 0; k < f.nnz && (offsets || b == 0); ++k)
+            if (cb[k] < -1 || cb[k] >= C)
+                return fail(MM_ERR_INVALID, who + ": class id " + std::to_string(cb[k]) + " of entry " + std::to_string(k) + " of utterance " + std::to_string(b) +
+                                                " is outside [-1, " + std::to_string(C) + ")");
+    }
+    return no_throw(who.c_str(), [&]() {
+        // one plan per distinct (FSM, class array); the image: [B] descriptors, then per plan its records and class pointers
+        struct Made { const mm_fsm_s *f; const int32_t *cls; size_t o_recs, o_cptr; int M, cphony; };
+        std::vector<Made> made;
+        std::vector<ClassDev> descs(B);
+        Blob bl;
+        (void)bl.add(descs);  // (at 0; filled in below)
+        int64_t terms = 0, max_M = 0;
+        for (size_t b = 0; b < B; ++b) {
+            mm_fsm_s &f = *h->fsms[b];
+            const int32_t *cb = cls + (offsets ? offsets[b] : 0);
+            const Made *m = nullptr;
+            for (const Made &c : made)
+                if (c.f == &f && (c.cls == cb || std::equal(cb, cb + f.nnz, c.cls))) m = &c;
+            if (!m) {
+                const ClassPlanHost pl = make_class_plan(f, cb, C);
+                const size_t o_recs = bl.add(pl.recs);
+                made.push_back(Made{&f, cb, o_recs, bl.add(pl.cptr), int(pl.recs.size()), pl.cphony});
+                m = &made.back();
+            }
+            ClassDev &d = descs[b];
+            d.recs = reinterpret_cast<const ClassRec *>(m->o_recs);
+            d.cptr = reinterpret_cast<const int *>(m->o_cptr);
+            d.term_off = terms;
+            d.M = m->M;
+            d.C = C;
+            d.cphony = m->cphony;
+            d.lgl = m->M >= 32ll * C ? 6 : (m->M >= 2ll * C ? 3 : 0);
+            terms += m->M;
+            max_M = std::max<int64_t>(max_M, m->M);
+        }
+        memcpy(bl.host.data(), descs.data(), sizeof(ClassDev) * B);
+        h->cls_image = std::move(bl.host);
+        h->d_cls = DevMem();  // (the next mm_arcclassposteriors_f32 call uploads the new plan)
+        h->cls_C = C;
+        h->cls_max_M = max_M;
+        h->cls_terms = terms;
+        return int(MM_OK);
+    });
+}
+
+int mm_batch_arc_class_info(mm_batch_t h, int64_t *cap, int64_t *max_M, int32_t *C) {
+    if (!h) return fail(MM_ERR_INVALID, "mm_batch_arc_class_info: NULL batch");
+    if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_arc_class_info: log-semiring batches only");
+    if (cap) *cap = arcclass_cap(item_plan(h, ItemEntry::ArcClass));
+    if (max_M) *max_M = h->cls_image.empty() ? -1 : h->cls_max_M;
+    if (C) *C = h->cls_C;
+    return MM_OK;
+}
+
+// the plan on the device: one allocation, one copy -- made by the first call behind mm_batch_set_arc_classes, never during a capture
+static int ensure_class_plan(mm_batch_t h, void *stream) {
+    if (h->d_cls) return MM_OK;
+    if (capturing(stream))
+        return fail(MM_ERR_INVALID, "the class plan of this batch is not on the device yet: run mm_arcclassposteriors_f32 once outside a stream capture");
+    void *d = nullptr;
+    HIP_TRY(hipMalloc(&d, h->cls_image.size()));
+    DevMem own(d);
+    std::vector<char> img = h->cls_image;  // (the descriptors' offsets become pointers into the allocation)
+    ClassDev *descs = reinterpret_cast<ClassDev *>(img.data());
+    for (int64_t b = 0; b < h->B; ++b) {
+        descs[b].recs = reinterpret_cast<const ClassRec *>(static_cast<char *>(d) + reinterpret_cast<size_t>(descs[b].recs));
+        descs[b].cptr = reinterpret_cast<const int *>(static_cast<char *>(d) + reinterpret_cast<size_t>(descs[b].cptr));
+    }
+    if (hipMemcpy(d, img.data(), img.size(), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(MM_ERR_HIP, "mm_arcclassposteriors_f32: upload of the class plan failed");
+    h->d_cls = std::move(own);
+    return MM_OK;
+}
+
+int mm_arcclassposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, float *xi, int64_t xsb,
+                              int64_t xsn, int64_t xsc, float *ttl, void *stream) {
+    const std::string who = "mm_arcclassposteriors_f32";
+    ItemPlan pl;
+    int rc = item_entry_begin(h, who.c_str(), ItemEntry::ArcClass, V, N, stream, [&]() {
+        if (!xi) return fail(MM_ERR_INVALID, who + ": xi is NULL");
+        if (h->cls_image.empty()) return fail(MM_ERR_INVALID, who + ": no classes set (mm_batch_set_arc_classes)");
+        return check_strides(who, "x", xsb, h->B, xsn, N, xsc, h->cls_C);
+    }, &pl);
+    if (rc) return rc;
+    rc = ensure_class_plan(h, stream);
+    if (rc) return rc;
+    const ItemWs W = item_ws_layout(h, pl, N);
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    rc = item_ws_bind(h, pl, W, p, stream);
+    if (rc) return rc;
+    const bool tg = h->cls_max_M > arcclass_cap(pl);
+    ArcClassParams cp{};
+    cp.cls = static_cast<const ClassDev *>(h->d_cls.get());
+    cp.terms = reinterpret_cast<float *>(static_cast<char *>(h->ws) + W.terms);
+    cp.terms_global = tg ? 1 : 0;
+    cp.xi = xi;
+    cp.xsb = xsb;
+    cp.xsn = xsn;
+    cp.xsc = xsc;
+    cp.ttl = ttl;
+    return mm_launch_arcclass(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, tg ? 0 : size_t(h->cls_max_M) * 2 * sizeof(float), p, cp,
+                              static_cast<hipStream_t>(stream));
 }
 
 // ---- expected path cost and its gradient (mm_kernel_cost.hip)

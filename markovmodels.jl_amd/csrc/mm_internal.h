@@ -216,6 +216,32 @@ struct ArcParams {
 // NI: register-resident items per wave (8, or 0 for FSMs of more than 65534 states); bigv: the state vectors in global memory
 int mm_launch_arcs(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, const RunParams &p, const ArcParams &ap, hipStream_t stream);
 
+// ---- per-frame arc-class posteriors (mm_arcclass_tu.hip: mm_log_kernel's forward half, then mm_arcclass_kernel on the item form)
+struct alignas(16) ClassRec {  // one classified entry i -> j, at its rank (sorted by class, then by the caller's entry index)
+    int row, col;              // i, j
+    float w;                   // log2 T_hat_ij, the weight of the entry's slot of the backward item form
+    int k;                     // the caller's entry
+};
+struct ClassDev {  // one utterance's class plan (mm_engine.hip mm_batch_set_arc_classes)
+    const ClassRec *recs;  // [M]
+    const int *cptr;       // [C + 1] class c owns the ranks [cptr[c], cptr[c + 1])
+    long long term_off;    // the ranks of the utterances before this one (its rows in ArcClassParams::terms start at 2 * term_off)
+    int M, C;
+    int cphony;  // class of the phony self-loop (final -> final), -1: none
+    int lgl;     // log2 of the lanes that sum one class: 0, 3 or 6 by the plan's mean class size
+};
+struct ArcClassParams {
+    const ClassDev *cls;  // [B]
+    float *terms;         // per utterance [2][M] in the workspace; read when terms_global
+    int terms_global;     // 0: the term rows live in LDS behind the arc kernel's plan
+    float *xi;
+    long long xsb, xsn, xsc;
+    float *ttl;  // NULL: not asked for
+};
+// lds_bytes: the item kernel's plan, as mm_launch_arcs; term_lds: bytes of the term rows in LDS (0: they are global)
+int mm_launch_arcclass(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, size_t term_lds, const RunParams &p, const ArcClassParams &cp,
+                       hipStream_t stream);
+
 // ---- posterior path sampling (mm_sample_tu.hip: mm_log_kernel's forward half, then mm_sample_kernel on the sampling form)
 #define MM_SAMPLE_NW 8  // waves of a workgroup of mm_sample_kernel that run chains (+ one that stages the alpha~ rows)
 #define MM_SAMPLE_CW 8  // the most chains one wave carries in registers (1, 2, 4 or 8: mm_sample_tu.hip sample_cw)

@@ -229,6 +229,41 @@ def nstates(fsm: FSM) -> int:
     return fsm.S1 - 1
 
 
+def _entry_ends(fsm: FSM) -> Tuple[np.ndarray, np.ndarray]:
+    """(source i_k, destination j_k) of every stored entry of T_hat, in the order of ``FSM.nzval``."""
+    return np.asarray(fsm.rowval, dtype=np.int64), np.repeat(np.arange(fsm.S1, dtype=np.int64), np.diff(fsm.colptr))
+
+
+def _per_state(fsm: FSM, values, what: str) -> np.ndarray:
+    """``values`` for the S real states, or for all S + 1: as int64[S + 1], the phony final state -1 when it was left out."""
+    v = np.asarray(values, dtype=np.int64).ravel()
+    if v.size == fsm.S1 - 1:
+        v = np.concatenate([v, [-1]])
+    if v.size != fsm.S1:
+        raise ValueError(f"{what} needs one entry per state ({fsm.S1 - 1}, or {fsm.S1} with the phony final state), got {v.size}")
+    return v
+
+
+def arc_classes_by_destination(fsm: FSM, state_class) -> np.ndarray:
+    """Arc classes for ``BatchedFSM.set_arc_classes``: the class of entry k = (i_k -> j_k) is ``state_class[j_k]`` -- phones or
+    words of the state an arc enters, or ``C_hat.state2pdf`` (all S + 1 entries) for the posteriors of the next frame's pdfs.
+    ``state_class`` has S entries (the arcs into the phony final state, its self-loop included, then get -1) or S + 1."""
+    _, dst = _entry_ends(fsm)
+    return _per_state(fsm, state_class, "arc_classes_by_destination")[dst].astype(np.int32)
+
+
+def boundary_classes(fsm: FSM, state_group) -> np.ndarray:
+    """Arc classes that mark boundaries: entry k = (i_k -> j_k) gets ``state_group[j_k]`` when ``state_group[i_k] !=
+    state_group[j_k]`` -- an arc that enters group g from outside it is a boundary of g --, else -1.  The phony entries (the
+    final column and the self-loop) get -1.  With the words (phones, segments) of the states as groups, the row of group g that
+    ``arcclassposteriors`` returns is P(g starts at frame t + 1)."""
+    src, dst = _entry_ends(fsm)
+    g = _per_state(fsm, state_group, "boundary_classes")
+    S = fsm.S1 - 1
+    out = np.where((g[src] != g[dst]) & (src < S) & (dst < S), g[dst], -1)
+    return out.astype(np.int32)
+
+
 def rawunion(*fsms: FSM) -> FSM:
     """rawunion(fsms...) (src/fsmops.jl:28-36): vcat of the alpha_hat's and
     blockdiag of the T_hat's -- several independent FSMs (each keeping its own

@@ -407,6 +407,55 @@ class BatchedFSM:
         out = (counts, ttl) + ((init,) if want_init else ())
         return tuple(t.cpu().numpy() for t in out) if as_numpy else out
 
+    def set_arc_classes(self, classes, C=None):
+        """The class of every stored entry of ``T_hat`` for ``arcclassposteriors`` (mm_batch_set_arc_classes): ``classes`` is one
+        int array of ``nnz`` ids for a batch of one shared FSM, or a list with one array per utterance; ids in ``[-1, C)``, -1 = not
+        counted, in the order of ``FSM.nzval`` (phony final column and self-loop included).  ``C`` defaults to the largest id + 1.
+        Host work only; calling it again replaces the plan.  Not during a stream capture.  Returns C."""
+        torch = _torch()
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise _lib.MarkovModelsAMDError(-1, "set_arc_classes: the class plan cannot be replaced during a stream capture")
+        shared = not isinstance(classes, (list, tuple))
+        arrs = [np.ascontiguousarray(c, dtype=np.int32).ravel() for c in ([classes] if shared else classes)]
+        if not shared and len(arrs) != self.B:
+            raise _lib.DimensionMismatch(-2, f"need one class array per utterance: got {len(arrs)} for B={self.B}")
+        if C is None:
+            C = max(1, max((int(a.max()) + 1 for a in arrs if a.size), default=1))
+        if shared:
+            if arrs[0].size != self.cfsms[0].fsm.nnz:
+                raise _lib.DimensionMismatch(-2, f"classes has {arrs[0].size} ids, the FSM {self.cfsms[0].fsm.nnz} entries")
+            check(lib.mm_batch_set_arc_classes(self._h, arrs[0].ctypes.data, None, int(C)))
+        else:
+            flat = np.ascontiguousarray(np.concatenate(arrs), dtype=np.int32)
+            offs = np.cumsum([0] + [a.size for a in arrs]).astype(np.int64)
+            check(lib.mm_batch_set_arc_classes(self._h, flat.ctypes.data, offs.ctypes.data, int(C)))
+        return int(C)
+
+    def info(self) -> dict:
+        """What the batch knows about its arc-class plan (mm_batch_arc_class_info): ``arcclass_cap`` = the most classified entries
+        of one utterance whose per-frame terms ``arcclassposteriors`` keeps in LDS (beyond it: in the workspace), ``arcclass_max_M``
+        = the most any utterance of the current plan has (-1: no plan), ``arcclass_C``.  Log batches only."""
+        cap, m, c = C.c_int64(), C.c_int64(), C.c_int32()
+        check(lib.mm_batch_arc_class_info(self._h, C.byref(cap), C.byref(m), C.byref(c)))
+        return dict(arcclass_cap=cap.value, arcclass_max_M=m.value, arcclass_C=c.value)
+
+    def arcclassposteriors(self, V, lens=None):
+        """Per-frame arc-class posteriors (mm_arcclassposteriors_f32), Baum-Welch's xi_n summed by the classes ``set_arc_classes``
+        gave: ``(xi[B, C, N], ttl[B])``.  ``xi[b, c, t]`` is the posterior probability that utterance b takes an arc of class c between
+        frames t and t + 1 (0-based; t = len - 1: an arc into the phony final state; t >= len: the phony self-loop, exactly 1.0 for
+        its class and 0.0 elsewhere).  The result is a view of a ``[B, N, C]`` buffer (a frame's classes are adjacent in memory).
+        No atomics: bit-identical from call to call.  Log batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        nc = max(1, self.info()["arcclass_C"])  # (no plan: the library refuses the call)
+        buf = torch.empty((B, N, nc), dtype=torch.float32, device=Vt.device)
+        ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        check(lib.mm_arcclassposteriors_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
+                                            lt.data_ptr() if lt is not None else None, N, buf.data_ptr(), buf.stride(0), buf.stride(1),
+                                            buf.stride(2), ttl.data_ptr(), self._stream(torch)))
+        xi = buf.permute(0, 2, 1)
+        return (np.ascontiguousarray(xi.cpu().numpy()), ttl.cpu().numpy()) if as_numpy else (xi, ttl)
+
     def weightedposteriors(self, V, W=None, W_init=None, lens=None, want_gamma=True, want_counts=True, want_init=False, out=None):
         """Posteriors with call-time arc weights (mm_weightedposteriors_f32): ``(gamma[B, N, P], counts[B, max nnz], ttl[B])``, plus
         ``init[B, max n_init]`` with ``want_init``; what ``want_gamma`` / ``want_counts`` do not ask for comes back as None.  The
@@ -860,7 +909,7 @@ class BatchedFSM:
         import ctypes
 
         buf = ctypes.create_string_buffer(1024)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13}[semiring], buf, 1024))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13, "arcclass": 14}[semiring], buf, 1024))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -1318,6 +1367,16 @@ def arcposteriors(fsm, Vhats, Chats=None, want_init=False):
     bf = _as_batch(fsm, Chats)
     V, lens = _need_expanded(Vhats, bf.semiring)
     return bf.arcposteriors(V, lens, want_init=want_init)
+
+
+def arcclassposteriors(fsm, Vhats, classes, Chats=None, C=None):
+    """Per-frame arc-class posteriors (Baum-Welch's xi_n summed by class): ``(xi[B, C, N], ttl[B])`` -- see
+    ``BatchedFSM.set_arc_classes`` / ``BatchedFSM.arcclassposteriors``.  ``fsm`` and the V_hats as for ``arcposteriors``;
+    ``classes``: one id array for a batch that repeats one FSM, or a list with one per utterance.  NumPy arrays out."""
+    bf = _as_batch(fsm, Chats)
+    V, lens = _need_expanded(Vhats, bf.semiring)
+    bf.set_arc_classes(classes, C)
+    return bf.arcclassposteriors(V, lens)
 
 
 def weightedposteriors(fsm, Vhats, W, Chats=None, W_init=None, seqlengths=None):
