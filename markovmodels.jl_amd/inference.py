@@ -38,6 +38,76 @@ def _torch():
     return torch
 
 
+# ---- what the BatchedFSM entries check, allocate and pass alike.  The kernels write through the raw pointers and strides this layer
+# hands over: a wrong buffer is memory corruption, not an exception.  Functions of the tensor and of the device or shape it must
+# match, not of a batch, so that they run on CPU tensors as well.
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _head(h, Vt, lt, N):
+    """What the argument list of every entry starts with: the batch, V and its strides, the lengths, N."""
+    return h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1), _ptr(lt), N
+
+
+def _out_buffer(out, shape, device):
+    """The ``out`` of a call, a float32 tensor [B, N, P] on V's device with strides of its own, or a fresh buffer."""
+    import torch
+
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != device:
+        raise TypeError("out must be a float32 tensor on V's device")
+    if tuple(out.shape) != tuple(shape):
+        B, N, P = shape
+        raise _lib.DimensionMismatch(-2, f"out must be [B={B}, N={N}, P={P}], got {tuple(out.shape)}")
+    return out
+
+
+def _state_vector(x, name, n, device):
+    """A carried vector (``state``, ``end``, or the tensor that receives one): float32, contiguous [n = total_states], on V's device.
+    What is not a tensor goes there through NumPy; None passes."""
+    import torch
+
+    if x is None:
+        return None
+    if not isinstance(x, torch.Tensor):
+        x = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32))
+        if device.type == "cuda":  # (the current device: the check below compares it with V's)
+            x = x.cuda()
+    if x.dtype != torch.float32 or x.device != device:
+        raise TypeError(f"{name} must be a float32 tensor on V's device")
+    if x.dim() != 1 or x.numel() != n or not x.is_contiguous():
+        raise _lib.DimensionMismatch(-2, f"{name} must be a contiguous [{n}] vector, got {tuple(x.shape)}")
+    return x
+
+
+def _want_vector(want, name, n, device):
+    """``want_state`` / ``want_end``: the tensor that receives the vector (checked), or whether to make one; None if not wanted."""
+    import torch
+
+    if isinstance(want, torch.Tensor):
+        return _state_vector(want, name, n, device)
+    return torch.empty(n, dtype=torch.float32, device=device) if want else None
+
+
+def _per_utt(x, name, B, device):
+    """A per-utterance argument (``closed``, ``commit``, ``end_mode``) as a contiguous int32 [B] tensor on V's device; None passes."""
+    import torch
+
+    if x is None:
+        return None
+    t = x.to(device=device, dtype=torch.int32) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.int32)).to(device)
+    if t.dim() != 1 or t.numel() != B:
+        raise _lib.DimensionMismatch(-2, f"{name} must be a [{B}] vector, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _results(res, as_numpy):
+    """The tuple an entry returns: NumPy arrays if V came as NumPy, None members as they are."""
+    return tuple(t.cpu().numpy() if t is not None else None for t in res) if as_numpy else res
+
+
 class CompiledFSM:
     """CompiledFSM{K} (src/inference.jl:3-12): alpha_hat, T_hat, T_hat', C_hat, C_hat'
     prepared once -- here as the packed device forms the kernels stream."""
@@ -270,20 +340,10 @@ class BatchedFSM:
         """One call of the engine: gamma[B, N, P] (probabilities), ttl[B]."""
         torch, Vt, lt, as_numpy = self._prep(V, lens)
         B, N, P = Vt.shape
-        if out is not None:
-            # the kernels write through raw pointers and strides: a wrong buffer is memory corruption, not an exception
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != Vt.device:
-                raise TypeError("out must be a float32 tensor on V's device")
-            if out.dim() != 3 or tuple(out.shape) != (B, N, P):
-                raise _lib.DimensionMismatch(-2, f"out must be [B={B}, N={N}, P={P}], got {tuple(out.shape)}")
-        gamma = out if out is not None else torch.empty((B, N, P), dtype=torch.float32, device=Vt.device)
+        gamma = _out_buffer(out, (B, N, P), Vt.device)
         ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
-        check(lib.mm_pdfposteriors_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
-                                       lt.data_ptr() if lt is not None else None, N, gamma.data_ptr(), gamma.stride(0),
-                                       gamma.stride(1), gamma.stride(2), ttl.data_ptr(), self._stream(torch)))
-        if as_numpy:
-            return gamma.cpu().numpy(), ttl.cpu().numpy()
-        return gamma, ttl
+        check(lib.mm_pdfposteriors_f32(*_head(self._h, Vt, lt, N), gamma.data_ptr(), *gamma.stride(), ttl.data_ptr(), self._stream(torch)))
+        return _results((gamma, ttl), as_numpy)
 
     def has_fast_entry(self) -> bool:
         """True if ``pdfposteriors(V, lens)`` -- mm_pdfposteriors_f32, the fast kernels -- serves this batch: Log batches always,
@@ -380,8 +440,7 @@ class BatchedFSM:
         torch, Vt, lt, as_numpy = self._prep(V, lens)
         B, N, P = Vt.shape
         out = torch.empty((N + 1, self.total_states), dtype=torch.float32, device=Vt.device)
-        check(fn(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1), lt.data_ptr() if lt is not None else None, N,
-                 out.data_ptr(), out.stride(0), self._stream(torch)))
+        check(fn(*_head(self._h, Vt, lt, N), out.data_ptr(), out.stride(0), self._stream(torch)))
         out = out.t()  # (sum S1) x (N+1) like the reference's state_A / state_B
         return out.cpu().numpy() if as_numpy else out
 
@@ -400,12 +459,9 @@ class BatchedFSM:
         if want_init:
             I = max(1, max(len(c.fsm.alpha_idx) for c in self.cfsms))
             init = torch.zeros((B, I), dtype=torch.float32, device=Vt.device)
-        check(lib.mm_arcposteriors_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
-                                       lt.data_ptr() if lt is not None else None, N, counts.data_ptr(), counts.stride(0),
-                                       init.data_ptr() if init is not None else None, init.stride(0) if init is not None else 0,
-                                       ttl.data_ptr(), self._stream(torch)))
-        out = (counts, ttl) + ((init,) if want_init else ())
-        return tuple(t.cpu().numpy() for t in out) if as_numpy else out
+        check(lib.mm_arcposteriors_f32(*_head(self._h, Vt, lt, N), counts.data_ptr(), counts.stride(0), _ptr(init),
+                                       init.stride(0) if init is not None else 0, ttl.data_ptr(), self._stream(torch)))
+        return _results((counts, ttl) + ((init,) if want_init else ()), as_numpy)
 
     def set_arc_classes(self, classes, C=None):
         """The class of every stored entry of ``T_hat`` for ``arcclassposteriors`` (mm_batch_set_arc_classes): ``classes`` is one
@@ -450,11 +506,9 @@ class BatchedFSM:
         nc = max(1, self.info()["arcclass_C"])  # (no plan: the library refuses the call)
         buf = torch.empty((B, N, nc), dtype=torch.float32, device=Vt.device)
         ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
-        check(lib.mm_arcclassposteriors_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
-                                            lt.data_ptr() if lt is not None else None, N, buf.data_ptr(), buf.stride(0), buf.stride(1),
-                                            buf.stride(2), ttl.data_ptr(), self._stream(torch)))
-        xi = buf.permute(0, 2, 1)
-        return (np.ascontiguousarray(xi.cpu().numpy()), ttl.cpu().numpy()) if as_numpy else (xi, ttl)
+        check(lib.mm_arcclassposteriors_f32(*_head(self._h, Vt, lt, N), buf.data_ptr(), *buf.stride(), ttl.data_ptr(), self._stream(torch)))
+        xi, ttl = _results((buf.permute(0, 2, 1), ttl), as_numpy)
+        return (np.ascontiguousarray(xi) if as_numpy else xi), ttl
 
     def weightedposteriors(self, V, W=None, W_init=None, lens=None, want_gamma=True, want_counts=True, want_init=False, out=None):
         """Posteriors with call-time arc weights (mm_weightedposteriors_f32): ``(gamma[B, N, P], counts[B, max nnz], ttl[B])``, plus
@@ -491,23 +545,14 @@ class BatchedFSM:
 
         Wt, wsb = weights(W, K, "W")
         Wi, wisb = weights(W_init, max(len(c.fsm.alpha_idx) for c in self.cfsms), "W_init")
-        gamma = None
-        if want_gamma:
-            if out is not None:
-                if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != Vt.device:
-                    raise TypeError("out must be a float32 tensor on V's device")
-                if tuple(out.shape) != (B, N, P):
-                    raise _lib.DimensionMismatch(-2, f"out must be [B={B}, N={N}, P={P}], got {tuple(out.shape)}")
-            gamma = out if out is not None else torch.empty((B, N, P), dtype=torch.float32, device=Vt.device)
+        gamma = _out_buffer(out, (B, N, P), Vt.device) if want_gamma else None
         counts = torch.zeros((B, K), dtype=torch.float32, device=Vt.device) if want_counts else None
         init = torch.zeros((B, I), dtype=torch.float32, device=Vt.device) if want_init else None
         ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
-        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-        check(lib.mm_weightedposteriors_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1), ptr(lt), N, ptr(Wt), wsb, ptr(Wi), wisb,
-                                            ptr(gamma), *(gamma.stride() if gamma is not None else (0, 0, 0)),
-                                            ptr(counts), K, ptr(init), I, ttl.data_ptr(), self._stream(torch)))
-        res = (gamma, counts, ttl) + ((init,) if want_init else ())
-        return tuple(t.cpu().numpy() if t is not None else None for t in res) if as_numpy else res
+        check(lib.mm_weightedposteriors_f32(*_head(self._h, Vt, lt, N), _ptr(Wt), wsb, _ptr(Wi), wisb,
+                                            _ptr(gamma), *(gamma.stride() if gamma is not None else (0, 0, 0)),
+                                            _ptr(counts), K, _ptr(init), I, ttl.data_ptr(), self._stream(torch)))
+        return _results((gamma, counts, ttl) + ((init,) if want_init else ()), as_numpy)
 
     def samplepaths(self, V, lens=None, nsamples=1, seed=0, want_logprob=False):
         """Posterior path samples (mm_samplepaths_f32): ``(paths[B, K, N] int32, ttl[B])``, plus ``logprob[B, K]`` when
@@ -522,13 +567,9 @@ class BatchedFSM:
         paths = torch.empty((B, max(K, 0), N), dtype=torch.int32, device=Vt.device)
         ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
         lp = torch.empty((B, max(K, 0)), dtype=torch.float32, device=Vt.device) if want_logprob else None
-        check(lib.mm_samplepaths_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
-                                     lt.data_ptr() if lt is not None else None, N, K, int(seed),
-                                     paths.data_ptr(), max(K, 0) * N, N,
-                                     lp.data_ptr() if lp is not None else None, max(K, 0) if lp is not None else 0,
-                                     ttl.data_ptr(), self._stream(torch)))
-        out = (paths, ttl) + ((lp,) if want_logprob else ())
-        return tuple(t.cpu().numpy() for t in out) if as_numpy else out
+        check(lib.mm_samplepaths_f32(*_head(self._h, Vt, lt, N), K, int(seed), paths.data_ptr(), max(K, 0) * N, N,
+                                     _ptr(lp), max(K, 0) if lp is not None else 0, ttl.data_ptr(), self._stream(torch)))
+        return _results((paths, ttl) + ((lp,) if want_logprob else ()), as_numpy)
 
     def expectedcost(self, V, cost, lens=None, want_gamma=False):
         """Expected path cost under the path posterior and its gradient (mm_expectedcost_f32): ``(risk[B], grad[B, N, P],
@@ -550,12 +591,9 @@ class BatchedFSM:
         ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
         grad = torch.empty((B, N, P), dtype=torch.float32, device=Vt.device)
         gamma = torch.empty((B, N, P), dtype=torch.float32, device=Vt.device) if want_gamma else None
-        check(lib.mm_expectedcost_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
-                                      lt.data_ptr() if lt is not None else None, N, Ct.data_ptr(), Ct.stride(0), Ct.stride(1),
-                                      risk.data_ptr(), grad.data_ptr(), gamma.data_ptr() if gamma is not None else None,
-                                      grad.stride(0), grad.stride(1), grad.stride(2), ttl.data_ptr(), self._stream(torch)))
-        out = (risk, grad, ttl) + ((gamma,) if want_gamma else ())
-        return tuple(t.cpu().numpy() for t in out) if as_numpy else out
+        check(lib.mm_expectedcost_f32(*_head(self._h, Vt, lt, N), Ct.data_ptr(), Ct.stride(0), Ct.stride(1), risk.data_ptr(),
+                                      grad.data_ptr(), _ptr(gamma), *grad.stride(), ttl.data_ptr(), self._stream(torch)))
+        return _results((risk, grad, ttl) + ((gamma,) if want_gamma else ()), as_numpy)
 
     def pathentropy(self, V, lens=None, want_grad=True, want_gamma=False):
         """Entropy of the posterior over complete paths and its gradient (mm_pathentropy_f32): ``(entropy[B], grad[B, N, P],
@@ -570,12 +608,11 @@ class BatchedFSM:
         ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
         grad = torch.empty((B, N, P), dtype=torch.float32, device=Vt.device) if want_grad else None
         gamma = torch.empty((B, N, P), dtype=torch.float32, device=Vt.device) if want_gamma else None
-        check(lib.mm_pathentropy_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
-                                     lt.data_ptr() if lt is not None else None, N, ent.data_ptr(),
-                                     grad.data_ptr() if grad is not None else None, gamma.data_ptr() if gamma is not None else None,
-                                     N * P, P, 1, ttl.data_ptr(), self._stream(torch)))
-        out = (ent, grad, ttl) + ((gamma,) if want_gamma else ())
-        return tuple(t.cpu().numpy() if t is not None else None for t in out) if as_numpy else out
+        kept = grad if grad is not None else gamma  # the entry takes ONE set of strides for the two
+        assert grad is None or gamma is None or grad.stride() == gamma.stride()
+        check(lib.mm_pathentropy_f32(*_head(self._h, Vt, lt, N), ent.data_ptr(), _ptr(grad), _ptr(gamma),
+                                     *(kept.stride() if kept is not None else (N * P, P, 1)), ttl.data_ptr(), self._stream(torch)))
+        return _results((ent, grad, ttl) + ((gamma,) if want_gamma else ()), as_numpy)
 
     def leakyposteriors(self, V, lens=None, leak=1e-5, out=None):
         """Pdf posteriors of the leaky HMM (mm_leakyposteriors_f32): ``(gamma[B, N, P], ttl[B])`` as ``pdfposteriors`` returns
@@ -586,20 +623,11 @@ class BatchedFSM:
         ``pdfposteriors``.  Log batches only."""
         torch, Vt, lt, as_numpy = self._prep(V, lens)
         B, N, P = Vt.shape
-        if out is not None:
-            # the kernels write through raw pointers and strides: a wrong buffer is memory corruption, not an exception
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != Vt.device:
-                raise TypeError("out must be a float32 tensor on V's device")
-            if out.dim() != 3 or tuple(out.shape) != (B, N, P):
-                raise _lib.DimensionMismatch(-2, f"out must be [B={B}, N={N}, P={P}], got {tuple(out.shape)}")
-        gamma = out if out is not None else torch.empty((B, N, P), dtype=torch.float32, device=Vt.device)
+        gamma = _out_buffer(out, (B, N, P), Vt.device)
         ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
-        check(lib.mm_leakyposteriors_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
-                                         lt.data_ptr() if lt is not None else None, N, float(leak), gamma.data_ptr(),
-                                         gamma.stride(0), gamma.stride(1), gamma.stride(2), ttl.data_ptr(), self._stream(torch)))
-        if as_numpy:
-            return gamma.cpu().numpy(), ttl.cpu().numpy()
-        return gamma, ttl
+        check(lib.mm_leakyposteriors_f32(*_head(self._h, Vt, lt, N), float(leak), gamma.data_ptr(), *gamma.stride(), ttl.data_ptr(),
+                                         self._stream(torch)))
+        return _results((gamma, ttl), as_numpy)
 
     def filterposteriors(self, V, lens=None, state=None, out=None, want_state=False, want_filt=True):
         """Forward filtering posteriors with a carried state (mm_filterposteriors_f32): ``(filt[B, N, P], incr[B, N], ttl[B])``,
@@ -617,41 +645,17 @@ class BatchedFSM:
         without a live state on ``filt`` = 0 and ``incr`` = -inf.  No frame is kept: the call uses no workspace.  Log batches only."""
         torch, Vt, lt, as_numpy = self._prep(V, lens)
         B, N, P = Vt.shape
-        if out is not None:
-            # the kernels write through raw pointers and strides: a wrong buffer is memory corruption, not an exception
-            if not want_filt:
-                raise ValueError("out given with want_filt=False")
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != Vt.device:
-                raise TypeError("out must be a float32 tensor on V's device")
-            if out.dim() != 3 or tuple(out.shape) != (B, N, P):
-                raise _lib.DimensionMismatch(-2, f"out must be [B={B}, N={N}, P={P}], got {tuple(out.shape)}")
-        st = None
-        if state is not None:
-            st = torch.as_tensor(np.ascontiguousarray(state, dtype=np.float32)).cuda() if not isinstance(state, torch.Tensor) else state
-            if st.dtype != torch.float32 or st.device != Vt.device:
-                raise TypeError("state must be a float32 tensor on V's device")
-            if st.dim() != 1 or st.numel() != self.total_states or not st.is_contiguous():
-                raise _lib.DimensionMismatch(-2, f"state must be a contiguous [{self.total_states}] vector, got {tuple(st.shape)}")
-        filt = (out if out is not None else torch.empty((B, N, P), dtype=torch.float32, device=Vt.device)) if want_filt else None
+        if out is not None and not want_filt:
+            raise ValueError("out given with want_filt=False")
+        filt = _out_buffer(out, (B, N, P), Vt.device) if want_filt else None
+        st = _state_vector(state, "state", self.total_states, Vt.device)
         incr = torch.empty((B, N), dtype=torch.float32, device=Vt.device)
         ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
-        so = None
-        if isinstance(want_state, torch.Tensor):
-            so = want_state
-            if so.dtype != torch.float32 or so.device != Vt.device:
-                raise TypeError("the state buffer must be a float32 tensor on V's device")
-            if so.dim() != 1 or so.numel() != self.total_states or not so.is_contiguous():
-                raise _lib.DimensionMismatch(-2, f"the state buffer must be a contiguous [{self.total_states}] vector, got {tuple(so.shape)}")
-        elif want_state:
-            so = torch.empty(self.total_states, dtype=torch.float32, device=Vt.device)
-        fs = (filt.stride(0), filt.stride(1), filt.stride(2)) if filt is not None else (0, 0, 0)
-        check(lib.mm_filterposteriors_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
-                                          lt.data_ptr() if lt is not None else None, N,
-                                          st.data_ptr() if st is not None else None, so.data_ptr() if so is not None else None,
-                                          filt.data_ptr() if filt is not None else None, fs[0], fs[1], fs[2],
+        so = _want_vector(want_state, "the state buffer", self.total_states, Vt.device)
+        check(lib.mm_filterposteriors_f32(*_head(self._h, Vt, lt, N), _ptr(st), _ptr(so),
+                                          _ptr(filt), *(filt.stride() if filt is not None else (0, 0, 0)),
                                           incr.data_ptr(), incr.stride(0), ttl.data_ptr(), self._stream(torch)))
-        res = (filt, incr, ttl) + ((so,) if so is not None else ())
-        return tuple(t.cpu().numpy() if t is not None else None for t in res) if as_numpy else res
+        return _results((filt, incr, ttl) + ((so,) if so is not None else ()), as_numpy)
 
     def windowposteriors(self, V, lens=None, state=None, closed=None, commit=None, out=None, want_state=False):
         """Fixed-lag smoothing posteriors (mm_windowposteriors_f32): the forward-backward over a WINDOW of the audio that starts
@@ -669,50 +673,15 @@ class BatchedFSM:
         mass has gamma = 0 and ttl = -inf.  d ttl / d V = gamma.  Log batches only."""
         torch, Vt, lt, as_numpy = self._prep(V, lens)
         B, N, P = Vt.shape
-        if out is not None:
-            # the kernels write through raw pointers and strides: a wrong buffer is memory corruption, not an exception
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != Vt.device:
-                raise TypeError("out must be a float32 tensor on V's device")
-            if out.dim() != 3 or tuple(out.shape) != (B, N, P):
-                raise _lib.DimensionMismatch(-2, f"out must be [B={B}, N={N}, P={P}], got {tuple(out.shape)}")
-        st = None
-        if state is not None:
-            st = torch.as_tensor(np.ascontiguousarray(state, dtype=np.float32)).cuda() if not isinstance(state, torch.Tensor) else state
-            if st.dtype != torch.float32 or st.device != Vt.device:
-                raise TypeError("state must be a float32 tensor on V's device")
-            if st.dim() != 1 or st.numel() != self.total_states or not st.is_contiguous():
-                raise _lib.DimensionMismatch(-2, f"state must be a contiguous [{self.total_states}] vector, got {tuple(st.shape)}")
-
-        def per_utt(x, name):
-            if x is None:
-                return None
-            t = x.to(device=Vt.device, dtype=torch.int32) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.int32)).to(Vt.device)
-            if t.dim() != 1 or t.numel() != B:
-                raise _lib.DimensionMismatch(-2, f"{name} must be a [{B}] vector, got {tuple(t.shape)}")
-            return t.contiguous()
-
-        cl, cm = per_utt(closed, "closed"), per_utt(commit, "commit")
-        gamma = out if out is not None else torch.empty((B, N, P), dtype=torch.float32, device=Vt.device)
+        gamma = _out_buffer(out, (B, N, P), Vt.device)
+        st = _state_vector(state, "state", self.total_states, Vt.device)
+        cl, cm = _per_utt(closed, "closed", B, Vt.device), _per_utt(commit, "commit", B, Vt.device)
         ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
         lcommit = torch.empty(B, dtype=torch.float32, device=Vt.device)
-        so = None
-        if isinstance(want_state, torch.Tensor):
-            so = want_state
-            if so.dtype != torch.float32 or so.device != Vt.device:
-                raise TypeError("the state buffer must be a float32 tensor on V's device")
-            if so.dim() != 1 or so.numel() != self.total_states or not so.is_contiguous():
-                raise _lib.DimensionMismatch(-2, f"the state buffer must be a contiguous [{self.total_states}] vector, got {tuple(so.shape)}")
-        elif want_state:
-            so = torch.empty(self.total_states, dtype=torch.float32, device=Vt.device)
-        check(lib.mm_windowposteriors_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
-                                          lt.data_ptr() if lt is not None else None, N,
-                                          st.data_ptr() if st is not None else None,
-                                          cl.data_ptr() if cl is not None else None, cm.data_ptr() if cm is not None else None,
-                                          so.data_ptr() if so is not None else None, lcommit.data_ptr(),
-                                          gamma.data_ptr(), gamma.stride(0), gamma.stride(1), gamma.stride(2), ttl.data_ptr(),
-                                          self._stream(torch)))
-        res = (gamma, ttl, lcommit) + ((so,) if so is not None else ())
-        return tuple(t.cpu().numpy() for t in res) if as_numpy else res
+        so = _want_vector(want_state, "the state buffer", self.total_states, Vt.device)
+        check(lib.mm_windowposteriors_f32(*_head(self._h, Vt, lt, N), _ptr(st), _ptr(cl), _ptr(cm), _ptr(so), lcommit.data_ptr(),
+                                          gamma.data_ptr(), *gamma.stride(), ttl.data_ptr(), self._stream(torch)))
+        return _results((gamma, ttl, lcommit) + ((so,) if so is not None else ()), as_numpy)
 
     def segmentposteriors(self, V, lens=None, state=None, end_mode=None, end=None, out=None, want_end=False):
         """Segment posteriors (mm_segmentposteriors_f32): the forward-backward over a SEGMENT of the audio that starts from a carried
@@ -731,46 +700,16 @@ class BatchedFSM:
         batches only."""
         torch, Vt, lt, as_numpy = self._prep(V, lens)
         B, N, P = Vt.shape
-        if out is not None:
-            # the kernels write through raw pointers and strides: a wrong buffer is memory corruption, not an exception
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != Vt.device:
-                raise TypeError("out must be a float32 tensor on V's device")
-            if out.dim() != 3 or tuple(out.shape) != (B, N, P):
-                raise _lib.DimensionMismatch(-2, f"out must be [B={B}, N={N}, P={P}], got {tuple(out.shape)}")
-
-        def vector(x, name):
-            if x is None:
-                return None
-            t = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).cuda() if not isinstance(x, torch.Tensor) else x
-            if t.dtype != torch.float32 or t.device != Vt.device:
-                raise TypeError(f"{name} must be a float32 tensor on V's device")
-            if t.dim() != 1 or t.numel() != self.total_states or not t.is_contiguous():
-                raise _lib.DimensionMismatch(-2, f"{name} must be a contiguous [{self.total_states}] vector, got {tuple(t.shape)}")
-            return t
-
-        st, ei = vector(state, "state"), vector(end, "end")
-        em = None
-        if end_mode is not None:
-            em = end_mode.to(device=Vt.device, dtype=torch.int32) if isinstance(end_mode, torch.Tensor) else torch.as_tensor(np.asarray(end_mode, dtype=np.int32)).to(Vt.device)
-            if em.dim() != 1 or em.numel() != B:
-                raise _lib.DimensionMismatch(-2, f"end_mode must be a [{B}] vector, got {tuple(em.shape)}")
-            em = em.contiguous()
-        gamma = out if out is not None else torch.empty((B, N, P), dtype=torch.float32, device=Vt.device)
+        gamma = _out_buffer(out, (B, N, P), Vt.device)
+        st = _state_vector(state, "state", self.total_states, Vt.device)
+        ei = _state_vector(end, "end", self.total_states, Vt.device)
+        em = _per_utt(end_mode, "end_mode", B, Vt.device)
         ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
         lend = torch.empty(B, dtype=torch.float32, device=Vt.device)
-        eo = None
-        if isinstance(want_end, torch.Tensor):
-            eo = vector(want_end, "the end buffer")
-        elif want_end:
-            eo = torch.empty(self.total_states, dtype=torch.float32, device=Vt.device)
-        check(lib.mm_segmentposteriors_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
-                                           lt.data_ptr() if lt is not None else None, N,
-                                           st.data_ptr() if st is not None else None, em.data_ptr() if em is not None else None,
-                                           ei.data_ptr() if ei is not None else None, eo.data_ptr() if eo is not None else None,
-                                           lend.data_ptr(), gamma.data_ptr(), gamma.stride(0), gamma.stride(1), gamma.stride(2),
-                                           ttl.data_ptr(), self._stream(torch)))
-        res = (gamma, ttl, lend) + ((eo,) if eo is not None else ())
-        return tuple(t.cpu().numpy() for t in res) if as_numpy else res
+        eo = _want_vector(want_end, "the end buffer", self.total_states, Vt.device)
+        check(lib.mm_segmentposteriors_f32(*_head(self._h, Vt, lt, N), _ptr(st), _ptr(em), _ptr(ei), _ptr(eo), lend.data_ptr(),
+                                           gamma.data_ptr(), *gamma.stride(), ttl.data_ptr(), self._stream(torch)))
+        return _results((gamma, ttl, lend) + ((eo,) if eo is not None else ()), as_numpy)
 
     def chunkedposteriors(self, V, lens=None, chunk=1024, out=None):
         """The exact smoothing posteriors of long recordings in the workspace of ONE chunk: ``(gamma[B, N, P], ttl[B])``, the gamma
@@ -788,18 +727,13 @@ class BatchedFSM:
         chunk = int(chunk)
         if chunk < 1:
             raise ValueError("chunk must be at least one frame")
-        if out is not None:
-            if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != Vt.device:
-                raise TypeError("out must be a float32 tensor on V's device")
-            if out.dim() != 3 or tuple(out.shape) != (B, N, P):
-                raise _lib.DimensionMismatch(-2, f"out must be [B={B}, N={N}, P={P}], got {tuple(out.shape)}")
         dev = Vt.device
-        gamma = out if out is not None else torch.empty((B, N, P), dtype=torch.float32, device=dev)
+        gamma = _out_buffer(out, (B, N, P), dev)
         if lt is None:
             lt = torch.full((B,), N, dtype=torch.int32, device=dev)
         if chunk >= N:
             _, ttl, _ = self.segmentposteriors(Vt, lt, end_mode=torch.ones(B, dtype=torch.int32, device=dev), out=gamma)
-            return (gamma.cpu().numpy(), ttl.cpu().numpy()) if as_numpy else (gamma, ttl)
+            return _results((gamma, ttl), as_numpy)
         K = (N + chunk - 1) // chunk
         lens_k = [torch.clamp(lt - k * chunk, 0, chunk).to(torch.int32) for k in range(K)]
         # pass 1: states[k] is the state behind chunk k, the start of chunk k + 1 (chunk 0 starts from the FSMs' own vectors)
@@ -819,7 +753,7 @@ class BatchedFSM:
             mode = torch.where(lt <= (k + 1) * chunk, 1, 2).to(torch.int32)
             self.segmentposteriors(Vt[:, k * chunk : (k + 1) * chunk], lens_k[k], state=states[k - 1] if k else None, end_mode=mode,
                                    end=endv if k < K - 1 else None, out=gamma[:, k * chunk : (k + 1) * chunk], want_end=endv if k else False)
-        return (gamma.cpu().numpy(), ttl.cpu().numpy()) if as_numpy else (gamma, ttl)
+        return _results((gamma, ttl), as_numpy)
 
     def maxstateposteriors(self, V, lens=None):
         """Max-marginals of the tropical semiring, (sum S1) x (N+1), computed on the device."""
@@ -927,14 +861,9 @@ class BatchedFSM:
         path = torch.empty((B, N), dtype=torch.int32, device=Vt.device)
         score = torch.empty(B, dtype=torch.float32, device=Vt.device)
         bp = torch.empty((N + 1, self.total_states), dtype=torch.int32, device=Vt.device) if return_backpointers else None
-        check(lib.mm_viterbi_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
-                                 lt.data_ptr() if lt is not None else None, N, path.data_ptr(), path.stride(0),
-                                 score.data_ptr(), bp.data_ptr() if bp is not None else None,
+        check(lib.mm_viterbi_f32(*_head(self._h, Vt, lt, N), path.data_ptr(), path.stride(0), score.data_ptr(), _ptr(bp),
                                  bp.stride(0) if bp is not None else 0, self._stream(torch)))
-        res = (path, score) + ((bp,) if bp is not None else ())
-        if as_numpy:
-            res = tuple(r.cpu().numpy() for r in res)
-        return res
+        return _results((path, score) + ((bp,) if bp is not None else ()), as_numpy)
 
     def viterbiwindow(self, V, lens=None, state=None, closed=None, commit=None, commit_converged=False, want_state=False):
         """Windowed best paths (mm_viterbiwindow_f32): the Viterbi recursion over a WINDOW of the audio that starts from a carried
@@ -953,46 +882,18 @@ class BatchedFSM:
         itself included.  ``path`` is -1 beyond the lengths and where there is no path.  Tropical batches only."""
         torch, Vt, lt, as_numpy = self._prep(V, lens)
         B, N, P = Vt.shape
-        st = None
-        if state is not None:
-            st = torch.as_tensor(np.ascontiguousarray(state, dtype=np.float32)).cuda() if not isinstance(state, torch.Tensor) else state
-            if st.dtype != torch.float32 or st.device != Vt.device:
-                raise TypeError("state must be a float32 tensor on V's device")
-            if st.dim() != 1 or st.numel() != self.total_states or not st.is_contiguous():
-                raise _lib.DimensionMismatch(-2, f"state must be a contiguous [{self.total_states}] vector, got {tuple(st.shape)}")
-
-        def per_utt(x, name):
-            if x is None:
-                return None
-            t = x.to(device=Vt.device, dtype=torch.int32) if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.int32)).to(Vt.device)
-            if t.dim() != 1 or t.numel() != B:
-                raise _lib.DimensionMismatch(-2, f"{name} must be a [{B}] vector, got {tuple(t.shape)}")
-            return t.contiguous()
-
-        cl, cm = per_utt(closed, "closed"), per_utt(commit, "commit")
+        st = _state_vector(state, "state", self.total_states, Vt.device)
+        cl, cm = _per_utt(closed, "closed", B, Vt.device), _per_utt(commit, "commit", B, Vt.device)
         path = torch.empty((B, N), dtype=torch.int32, device=Vt.device)
         score = torch.empty(B, dtype=torch.float32, device=Vt.device)
         conv = torch.empty(B, dtype=torch.int32, device=Vt.device)
         ncommit = torch.empty(B, dtype=torch.int32, device=Vt.device)
         mcommit = torch.empty(B, dtype=torch.float32, device=Vt.device)
-        so = None
-        if isinstance(want_state, torch.Tensor):
-            so = want_state
-            if so.dtype != torch.float32 or so.device != Vt.device:
-                raise TypeError("the state buffer must be a float32 tensor on V's device")
-            if so.dim() != 1 or so.numel() != self.total_states or not so.is_contiguous():
-                raise _lib.DimensionMismatch(-2, f"the state buffer must be a contiguous [{self.total_states}] vector, got {tuple(so.shape)}")
-        elif want_state:
-            so = torch.empty(self.total_states, dtype=torch.float32, device=Vt.device)
-        check(lib.mm_viterbiwindow_f32(self._h, Vt.data_ptr(), Vt.stride(0), Vt.stride(1),
-                                       lt.data_ptr() if lt is not None else None, N,
-                                       st.data_ptr() if st is not None else None,
-                                       cl.data_ptr() if cl is not None else None, cm.data_ptr() if cm is not None else None,
-                                       1 if commit_converged else 0, so.data_ptr() if so is not None else None,
+        so = _want_vector(want_state, "the state buffer", self.total_states, Vt.device)
+        check(lib.mm_viterbiwindow_f32(*_head(self._h, Vt, lt, N), _ptr(st), _ptr(cl), _ptr(cm), 1 if commit_converged else 0, _ptr(so),
                                        mcommit.data_ptr(), ncommit.data_ptr(), path.data_ptr(), path.stride(0), score.data_ptr(),
                                        conv.data_ptr(), self._stream(torch)))
-        res = (path, score, conv, ncommit, mcommit, so)
-        return tuple(t.cpu().numpy() if t is not None else None for t in res) if as_numpy else res
+        return _results((path, score, conv, ncommit, mcommit, so), as_numpy)
 
 
     def totalsum(self, n: int, cumulative: bool = False):
@@ -1263,11 +1164,10 @@ def pdfposteriors(fsm, Vhats, Chats=None, seqlengths=None):
     return np.ascontiguousarray(g.transpose(0, 2, 1)), ttl
 
 
-def leakyposteriors(fsm, Vhats, Chats=None, leak=1e-5, seqlengths=None):
-    """Pdf posteriors of the leaky HMM -- see ``BatchedFSM.leakyposteriors`` -- in ``pdfposteriors``' call shape: ``fsm`` the
-    rawunion of the batch with its state maps, or a BatchedFSM / CompiledFSM (log semiring, Float32); V_hats what ``expand``
-    makes.  Returns (gamma[B, P, N] probabilities, ttl[B]): NumPy arrays for host inputs, device tensors for float32 V_hats on
-    the HIP device given with their ``seqlengths``."""
+def _expanded_inputs(fsm, Vhats, Chats, seqlengths):
+    """``(bf, V, lens, on_device)`` for the entries in ``pdfposteriors``' call shape that take only what ``expand`` makes: float32
+    V_hats on the HIP device given with their ``seqlengths`` stay there (one transposing copy to the engine's [B, N, P]), everything
+    else goes through the host.  The caller transposes its [B, N, P] result back: a view on the device, a fresh array on the host."""
     if not hasattr(Vhats, "dim"):  # (a generator is read once)
         Vhats = list(Vhats)
     bf = _as_batch(fsm, Chats)
@@ -1278,13 +1178,20 @@ def leakyposteriors(fsm, Vhats, Chats=None, leak=1e-5, seqlengths=None):
         if B != bf.B:
             raise _lib.DimensionMismatch(-2, f"{B} matrices V_hat for a batch of {bf.B} FSMs")
         lens = torch.as_tensor(seqlengths, dtype=torch.int32, device=Vd.device)
-        g, ttl = bf.leakyposteriors(Vd[:, : P1 - 1, : N1 - 1].transpose(1, 2).contiguous(), lens, leak=leak)
-        return g.transpose(1, 2), ttl
+        return bf, Vd[:, : P1 - 1, : N1 - 1].transpose(1, 2).contiguous(), lens, True
     # (device V_hats without their lengths: to the host, as pdfposteriors moves them, where the phony row gives the lengths)
     Vh = [np.asarray(v.cpu() if hasattr(v, "cpu") else v) for v in Vhats]
-    V, lens = _need_expanded(Vh, bf.semiring)
+    return (bf, *_need_expanded(Vh, bf.semiring), False)
+
+
+def leakyposteriors(fsm, Vhats, Chats=None, leak=1e-5, seqlengths=None):
+    """Pdf posteriors of the leaky HMM -- see ``BatchedFSM.leakyposteriors`` -- in ``pdfposteriors``' call shape: ``fsm`` the
+    rawunion of the batch with its state maps, or a BatchedFSM / CompiledFSM (log semiring, Float32); V_hats what ``expand``
+    makes.  Returns (gamma[B, P, N] probabilities, ttl[B]): NumPy arrays for host inputs, device tensors for float32 V_hats on
+    the HIP device given with their ``seqlengths``."""
+    bf, V, lens, on_device = _expanded_inputs(fsm, Vhats, Chats, seqlengths)
     g, ttl = bf.leakyposteriors(V, lens, leak=leak)
-    return np.ascontiguousarray(g.transpose(0, 2, 1)), ttl
+    return (g.transpose(1, 2) if on_device else np.ascontiguousarray(g.transpose(0, 2, 1))), ttl
 
 
 def filterposteriors(fsm, Vhats, Chats=None, seqlengths=None):
@@ -1292,23 +1199,9 @@ def filterposteriors(fsm, Vhats, Chats=None, seqlengths=None):
     initial vectors: ``fsm`` the rawunion of the batch with its state maps, or a BatchedFSM / CompiledFSM (log semiring,
     Float32); V_hats what ``expand`` makes.  Returns (filt[B, P, N] probabilities, incr[B, N], ttl[B]): NumPy arrays for host
     inputs, device tensors for float32 V_hats on the HIP device given with their ``seqlengths``."""
-    if not hasattr(Vhats, "dim"):  # (a generator is read once)
-        Vhats = list(Vhats)
-    bf = _as_batch(fsm, Chats)
-    Vd = _device_vhats(Vhats)
-    if Vd is not None and seqlengths is not None:
-        torch = _torch()
-        B, P1, N1 = Vd.shape
-        if B != bf.B:
-            raise _lib.DimensionMismatch(-2, f"{B} matrices V_hat for a batch of {bf.B} FSMs")
-        lens = torch.as_tensor(seqlengths, dtype=torch.int32, device=Vd.device)
-        f, incr, ttl = bf.filterposteriors(Vd[:, : P1 - 1, : N1 - 1].transpose(1, 2).contiguous(), lens)
-        return f.transpose(1, 2), incr, ttl
-    # (device V_hats without their lengths: to the host, as pdfposteriors moves them, where the phony row gives the lengths)
-    Vh = [np.asarray(v.cpu() if hasattr(v, "cpu") else v) for v in Vhats]
-    V, lens = _need_expanded(Vh, bf.semiring)
+    bf, V, lens, on_device = _expanded_inputs(fsm, Vhats, Chats, seqlengths)
     f, incr, ttl = bf.filterposteriors(V, lens)
-    return np.ascontiguousarray(f.transpose(0, 2, 1)), incr, ttl
+    return (f.transpose(1, 2) if on_device else np.ascontiguousarray(f.transpose(0, 2, 1))), incr, ttl
 
 
 def windowposteriors(fsm, Vhats, Chats=None, seqlengths=None, closed=None):
@@ -1316,23 +1209,9 @@ def windowposteriors(fsm, Vhats, Chats=None, seqlengths=None, closed=None):
     vectors: ``fsm`` the rawunion of the batch with its state maps, or a BatchedFSM / CompiledFSM (log semiring, Float32);
     V_hats what ``expand`` makes; ``closed`` None: every window ends open.  Returns (gamma[B, P, N] probabilities, ttl[B]):
     NumPy arrays for host inputs, device tensors for float32 V_hats on the HIP device given with their ``seqlengths``."""
-    if not hasattr(Vhats, "dim"):  # (a generator is read once)
-        Vhats = list(Vhats)
-    bf = _as_batch(fsm, Chats)
-    Vd = _device_vhats(Vhats)
-    if Vd is not None and seqlengths is not None:
-        torch = _torch()
-        B, P1, N1 = Vd.shape
-        if B != bf.B:
-            raise _lib.DimensionMismatch(-2, f"{B} matrices V_hat for a batch of {bf.B} FSMs")
-        lens = torch.as_tensor(seqlengths, dtype=torch.int32, device=Vd.device)
-        g, ttl, _ = bf.windowposteriors(Vd[:, : P1 - 1, : N1 - 1].transpose(1, 2).contiguous(), lens, closed=closed)
-        return g.transpose(1, 2), ttl
-    # (device V_hats without their lengths: to the host, as pdfposteriors moves them, where the phony row gives the lengths)
-    Vh = [np.asarray(v.cpu() if hasattr(v, "cpu") else v) for v in Vhats]
-    V, lens = _need_expanded(Vh, bf.semiring)
+    bf, V, lens, on_device = _expanded_inputs(fsm, Vhats, Chats, seqlengths)
     g, ttl, _ = bf.windowposteriors(V, lens, closed=closed)
-    return np.ascontiguousarray(g.transpose(0, 2, 1)), ttl
+    return (g.transpose(1, 2) if on_device else np.ascontiguousarray(g.transpose(0, 2, 1))), ttl
 
 
 def chunkedposteriors(fsm, Vhats, Chats=None, seqlengths=None, chunk=1024):
@@ -1340,23 +1219,9 @@ def chunkedposteriors(fsm, Vhats, Chats=None, seqlengths=None, chunk=1024):
     call shape: ``fsm`` the rawunion of the batch with its state maps, or a BatchedFSM / CompiledFSM (log semiring, Float32);
     V_hats what ``expand`` makes.  Returns (gamma[B, P, N] probabilities, ttl[B]): NumPy arrays for host inputs, device tensors for
     float32 V_hats on the HIP device given with their ``seqlengths``."""
-    if not hasattr(Vhats, "dim"):  # (a generator is read once)
-        Vhats = list(Vhats)
-    bf = _as_batch(fsm, Chats)
-    Vd = _device_vhats(Vhats)
-    if Vd is not None and seqlengths is not None:
-        torch = _torch()
-        B, P1, N1 = Vd.shape
-        if B != bf.B:
-            raise _lib.DimensionMismatch(-2, f"{B} matrices V_hat for a batch of {bf.B} FSMs")
-        lens = torch.as_tensor(seqlengths, dtype=torch.int32, device=Vd.device)
-        g, ttl = bf.chunkedposteriors(Vd[:, : P1 - 1, : N1 - 1].transpose(1, 2).contiguous(), lens, chunk=chunk)
-        return g.transpose(1, 2), ttl
-    # (device V_hats without their lengths: to the host, as pdfposteriors moves them, where the phony row gives the lengths)
-    Vh = [np.asarray(v.cpu() if hasattr(v, "cpu") else v) for v in Vhats]
-    V, lens = _need_expanded(Vh, bf.semiring)
+    bf, V, lens, on_device = _expanded_inputs(fsm, Vhats, Chats, seqlengths)
     g, ttl = bf.chunkedposteriors(V, lens, chunk=chunk)
-    return np.ascontiguousarray(g.transpose(0, 2, 1)), ttl
+    return (g.transpose(1, 2) if on_device else np.ascontiguousarray(g.transpose(0, 2, 1))), ttl
 
 
 def arcposteriors(fsm, Vhats, Chats=None, want_init=False):
