@@ -126,6 +126,8 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * 13 = mm_segmentposteriors_f32 (log batches only): mm_window_fwd_kernel<NI,lds|global> + mm_segment_bwd_kernel<...>.
  * 14 = mm_arcclassposteriors_f32 (log batches only): mm_log_kernel<MODE_FB,NI,1> + mm_arcclass_kernel<NI,lds|global>; the text ends
  * in where the current class plan's term rows live ("terms in LDS" / "terms in global memory" / "no classes set").
+ * 15 = mm_scoredposteriors_f32 (log batches only): mm_scored_fwd_kernel<NI,lds|global> + mm_scored_bwd_kernel<NI,lds|global>; the text
+ * names the class cap and, for the current class plan, the term cap and where the term rows live (the endings of entry 14).
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -572,6 +574,43 @@ int mm_batch_set_arc_classes(mm_batch_t batch, const int32_t *cls, const int64_t
 int mm_batch_arc_class_info(mm_batch_t batch, int64_t *cap, int64_t *max_M, int32_t *C);
 int mm_arcclassposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
                               float *xi, int64_t x_stride_b, int64_t x_stride_n, int64_t x_stride_c, float *ttl, void *stream);
+
+/* Posteriors with per-frame arc-class scores and their gradient.  Under the class plan of mm_batch_set_arc_classes, a complete
+ * path of utterance b (length len; frames 1-based inside the formula, t 0-based as in mm_arcclassposteriors_f32) weighs
+ *
+ *   alpha_hat(s_1) * prod_n lhs_n(s_n) * prod_{t=0}^{len-1} T_hat[k_t] * exp(U[b, t, cls(k_t)])
+ *
+ * with k_t the stored entry taken from frame t+1 to frame t+2 (t = len-1: the arc into the phony final state); Z_b(U) is the sum
+ * over the paths.  An entry of class -1 contributes exp(0); parallel entries between the same two states are scored one by one;
+ * the phony self-loop stays one(K) whatever its class holds (as under mm_weightedposteriors_f32).  U is finite or -inf (-inf
+ * removes the class at that transition); rows t >= len are never read.  For finite or -inf inputs no output is ever NaN.
+ *
+ *   V, lens, N   as mm_pdfposteriors_f32
+ *   U            device, element (b, t, c) at U[b*u_stride_b + t*u_stride_n + c*u_stride_c], natural log; strides that cannot hold
+ *                B x N x C elements: MM_ERR_DIM.  NULL: all zeros (no scores)
+ *   gamma        device, out (NULL: not computed): d log Z_b / d V -- what mm_pdfposteriors_f32 would return if the scores were
+ *                part of the graph; frames n >= len are exact zeros.  Strides checked as mm_weightedposteriors_f32 checks them
+ *   xi           device, out (NULL: not computed), laid out as mm_arcclassposteriors_f32's: xi by class under Z_b(U).  For t < len
+ *                it is d log Z_b / d U[b, t, c]; for t >= len and for an utterance without a path the conventions of
+ *                mm_arcclassposteriors_f32 hold (the phony loop's class exactly 1.0f, the others exactly 0.0f; no path: 0)
+ *   ttl          device float[B], out (NULL: not written): log Z_b(U); -inf without a path
+ * gamma, xi and ttl all NULL: MM_ERR_INVALID.  With U NULL xi and ttl are those of mm_arcclassposteriors_f32 and gamma that of
+ * mm_pdfposteriors_f32, from ONE forward pass; with U constant in t (U[b, t, c] = u_c) the result is that of
+ * mm_weightedposteriors_f32 with W[k] = w_k + u_{cls[k]}.
+ * MM_LOG batches only (others: MM_ERR_UNSUPPORTED); no classes set, or a first call during a stream capture: MM_ERR_INVALID; more
+ * classes than mm_batch_score_class_cap reports -- the classes whose two score rows fit the LDS beside the kernel's plan --:
+ * MM_ERR_UNSUPPORTED, the message names the cap.  Runs on the item form of every FSM: mm_scored_fwd_kernel (the item kernel's
+ * forward loop, every arc adding its class's entry of the transition's score row, staged in LDS one step ahead), then
+ * mm_scored_bwd_kernel (the loop of mm_arcclass_kernel with the score in the beta~ recursion and in every term, and a per-pdf pass
+ * in a fixed order for gamma).  The class ids travel in a plane of 16-bit ids parallel to the slots of each item form, built with
+ * the class plan and replaced with it.  Stream contract of the arc entries: launches on `stream` only; no atomics, the same bits on
+ * every run; capturable in a hipGraph after a first call has put the plan on the device and sized the workspace; a replay after U
+ * was overwritten in place follows the new scores. */
+int mm_scoredposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                            const float *U, int64_t u_stride_b, int64_t u_stride_n, int64_t u_stride_c,
+                            float *gamma, int64_t g_stride_b, int64_t g_stride_n, int64_t g_stride_p,
+                            float *xi, int64_t x_stride_b, int64_t x_stride_n, int64_t x_stride_c, float *ttl, void *stream);
+int mm_batch_score_class_cap(mm_batch_t batch, int64_t *cap);
 
 /* alpha-recursion(alpha_hat, T_hat', C_hat*V_hat) (src/inference.jl:62-74) as
  * called from pdfposteriors (:150-152): out is the reference's state_A, a

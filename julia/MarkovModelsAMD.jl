@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, set_arc_classes!, arc_class_info, arcclassposteriors, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, set_arc_classes!, arc_class_info, arcclassposteriors, score_class_cap, scoredposteriors, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -288,6 +288,39 @@ function arcclassposteriors(b::ROCBatch, V::ROCArray{Float32,3}, lens = nothing)
         (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Float32}, Int64, Int64, Int64, Ptr{Float32}, Ptr{Cvoid}),
         b.handle, pointer(V), P * N, P, lp, N, pointer(ξ), nc * N, nc, 1, pointer(ttl), AMDGPU.stream().stream))
     ξ, ttl
+end
+
+"The most classes `scoredposteriors` takes on this batch (mm_batch_score_class_cap): their score rows fit the LDS beside the kernel's plan"
+function score_class_cap(b::ROCBatch)
+    cap = Ref{Int64}(0)
+    check(ccall((:mm_batch_score_class_cap, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), b.handle, cap))
+    cap[]
+end
+
+"""
+    scoredposteriors(b::ROCBatch, V::ROCArray{Float32,3}, U = nothing, lens = nothing) -> (γ, ξ, ttl)
+
+Posteriors with per-frame arc-class scores (mm_scoredposteriors_f32 in the header): under the classes of `set_arc_classes!` the
+entry taken between frames t and t + 1 is weighted by `exp(U[c, t, u])` on top of its own weight.  `U` is a `C × N × B`
+`ROCArray{Float32,3}` (finite or `-Inf`), `nothing`: no scores.  `γ` (`P × N × B`) is ∂ log Z / ∂ V, `ξ` (`C × N × B`) is
+∂ log Z / ∂ U on the frames below an utterance's length and what `arcclassposteriors` returns beyond, `ttl` = log Z(U).
+"""
+function scoredposteriors(b::ROCBatch, V::ROCArray{Float32,3}, U = nothing, lens = nothing)
+    P, N, B = size(V)
+    P == b.P || throw(DimensionMismatch("V has $P pdfs, the FSMs $(b.P)"))
+    nc = max(1, arc_class_info(b).C)
+    U === nothing || size(U) == (nc, N, B) || throw(DimensionMismatch("U must be $nc × $N × $B"))
+    γ = ROCArray{Float32}(undef, P, N, B)
+    ξ = ROCArray{Float32}(undef, nc, N, B)
+    ttl = ROCArray{Float32}(undef, B)
+    lp = lens === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(lens))
+    up = U === nothing ? Ptr{Float32}(C_NULL) : Ptr{Float32}(pointer(U))
+    check(ccall((:mm_scoredposteriors_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Float32}, Int64, Int64, Int64, Ptr{Float32}, Int64, Int64, Int64,
+         Ptr{Float32}, Int64, Int64, Int64, Ptr{Float32}, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, lp, N, up, nc * N, nc, 1, pointer(γ), P * N, P, 1, pointer(ξ), nc * N, nc, 1, pointer(ttl),
+        AMDGPU.stream().stream))
+    γ, ξ, ttl
 end
 
 """

@@ -2,12 +2,12 @@
 
 Host-side mirror of the reference's hot-path interface (src/MarkovModels.jl:14-45:
 FSM, nstates, rawunion, CompiledFSM, batch, compile, expand, alpha-recursion,
-beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, chunkedposteriors, windowbestpath, arcposteriors, arcclassposteriors, weightedposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
+beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, chunkedposteriors, windowbestpath, arcposteriors, arcclassposteriors, scoredposteriors, weightedposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
 The directory name contains a dot, so load it with
 ``__graft_entry__.load_package()`` (importlib) rather than a plain import.
 """
 from ._lib import LIB_PATH, SYMBOLS, DimensionMismatch, MarkovModelsAMDError  # noqa: F401
-from .fsm import FSM, GeneralStateMap, StateMap, arc_classes_by_destination, boundary_classes, nstates, rawunion, statemap  # noqa: F401
+from .fsm import FSM, GeneralStateMap, StateMap, arc_classes_by_destination, boundary_classes, loop_exit_classes, nstates, rawunion, statemap  # noqa: F401
 from .inference import (  # noqa: F401
     BatchedFSM,
     CompiledFSM,
@@ -30,6 +30,7 @@ from .inference import (  # noqa: F401
     pathentropy,
     pdfposteriors,
     samplepaths,
+    scoredposteriors,
     totalcumsum,
     totalsum,
     totalweightsum,
@@ -49,5 +50,7 @@ from . import graphweights  # noqa: F401
 from .graphweights import graph_loglik, reestimate  # noqa: F401
 from . import longform  # noqa: F401
 from .longform import chunked_loglik  # noqa: F401
+from . import transitions  # noqa: F401
+from .transitions import constraint_scores, transition_loglik  # noqa: F401
 from . import streaming  # noqa: F401
 from .streaming import FixedLagSmoother, ForwardFilter, OnlineViterbi  # noqa: F401

@@ -52,6 +52,8 @@ SYMBOLS = [
     "mm_batch_set_arc_classes",
     "mm_batch_arc_class_info",
     "mm_arcclassposteriors_f32",
+    "mm_scoredposteriors_f32",
+    "mm_batch_score_class_cap",
     "mm_samplepaths_f32",
     "mm_expectedcost_f32",
     "mm_leakyposteriors_f32",
@@ -175,6 +177,10 @@ def _load():
     lib.mm_batch_arc_class_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]
     lib.mm_arcclassposteriors_f32.restype = C.c_int
     lib.mm_arcclassposteriors_f32.argtypes = [vp, fp, i64, i64, vp, i64, fp, i64, i64, i64, fp, vp]
+    lib.mm_scoredposteriors_f32.restype = C.c_int
+    lib.mm_scoredposteriors_f32.argtypes = [vp, fp, i64, i64, vp, i64, fp, i64, i64, i64, fp, i64, i64, i64, fp, i64, i64, i64, fp, vp]
+    lib.mm_batch_score_class_cap.restype = C.c_int
+    lib.mm_batch_score_class_cap.argtypes = [vp, C.POINTER(i64)]
     lib.mm_samplepaths_f32.restype = C.c_int
     lib.mm_samplepaths_f32.argtypes = [vp, fp, i64, i64, vp, i64, i64, i64, vp, i64, i64, fp, i64, fp, vp]
     lib.mm_expectedcost_f32.restype = C.c_int

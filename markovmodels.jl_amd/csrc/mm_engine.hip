@@ -362,6 +362,11 @@ struct mm_batch_s {
     // classes, the most ranks of one utterance and the ranks of all
     std::vector<char> cls_image;
     DevMem d_cls;
+    // ... and, for mm_scoredposteriors_f32, the class planes of the same plan: the utterances' ScoredDev descriptors in front of the
+    // planes of both item forms and the ranks' classes of every distinct (FSM, class array); made and replaced with the plan (empty:
+    // more classes than a 16-bit id holds), on the device from the first scored call behind it
+    std::vector<char> sc_image;
+    DevMem d_sc;
     int cls_C = 0;
     int64_t cls_max_M = 0, cls_terms = 0;
 };
@@ -446,7 +451,7 @@ static Geometry pick_geometry(mm_batch_t h) {
 }
 
 // ---- one plan per entry that runs on the item form: its launch geometry and where its state vectors live
-enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter, Window, VitWindow, Weighted, Segment, ArcClass };
+enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter, Window, VitWindow, Weighted, Segment, ArcClass, Scored };
 struct ItemPlan {
     ItemEntry e;
     int NW, NI;        // waves per workgroup, register-resident items per wave of the instance (8 or 0)
@@ -463,6 +468,7 @@ struct ItemPlan {
 // streamed-only instance with the vectors in LDS.  VitWindow (tropical batches): the tropical kernel's geometry, its LDS plan + the
 // arc kernel's extra.  Weighted: the arc kernel's size + one row of state posteriors (mm_weighted_lds_bytes), 8 waves like Arcs.
 // ArcClass: the arc entry's plan (its term rows take what LDS the plan leaves, or the workspace: arcclass_cap).
+// Scored: the arc entry's plan as well; the two score rows come behind it (scored_class_cap), the term rows behind them (scored_term_cap).
 // `global` never depends on max_items, nor does NI except Tropical's (8: the whole graph is register-resident): mm_batch_create
 // asks before the item forms are up, and ensure_item_forms raises max_items later -- only NW follows it.
 static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
@@ -479,13 +485,13 @@ static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
         return e == ItemEntry::Cost ? mm_cost_lds_bytes(S1p, P1p) : size_t(lds_plan(S1p, P1p, e != ItemEntry::Export).total) * 4;
     };
     const bool derived = e == ItemEntry::Arcs || e == ItemEntry::Sample || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy ||
-                         e == ItemEntry::Filter || e == ItemEntry::Window || e == ItemEntry::Weighted || e == ItemEntry::Segment || e == ItemEntry::ArcClass;
+                         e == ItemEntry::Filter || e == ItemEntry::Window || e == ItemEntry::Weighted || e == ItemEntry::Segment || e == ItemEntry::ArcClass || e == ItemEntry::Scored;
     ItemPlan pl{e, g.NW, g.NI, false, false, 0};
-    pl.global = bytes(h->max_S1p) + (e == ItemEntry::Arcs || e == ItemEntry::ArcClass ? MM_ARC_LDS_EXTRA : 0) > lds_max || h->dbg.bigv || (derived && g.NI == 0);
+    pl.global = bytes(h->max_S1p) + (e == ItemEntry::Arcs || e == ItemEntry::ArcClass || e == ItemEntry::Scored ? MM_ARC_LDS_EXTRA : 0) > lds_max || h->dbg.bigv || (derived && g.NI == 0);
     pl.lds_bytes = bytes(pl.global ? 0 : h->max_S1p);
     // (8 items' arcs and their sums / the pair arithmetic / the leak term and its sums per wave: compiled for 8 waves per CU)
     if (e == ItemEntry::Arcs || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy || e == ItemEntry::Filter ||
-        e == ItemEntry::Window || e == ItemEntry::Weighted || e == ItemEntry::Segment || e == ItemEntry::ArcClass)
+        e == ItemEntry::Window || e == ItemEntry::Weighted || e == ItemEntry::Segment || e == ItemEntry::ArcClass || e == ItemEntry::Scored)
         pl.NW = std::min(g.NW, 8);
     if (e == ItemEntry::Sample) pl.stage = !pl.global && !h->dbg.sample_nostage && size_t(h->max_S1p) * 8 <= lds_max;
     if (e == ItemEntry::Tropical || e == ItemEntry::VitWindow) {
@@ -514,6 +520,20 @@ static const char *where_of(bool global) { return global ? "global" : "lds"; }
 // the most ranks of one utterance whose two term rows mm_arcclass_kernel keeps in LDS, behind the arc kernel's plan
 static int64_t arcclass_cap(const ItemPlan &pl) {
     const size_t used = pl.lds_bytes + MM_ARC_LDS_EXTRA;
+    return used >= MM_LDS_MAX ? 0 : int64_t((MM_LDS_MAX - used) / (2 * sizeof(float)));
+}
+
+// mm_scoredposteriors_f32: the most classes whose two score rows (C + 1 floats each, padded to 4) fit the LDS behind the arc kernel's
+// plan -- and a 16-bit class id --, and the most ranks of one utterance whose two term rows fit behind the score rows of C classes
+static int64_t scored_class_cap(const ItemPlan &pl) {
+    const size_t used = pl.lds_bytes + MM_ARC_LDS_EXTRA;
+    if (used + 2 * 4 * sizeof(float) > MM_LDS_MAX) return 0;
+    const int64_t row = int64_t((MM_LDS_MAX - used) / (2 * sizeof(float))) & ~int64_t(3);  // floats of one row
+    return std::min<int64_t>(row - 1, 65534);
+}
+static size_t scored_lds_bytes(const ItemPlan &pl, int64_t C) { return pl.lds_bytes + MM_ARC_LDS_EXTRA + size_t(mm_scored_urow(C)) * 2 * sizeof(float); }
+static int64_t scored_term_cap(const ItemPlan &pl, int64_t C) {
+    const size_t used = scored_lds_bytes(pl, C);
     return used >= MM_LDS_MAX ? 0 : int64_t((MM_LDS_MAX - used) / (2 * sizeof(float)));
 }
 
@@ -2686,6 +2706,19 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
         s = "mm_log_kernel<MODE_FB," + ni + ",1> (forward) + mm_arcclass_kernel<" + ni + "," + where_of(pl.global) +
             "> (backward: the classified arcs' terms by rank, a row of class sums per frame); state vectors " + (pl.global ? "in global memory" : "in LDS") +
             (h->cls_image.empty() ? "; no classes set" : h->cls_max_M > arcclass_cap(pl) ? "; terms in global memory" : "; terms in LDS");
+    } else if (entry == 15) {  // mm_scoredposteriors_f32
+        if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_scoredposteriors_f32 runs on log-semiring batches only");
+        const ItemPlan pl = item_plan(h, ItemEntry::Scored);
+        const std::string inst = "<" + std::to_string(pl.NI) + "," + where_of(pl.global) + ">";
+        const int64_t cap = scored_class_cap(pl);
+        s = "mm_scored_fwd_kernel" + inst + " (forward: every arc scored by its class's entry of the frame's score row) + mm_scored_bwd_kernel" + inst +
+            " (backward: the scored beta~ recursion, the classified arcs' terms by rank, a row of class sums per frame, gamma per pdf); state vectors " +
+            (pl.global ? "in global memory" : "in LDS") + "; class cap " + std::to_string(cap);
+        if (h->cls_image.empty()) s += "; no classes set";
+        else if (h->cls_C > cap) s += "; " + std::to_string(h->cls_C) + " classes exceed the cap";
+        else
+            s += "; term cap " + std::to_string(scored_term_cap(pl, h->cls_C)) +
+                 (h->cls_max_M > scored_term_cap(pl, h->cls_C) ? "; terms in global memory" : "; terms in LDS");
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -3128,7 +3161,7 @@ static int item_entry_begin(mm_batch_t h, const char *who, ItemEntry e, const fl
 // floats); Entropy: as Cost, the Hf store in the place of the r store -- and no such store for a value-only call (`store` false).
 // total: no less than what mm_pdfposteriors_f32 needs for as many frames.  (mm_batch_reserve does not cover it.)  Filter keeps
 // nothing: its offsets stay in registers, total = 0 whatever N -- the workspace is neither grown nor touched.  ArcClass: what Leaky
-// keeps, and the two term rows of every utterance when the plan has more ranks than the LDS holds.
+// keeps, and the two term rows of every utterance when the plan has more ranks than the LDS holds; Scored: the same.
 struct ItemWs { size_t c = 0, acc = 0, post1 = 0, r = 0, o = 0, big = 0, plane[2] = {0, 0}, initp = 0, utts = 0, terms = 0, total = 0; };
 // Weighted: the arc entry's areas, then what the call's weights need (wplanes / wiplanes: 0 none given, 1 one vector for the batch
 // -- the planes of ONE FSM --, 2 a vector per utterance): the {col, w} planes of both item forms, the dense init vectors, the call's
@@ -3154,9 +3187,10 @@ static ItemWs item_ws_layout(mm_batch_t h, const ItemPlan &pl, int64_t N, bool s
             W.utts = W.total;
             W.total += align_up(size_t(h->B) * sizeof(UttDesc), 256);
         }
-    } else if (pl.e == ItemEntry::ArcClass) {
+    } else if (pl.e == ItemEntry::ArcClass || pl.e == ItemEntry::Scored) {
         W.terms = W.total;
-        W.total += h->cls_max_M > arcclass_cap(pl) ? align_up(size_t(h->cls_terms) * 2 * sizeof(float), 256) : 0;
+        const int64_t cap = pl.e == ItemEntry::Scored ? scored_term_cap(pl, h->cls_C) : arcclass_cap(pl);
+        W.total += h->cls_max_M > cap ? align_up(size_t(h->cls_terms) * 2 * sizeof(float), 256) : 0;
     } else if (ws_holds_big(pl.e)) {
         W.r = W.total;
         W.o = W.r + (store ? rows : 0);
@@ -3291,6 +3325,16 @@ struct ClassPlanHost {
     std::vector<int32_t> cptr;
     int cphony = -1;
 };
+static std::vector<int32_t> pack_slot2k(const mm_fsm_s &f, int d);
+// The class plane of item form d under the class array cls: the class id of the entry behind every slot; an entry without a class,
+// the phony self-loop and the padding slots carry the id C.  (mm_kernel_scored.hip)
+static std::vector<uint16_t> make_class_plane(const mm_fsm_s &f, int d, const int32_t *cls, int32_t C) {
+    const std::vector<int32_t> s2k = pack_slot2k(f, d);
+    std::vector<uint16_t> plane(s2k.size(), uint16_t(C));
+    for (size_t s = 0; s < s2k.size(); ++s)
+        if (s2k[s] >= 0 && cls[s2k[s]] >= 0) plane[s] = uint16_t(cls[s2k[s]]);
+    return plane;
+}
 static ClassPlanHost make_class_plan(mm_fsm_s &f, const int32_t *cls, int32_t C) {
     ensure_packed(&f);
     const Packed &pk = f.packed[1];
@@ -3344,6 +3388,13 @@ int mm_batch_set_arc_classes(mm_batch_t h, const int32_t *cls, const int64_t *of
         std::vector<ClassDev> descs(B);
         Blob bl;
         (void)bl.add(descs);  // (at 0; filled in below)
+        // the class planes of the scored entry, laid out the same way (none for more classes than a 16-bit id holds)
+        const bool planes = C <= 65534;
+        struct MadePlanes { size_t o_plane[2], o_rcls; };
+        std::vector<MadePlanes> made_sc;
+        std::vector<ScoredDev> sdescs(B);
+        Blob sbl;
+        (void)sbl.add(sdescs);
         int64_t terms = 0, max_M = 0;
         for (size_t b = 0; b < B; ++b) {
             mm_fsm_s &f = *h->fsms[b];
@@ -3356,6 +3407,23 @@ int mm_batch_set_arc_classes(mm_batch_t h, const int32_t *cls, const int64_t *of
                 const size_t o_recs = bl.add(pl.recs);
                 made.push_back(Made{&f, cb, o_recs, bl.add(pl.cptr), int(pl.recs.size()), pl.cphony});
                 m = &made.back();
+                if (planes) {
+                    std::vector<uint16_t> rcls(pl.recs.size());
+                    for (int32_t c = 0; c < C; ++c)
+                        for (int32_t r = pl.cptr[size_t(c)]; r < pl.cptr[size_t(c) + 1]; ++r) rcls[size_t(r)] = uint16_t(c);
+                    MadePlanes mp;
+                    mp.o_plane[0] = sbl.add(make_class_plane(f, 0, cb, C));
+                    mp.o_plane[1] = sbl.add(make_class_plane(f, 1, cb, C));
+                    mp.o_rcls = sbl.add(rcls);
+                    made_sc.push_back(mp);
+                }
+            }
+            if (planes) {
+                const MadePlanes &mp = made_sc[size_t(m - made.data())];
+                ScoredDev &sd = sdescs[b];
+                sd.plane[0] = reinterpret_cast<const unsigned short *>(mp.o_plane[0]);
+                sd.plane[1] = reinterpret_cast<const unsigned short *>(mp.o_plane[1]);
+                sd.rcls = reinterpret_cast<const unsigned short *>(mp.o_rcls);
             }
             ClassDev &d = descs[b];
             d.recs = reinterpret_cast<const ClassRec *>(m->o_recs);
@@ -3371,6 +3439,9 @@ int mm_batch_set_arc_classes(mm_batch_t h, const int32_t *cls, const int64_t *of
         memcpy(bl.host.data(), descs.data(), sizeof(ClassDev) * B);
         h->cls_image = std::move(bl.host);
         h->d_cls = DevMem();  // (the next mm_arcclassposteriors_f32 call uploads the new plan)
+        if (planes) memcpy(sbl.host.data(), sdescs.data(), sizeof(ScoredDev) * B);
+        h->sc_image = planes ? std::move(sbl.host) : std::vector<char>();
+        h->d_sc = DevMem();  // (... and the next mm_scoredposteriors_f32 call the new planes)
         h->cls_C = C;
         h->cls_max_M = max_M;
         h->cls_terms = terms;
@@ -3773,6 +3844,93 @@ int mm_weightedposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t
     // (the forward launch is the arc entry's: the item kernel's plan of the same placement)
     const size_t lds_fwd = size_t(lds_plan(pl.global ? 0 : h->max_S1p, (h->max_P1 + 3) & ~3, true).total) * 4;
     return mm_launch_weighted(h->B, pl.NW, pl.NI, pl.global, lds_fwd, pl.lds_bytes, p, wp, static_cast<hipStream_t>(stream));
+}
+
+// ---- posteriors with per-frame arc-class scores (mm_kernel_scored.hip)
+int mm_batch_score_class_cap(mm_batch_t h, int64_t *cap) {
+    if (!h || !cap) return fail(MM_ERR_INVALID, "mm_batch_score_class_cap: NULL argument");
+    if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_score_class_cap: log-semiring batches only");
+    *cap = scored_class_cap(item_plan(h, ItemEntry::Scored));
+    return MM_OK;
+}
+
+// the class planes on the device: one allocation, one copy -- made by the first call behind mm_batch_set_arc_classes, never during a
+// capture (as ensure_class_plan)
+static int ensure_score_planes(mm_batch_t h, void *stream) {
+    if (h->d_sc) return MM_OK;
+    if (capturing(stream))
+        return fail(MM_ERR_INVALID, "the class planes of this batch are not on the device yet: run mm_scoredposteriors_f32 once outside a stream capture");
+    void *d = nullptr;
+    HIP_TRY(hipMalloc(&d, h->sc_image.size()));
+    DevMem own(d);
+    std::vector<char> img = h->sc_image;  // (the descriptors' offsets become pointers into the allocation)
+    ScoredDev *descs = reinterpret_cast<ScoredDev *>(img.data());
+    auto at = [&](const unsigned short *off) { return reinterpret_cast<const unsigned short *>(static_cast<char *>(d) + reinterpret_cast<size_t>(off)); };
+    for (int64_t b = 0; b < h->B; ++b) {
+        descs[b].plane[0] = at(descs[b].plane[0]);
+        descs[b].plane[1] = at(descs[b].plane[1]);
+        descs[b].rcls = at(descs[b].rcls);
+    }
+    if (hipMemcpy(d, img.data(), img.size(), hipMemcpyHostToDevice) != hipSuccess)
+        return fail(MM_ERR_HIP, "mm_scoredposteriors_f32: upload of the class planes failed");
+    h->d_sc = std::move(own);
+    return MM_OK;
+}
+
+int mm_scoredposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, const float *U, int64_t usb,
+                            int64_t usn, int64_t usc, float *gamma, int64_t gsb, int64_t gsn, int64_t gsp, float *xi, int64_t xsb, int64_t xsn,
+                            int64_t xsc, float *ttl, void *stream) {
+    const std::string who = "mm_scoredposteriors_f32";
+    // what the arguments alone show comes first (without a batch: the frames' own extent), then the batch's refusals
+    if (!gamma && !xi && !ttl) return fail(MM_ERR_INVALID, who + ": gamma, xi and ttl are all NULL");
+    if (gamma) {
+        const int64_t B = h ? h->B : 1, P = h ? h->max_P1 - 1 : 1;
+        if (const int rc = check_strides(who, "g", gsb, B, gsn, N, gsp, P)) return rc;
+    }
+    ItemPlan pl;
+    int rc = item_entry_begin(h, who.c_str(), ItemEntry::Scored, V, N, stream, [&]() {
+        if (h->cls_image.empty()) return fail(MM_ERR_INVALID, who + ": no classes set (mm_batch_set_arc_classes)");
+        if (U)
+            if (const int rc = check_strides(who, "u", usb, h->B, usn, N, usc, h->cls_C)) return rc;
+        if (xi)
+            if (const int rc = check_strides(who, "x", xsb, h->B, xsn, N, xsc, h->cls_C)) return rc;
+        return int(MM_OK);
+    }, &pl);
+    if (rc) return rc;
+    const int64_t cap = scored_class_cap(pl);
+    if (h->cls_C > cap || h->sc_image.empty())
+        return fail(MM_ERR_UNSUPPORTED, who + ": " + std::to_string(h->cls_C) + " classes exceed the cap of " + std::to_string(cap) +
+                                            " classes whose score rows fit the LDS beside the kernel's plan (mm_batch_score_class_cap)");
+    rc = ensure_class_plan(h, stream);
+    if (!rc) rc = ensure_score_planes(h, stream);
+    if (rc) return rc;
+    const ItemWs W = item_ws_layout(h, pl, N);
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    rc = item_ws_bind(h, pl, W, p, stream);
+    if (rc) return rc;
+    p.gamma = gamma;
+    p.gsb = gsb;
+    p.gsn = gsn;
+    p.gsp = gsp;
+    const bool tg = h->cls_max_M > scored_term_cap(pl, h->cls_C);
+    ScoredParams sp{};
+    sp.cls = static_cast<const ClassDev *>(h->d_cls.get());
+    sp.sc = static_cast<const ScoredDev *>(h->d_sc.get());
+    sp.U = U;
+    sp.usb = usb;
+    sp.usn = usn;
+    sp.usc = usc;
+    sp.C = h->cls_C;
+    sp.urow = mm_scored_urow(h->cls_C);
+    sp.terms = reinterpret_cast<float *>(static_cast<char *>(h->ws) + W.terms);
+    sp.terms_global = tg ? 1 : 0;
+    sp.xi = xi;
+    sp.xsb = xsb;
+    sp.xsn = xsn;
+    sp.xsc = xsc;
+    sp.ttl = ttl;
+    return mm_launch_scored(h->B, pl.NW, pl.NI, pl.global, scored_lds_bytes(pl, h->cls_C), tg ? 0 : size_t(h->cls_max_M) * 2 * sizeof(float), p, sp,
+                            static_cast<hipStream_t>(stream));
 }
 
 // ---- pdf posteriors of the leaky HMM (mm_kernel_leaky.hip)

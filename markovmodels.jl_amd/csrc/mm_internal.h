@@ -242,6 +242,32 @@ struct ArcClassParams {
 int mm_launch_arcclass(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, size_t term_lds, const RunParams &p, const ArcClassParams &cp,
                        hipStream_t stream);
 
+// ---- posteriors with per-frame arc-class scores (mm_scored_tu.hip: mm_scored_fwd_kernel, mm_scored_bwd_kernel on the item form)
+struct ScoredDev {  // one utterance's class planes (mm_engine.hip build_score_planes, with the class plan)
+    const unsigned short *plane[2];  // [slots of the forward / backward item form] class id of the slot's entry; C: none
+    const unsigned short *rcls;      // [M] the class of every rank of ClassDev::recs
+};
+struct ScoredParams {
+    const ClassDev *cls;  // [B]
+    const ScoredDev *sc;  // [B]
+    const float *U;       // [b * usb + t * usn + c * usc], rows t < len_b only; NULL: no scores
+    long long usb, usn, usc;
+    int C;                // classes of the plan
+    int urow;             // floats of one score row in LDS: C + 1 rounded up to a multiple of 4
+    float *terms;         // as ArcClassParams
+    int terms_global;
+    float *xi;            // NULL: not asked for
+    long long xsb, xsn, xsc;
+    float *ttl;           // NULL: not asked for
+};
+// floats of one score row in LDS for a plan of C classes
+inline int mm_scored_urow(int64_t C) { return int((C + 1 + 3) & ~int64_t(3)); }
+// lds_bytes: the arc kernel's size (the item kernel's plan + MM_ARC_LDS_EXTRA) + the two score rows, of both kernels; term_lds: bytes
+// of the term rows the backward kernel keeps in LDS behind them (0: they are global).  gamma (NULL: not asked for) goes where
+// RunParams says.
+int mm_launch_scored(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, size_t term_lds, const RunParams &p, const ScoredParams &sp,
+                     hipStream_t stream);
+
 // ---- posterior path sampling (mm_sample_tu.hip: mm_log_kernel's forward half, then mm_sample_kernel on the sampling form)
 #define MM_SAMPLE_NW 8  // waves of a workgroup of mm_sample_kernel that run chains (+ one that stages the alpha~ rows)
 #define MM_SAMPLE_CW 8  // the most chains one wave carries in registers (1, 2, 4 or 8: mm_sample_tu.hip sample_cw)

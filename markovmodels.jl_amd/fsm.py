@@ -264,6 +264,24 @@ def boundary_classes(fsm: FSM, state_group) -> np.ndarray:
     return out.astype(np.int32)
 
 
+def loop_exit_classes(fsm: FSM, state2pdf, P: int) -> Tuple[np.ndarray, int]:
+    """Arc classes for per-frame loop / exit scores (``BatchedFSM.scoredposteriors``): entry k = (i_k -> j_k) gets class
+    ``2 * pdf(i_k)`` when it is a self-loop and ``2 * pdf(i_k) + 1`` when it leaves its state (the arcs into the phony final state
+    included); the phony self-loop gets -1.  ``state2pdf`` has one pdf per real state (an entry for the phony final state is
+    ignored).  Returns ``(classes int32[nnz], C = 2 * P)``."""
+    src, dst = _entry_ends(fsm)
+    S = fsm.S1 - 1
+    s2p = np.asarray(state2pdf, dtype=np.int64).ravel()
+    if s2p.size not in (S, S + 1):
+        raise ValueError(f"loop_exit_classes needs one pdf per state ({S}, or {S + 1} with the phony final state), got {s2p.size}")
+    s2p = s2p[:S]
+    if s2p.size and (s2p.min() < 0 or s2p.max() >= P):
+        raise ValueError(f"loop_exit_classes: a pdf outside [0, {P})")
+    pdf = np.concatenate([s2p, [0]])[src]
+    cls = np.where(src >= S, -1, 2 * pdf + (src != dst))
+    return cls.astype(np.int32), 2 * int(P)
+
+
 def rawunion(*fsms: FSM) -> FSM:
     """rawunion(fsms...) (src/fsmops.jl:28-36): vcat of the alpha_hat's and
     blockdiag of the T_hat's -- several independent FSMs (each keeping its own

@@ -487,13 +487,20 @@ class BatchedFSM:
             check(lib.mm_batch_set_arc_classes(self._h, flat.ctypes.data, offs.ctypes.data, int(C)))
         return int(C)
 
-    def info(self) -> dict:
+    def info(self, scored=False) -> dict:
         """What the batch knows about its arc-class plan (mm_batch_arc_class_info): ``arcclass_cap`` = the most classified entries
         of one utterance whose per-frame terms ``arcclassposteriors`` keeps in LDS (beyond it: in the workspace), ``arcclass_max_M``
-        = the most any utterance of the current plan has (-1: no plan), ``arcclass_C``.  Log batches only."""
+        = the most any utterance of the current plan has (-1: no plan), ``arcclass_C``.  With ``scored`` also ``score_class_cap`` = the most
+        classes ``scoredposteriors`` takes (mm_batch_score_class_cap: their score rows fit the LDS beside the kernel's plan); the
+        plain call keeps the three keys it has always had.  Log batches only."""
         cap, m, c = C.c_int64(), C.c_int64(), C.c_int32()
         check(lib.mm_batch_arc_class_info(self._h, C.byref(cap), C.byref(m), C.byref(c)))
-        return dict(arcclass_cap=cap.value, arcclass_max_M=m.value, arcclass_C=c.value)
+        out = dict(arcclass_cap=cap.value, arcclass_max_M=m.value, arcclass_C=c.value)
+        if scored:
+            sc = C.c_int64()
+            check(lib.mm_batch_score_class_cap(self._h, C.byref(sc)))
+            out["score_class_cap"] = sc.value
+        return out
 
     def arcclassposteriors(self, V, lens=None):
         """Per-frame arc-class posteriors (mm_arcclassposteriors_f32), Baum-Welch's xi_n summed by the classes ``set_arc_classes``
@@ -509,6 +516,38 @@ class BatchedFSM:
         check(lib.mm_arcclassposteriors_f32(*_head(self._h, Vt, lt, N), buf.data_ptr(), *buf.stride(), ttl.data_ptr(), self._stream(torch)))
         xi, ttl = _results((buf.permute(0, 2, 1), ttl), as_numpy)
         return (np.ascontiguousarray(xi) if as_numpy else xi), ttl
+
+    def scoredposteriors(self, V, U=None, lens=None, want_gamma=True, want_xi=True, out=None):
+        """Posteriors with per-frame arc-class scores (mm_scoredposteriors_f32): ``(gamma[B, N, P], xi[B, C, N], ttl[B])``; what
+        ``want_gamma`` / ``want_xi`` do not ask for comes back as None and is not computed.  Under the classes ``set_arc_classes``
+        gave, the entry taken between frames t and t + 1 (0-based; t = len - 1: the arc into the phony final state) is weighted by
+        ``exp(U[b, t, class])`` on top of its own weight: ``U`` is ``[B, N, C]`` float32 on the device, finite or -inf (-inf removes
+        the class at that transition; rows t >= len are not read), None: no scores.  An entry of class -1 and the phony self-loop are
+        not scored.  ``ttl`` = log Z(U), ``gamma = d ttl / d V`` (zeros for n >= len), ``xi[b, c, t] = d ttl / d U[b, t, c]`` for
+        t < len and what ``arcclassposteriors`` returns beyond; ``xi`` is a view of a ``[B, N, C]`` buffer.  With ``U`` None
+        ``xi``, ``ttl`` are those of ``arcclassposteriors`` and ``gamma`` that of ``pdfposteriors``, from one forward pass.  ``out``:
+        a [B, N, P] view gamma is written to with its own strides.  No atomics: bit-identical from call to call.  Log batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        nc = max(1, self.info()["arcclass_C"])  # (no plan: the library refuses the call)
+        Ut = None
+        if U is not None:
+            Ut = U if isinstance(U, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(U, dtype=np.float32))
+            Ut = Ut.to(device=Vt.device)
+            if Ut.dtype != torch.float32:
+                raise TypeError("U must be float32")
+            if tuple(Ut.shape) != (B, N, nc):
+                raise _lib.DimensionMismatch(-2, f"U must be [B={B}, N={N}, C={nc}], got {tuple(Ut.shape)}")
+        if out is not None and not want_gamma:
+            raise ValueError("out given with want_gamma=False")
+        gamma = _out_buffer(out, (B, N, P), Vt.device) if want_gamma else None
+        buf = torch.empty((B, N, nc), dtype=torch.float32, device=Vt.device) if want_xi else None
+        ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        check(lib.mm_scoredposteriors_f32(*_head(self._h, Vt, lt, N), _ptr(Ut), *(Ut.stride() if Ut is not None else (0, 0, 0)),
+                                          _ptr(gamma), *(gamma.stride() if gamma is not None else (0, 0, 0)),
+                                          _ptr(buf), *(buf.stride() if buf is not None else (0, 0, 0)), ttl.data_ptr(), self._stream(torch)))
+        gamma, xi, ttl = _results((gamma, None if buf is None else buf.permute(0, 2, 1), ttl), as_numpy)
+        return gamma, (np.ascontiguousarray(xi) if as_numpy and xi is not None else xi), ttl
 
     def weightedposteriors(self, V, W=None, W_init=None, lens=None, want_gamma=True, want_counts=True, want_init=False, out=None):
         """Posteriors with call-time arc weights (mm_weightedposteriors_f32): ``(gamma[B, N, P], counts[B, max nnz], ttl[B])``, plus
@@ -843,7 +882,7 @@ class BatchedFSM:
         import ctypes
 
         buf = ctypes.create_string_buffer(1024)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13, "arcclass": 14}[semiring], buf, 1024))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13, "arcclass": 14, "scored": 15}[semiring], buf, 1024))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -1242,6 +1281,16 @@ def arcclassposteriors(fsm, Vhats, classes, Chats=None, C=None):
     V, lens = _need_expanded(Vhats, bf.semiring)
     bf.set_arc_classes(classes, C)
     return bf.arcclassposteriors(V, lens)
+
+
+def scoredposteriors(fsm, Vhats, classes, U, Chats=None, C=None):
+    """Posteriors with per-frame arc-class scores: ``(gamma[B, N, P], xi[B, C, N], ttl[B])`` -- see ``BatchedFSM.set_arc_classes`` /
+    ``BatchedFSM.scoredposteriors``.  ``fsm``, the V_hats and ``classes`` as for ``arcclassposteriors``; ``U`` the scores
+    ``[B, N, C]`` (None: none).  NumPy arrays out."""
+    bf = _as_batch(fsm, Chats)
+    V, lens = _need_expanded(Vhats, bf.semiring)
+    bf.set_arc_classes(classes, C)
+    return bf.scoredposteriors(V, U, lens)
 
 
 def weightedposteriors(fsm, Vhats, W, Chats=None, W_init=None, seqlengths=None):
