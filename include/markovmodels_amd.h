@@ -128,6 +128,8 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * in where the current class plan's term rows live ("terms in LDS" / "terms in global memory" / "no classes set").
  * 15 = mm_scoredposteriors_f32 (log batches only): mm_scored_fwd_kernel<NI,lds|global> + mm_scored_bwd_kernel<NI,lds|global>; the text
  * names the class cap and, for the current class plan, the term cap and where the term rows live (the endings of entry 14).
+ * 16 = mm_classcost_f32 (log batches only): mm_classcost_fwd_kernel<NI,lds|global> + mm_classcost_bwd_kernel<NI,lds|global>; the text
+ * names the class cap and says "exceed the cap" when the current class plan has more classes ("no classes set" without a plan).
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -611,6 +613,58 @@ int mm_scoredposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b
                             float *gamma, int64_t g_stride_b, int64_t g_stride_n, int64_t g_stride_p,
                             float *xi, int64_t x_stride_b, int64_t x_stride_n, int64_t x_stride_c, float *ttl, void *stream);
 int mm_batch_score_class_cap(mm_batch_t batch, int64_t *cap);
+
+/* Expected arc-class cost under the path posterior and its gradient: a Bayes risk whose costs sit on the arcs -- with
+ * A = -[class equals the reference's class at that transition] over the denominator graph, lattice-free MPE / MWE (a phone or a
+ * word is right or wrong where its arc is entered); insertion and length penalties; an expected number of boundaries.  Under the
+ * class plan of mm_batch_set_arc_classes, for utterance b of length len, with class costs A[b, t, c], t = 0 .. len-1, on the
+ * transition index of mm_arcclassposteriors_f32 (entry k_t leads from frame t+1 to frame t+2, frames 1-based inside the formulas;
+ * t = len-1: the arc into the phony final state) and optional pdf costs D[b, n, p] that mean exactly what mm_expectedcost_f32's
+ * cost means:
+ *
+ *   A(pi)        = sum_{n=1..len} D(n, pdf(s_n))  +  sum_{t=0..len-1} A(t, cls(k_t))
+ *   risk_b       = sum_pi P(pi | V_b) * A(pi)
+ *   grad_b(n,p)  = d risk_b / d V_b(n,p) = sum_{j : pdf(j) = p} gamma_n(j) * (r_n(j) + s_n(j) - risk_b)
+ *
+ *   r_1(j) = D(1, pdf j)
+ *   r_n(j) = D(n, pdf j) + sum_{k into j} P(k | s_n=j, V_1..n) * (r_{n-1}(i_k) + A(n-2, cls k)),     P(k | j) ~ alpha_{n-1}(i_k) T_hat[k]
+ *   s_{N+1} = 0
+ *   s_n(i) = sum_{k out of i} P(k | s_n=i, V) * (A(n-1, cls k) + D(n+1, pdf j_k) + s_{n+1}(j_k)),    P(k | i) ~ T_hat[k] lhs_{n+1}(j_k) beta_{n+1}(j_k)
+ *   risk_b = r_{N+1}(final)
+ *
+ * Conventions (the scored entry's wherever both share a case): an entry of class -1 costs 0; the phony self-loop costs 0 whatever
+ * class it holds; parallel entries between the same two states are costed one by one, each with its own class; rows t >= len of A
+ * and n >= len of D are NEVER READ; A and D must be finite where they are read (a non-finite value leaves that utterance's outputs
+ * unspecified and touches no other utterance); an utterance without an accepting path (len = 0 included) gets risk 0, grad 0,
+ * gamma 0 and ttl = -inf; nothing is NaN for finite costs and finite or -inf emissions.
+ * Identities: with A = 0 the outputs are those of mm_expectedcost_f32 on D; with cls[k] = the pdf of the source state i_k,
+ * A[b, t, p] = D'[b, t, p] and D NULL they are those of mm_expectedcost_f32 on D'; risk_b = sum_{n,p} gamma_b(n,p) D_b(n,p) +
+ * sum_{t<len,c} xi_b(c,t) A_b(t,c) with xi of mm_arcclassposteriors_f32; with every entry classified and A[b, t, c] = a_t,
+ * risk_b = sum_{t<len} a_t and grad = 0; sum_p grad_b(n,p) = 0 for every frame.  d risk_b / d A[b, t, c] = xi_b(c, t) and
+ * d risk_b / d D = gamma: the first is what mm_arcclassposteriors_f32 returns and is not an output here.
+ *   V, lens, N   as mm_pdfposteriors_f32
+ *   A            device, element (b, t, c) at A[b*a_stride_b + t*a_stride_n + c*a_stride_c]; strides that cannot hold B x N x C
+ *                elements: MM_ERR_DIM (as mm_scoredposteriors_f32 checks U).  NULL: MM_ERR_INVALID
+ *   D            device, as mm_expectedcost_f32's cost (d_stride_n < P: MM_ERR_DIM).  NULL: zeros
+ *   risk, grad   device, out, required (NULL: MM_ERR_INVALID); grad's strides as mm_expectedcost_f32's, frames n >= len exact zeros
+ *   gamma, ttl   device, out, optional (NULL: not written): meaning and stride rules of mm_expectedcost_f32
+ * MM_LOG batches only (others: MM_ERR_UNSUPPORTED); no class plan: MM_ERR_INVALID; more classes than mm_batch_cost_class_cap
+ * reports -- the largest C whose two cost rows of C + 1 floats (padded to 4) fit the LDS behind the cost kernels' plan, at most
+ * 65 534 --: MM_ERR_UNSUPPORTED, the message names the cap.  Runs on the item form of every FSM, one workgroup per utterance:
+ * mm_classcost_fwd_kernel and mm_classcost_bwd_kernel, the loops of mm_expectedcost_f32's kernels in which every arc adds its
+ * class's entry of the transition's cost row (staged in LDS one step ahead, not scaled) to the gathered second operand; the class
+ * ids travel in the 16-bit planes of mm_scoredposteriors_f32.  r and s are carried centred as in mm_expectedcost_f32, the class
+ * term with them.  Workspace: mm_expectedcost_f32's -- the alpha~ store and an r store of the same size, float32
+ * (sum_b S1p_b) x (N + 1) each --, grown by the call: mm_batch_workspace_bytes and mm_batch_reserve do NOT cover it (they size
+ * mm_pdfposteriors_f32's workspace), so before a capture a first call with the same N is required.  Stream contract of the arc entries: launches on `stream` only; no host
+ * synchronisation; no atomics, so a repeated call returns the same bits; capturable in a hipGraph after a first call has put the
+ * class planes on the device and sized the workspace; a first call during a capture returns MM_ERR_INVALID. */
+int mm_classcost_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                     const float *A, int64_t a_stride_b, int64_t a_stride_n, int64_t a_stride_c,
+                     const float *D, int64_t d_stride_b, int64_t d_stride_n,
+                     float *risk, float *grad, float *gamma, int64_t g_stride_b, int64_t g_stride_n, int64_t g_stride_p,
+                     float *ttl, void *stream);
+int mm_batch_cost_class_cap(mm_batch_t batch, int64_t *cap);
 
 /* alpha-recursion(alpha_hat, T_hat', C_hat*V_hat) (src/inference.jl:62-74) as
  * called from pdfposteriors (:150-152): out is the reference's state_A, a

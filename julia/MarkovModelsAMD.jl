@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, set_arc_classes!, arc_class_info, arcclassposteriors, score_class_cap, scoredposteriors, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, set_arc_classes!, arc_class_info, arcclassposteriors, score_class_cap, scoredposteriors, cost_class_cap, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -411,6 +411,44 @@ function expectedcost(b::ROCBatch, V::ROCArray{Float32,3}, cost::ROCArray{Float3
         (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Float32}, Int64, Int64,
          Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int64, Int64, Int64, Ptr{Float32}, Ptr{Cvoid}),
         b.handle, pointer(V), P * N, P, lp, N, pointer(cost), P * N, P,
+        pointer(risk), pointer(grad), pointer(γ), 1, B * P, B, pointer(ttl),
+        AMDGPU.stream().stream))
+    risk, grad, γ, ttl
+end
+
+"The most classes `classcost` takes on this batch (mm_batch_cost_class_cap): their cost rows fit the LDS behind the cost kernels' plan"
+function cost_class_cap(b::ROCBatch)
+    cap = Ref{Int64}(0)
+    check(ccall((:mm_batch_cost_class_cap, LIB), Cint, (Ptr{Cvoid}, Ptr{Int64}), b.handle, cap))
+    cap[]
+end
+
+"""
+    classcost(b::ROCBatch, V::ROCArray{Float32,3}, A::ROCArray{Float32,3}, lens = nothing; D = nothing) -> (risk, grad, γ, ttl)
+
+Expected arc-class cost under the path posterior and its gradient (mm_classcost_f32 in the header) of a log-semiring batch: under
+the classes of `set_arc_classes!` the entry taken between frames t and t + 1 costs `A[c, t, u]` (`C × N × B`, finite inside the
+length, not read beyond it); `D` (`P × N × B`, optional) are pdf costs as `expectedcost` takes them.  Returns `risk` (B),
+`grad` = ∂ risk / ∂ V and `γ` = ∂ risk / ∂ D (the pdf posteriors), both B × P × N like `pdfposteriors`' γ, and ttl = log Z.
+∂ risk / ∂ A is the ξ of `arcclassposteriors`.  With `A = -onehot(reference classes)` on the denominator graph, `risk` is the
+lattice-free MPE objective (minus the expected number of correct arcs).
+"""
+function classcost(b::ROCBatch, V::ROCArray{Float32,3}, A::ROCArray{Float32,3}, lens = nothing; D = nothing)
+    P, N, B = size(V)
+    P == b.P || throw(DimensionMismatch("V has $P pdfs, the FSMs $(b.P)"))
+    nc = max(1, arc_class_info(b).C)
+    size(A) == (nc, N, B) || throw(DimensionMismatch("A must be $nc × $N × $B"))
+    D === nothing || size(D) == size(V) || throw(DimensionMismatch("D is $(size(D)), V $(size(V))"))
+    risk = ROCArray{Float32}(undef, B)
+    grad = ROCArray{Float32}(undef, B, P, N)
+    γ = ROCArray{Float32}(undef, B, P, N)
+    ttl = ROCArray{Float32}(undef, B)
+    lp = lens === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(lens))
+    dp = D === nothing ? Ptr{Float32}(C_NULL) : Ptr{Float32}(pointer(D))
+    check(ccall((:mm_classcost_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Float32}, Int64, Int64, Int64, Ptr{Float32}, Int64, Int64,
+         Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int64, Int64, Int64, Ptr{Float32}, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, lp, N, pointer(A), nc * N, nc, 1, dp, P * N, P,
         pointer(risk), pointer(grad), pointer(γ), 1, B * P, B, pointer(ttl),
         AMDGPU.stream().stream))
     risk, grad, γ, ttl

@@ -2,7 +2,7 @@
 
 Host-side mirror of the reference's hot-path interface (src/MarkovModels.jl:14-45:
 FSM, nstates, rawunion, CompiledFSM, batch, compile, expand, alpha-recursion,
-beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, chunkedposteriors, windowbestpath, arcposteriors, arcclassposteriors, scoredposteriors, weightedposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
+beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, chunkedposteriors, windowbestpath, arcposteriors, arcclassposteriors, scoredposteriors, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
 The directory name contains a dot, so load it with
 ``__graft_entry__.load_package()`` (importlib) rather than a plain import.
 """
@@ -31,6 +31,7 @@ from .inference import (  # noqa: F401
     pdfposteriors,
     samplepaths,
     scoredposteriors,
+    classcost,
     totalcumsum,
     totalsum,
     totalweightsum,
@@ -43,7 +44,7 @@ from .inference import (  # noqa: F401
 from . import dist, linalg  # noqa: F401
 from .linalg import SparseCSR, SparseVector, eldiv_, elmul_, mul_  # noqa: F401
 from .lfmmi import lfmmi_loss  # noqa: F401
-from .mbr import expected_cost, smbr_loss  # noqa: F401
+from .mbr import expected_class_cost, expected_cost, mpe_loss, smbr_loss  # noqa: F401
 from . import entropy  # noqa: F401
 from .entropy import conditional_entropy_loss, path_entropy  # noqa: F401
 from . import graphweights  # noqa: F401

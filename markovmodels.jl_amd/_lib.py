@@ -56,6 +56,8 @@ SYMBOLS = [
     "mm_batch_score_class_cap",
     "mm_samplepaths_f32",
     "mm_expectedcost_f32",
+    "mm_classcost_f32",
+    "mm_batch_cost_class_cap",
     "mm_leakyposteriors_f32",
     "mm_pathentropy_f32",
     "mm_filterposteriors_f32",
@@ -183,6 +185,10 @@ def _load():
     lib.mm_batch_score_class_cap.argtypes = [vp, C.POINTER(i64)]
     lib.mm_samplepaths_f32.restype = C.c_int
     lib.mm_samplepaths_f32.argtypes = [vp, fp, i64, i64, vp, i64, i64, i64, vp, i64, i64, fp, i64, fp, vp]
+    lib.mm_classcost_f32.restype = C.c_int
+    lib.mm_classcost_f32.argtypes = [vp, fp, i64, i64, vp, i64, fp, i64, i64, i64, fp, i64, i64, fp, fp, fp, i64, i64, i64, fp, vp]
+    lib.mm_batch_cost_class_cap.restype = C.c_int
+    lib.mm_batch_cost_class_cap.argtypes = [vp, C.POINTER(i64)]
     lib.mm_expectedcost_f32.restype = C.c_int
     lib.mm_expectedcost_f32.argtypes = [vp, fp, i64, i64, vp, i64, fp, i64, i64, fp, fp, fp, i64, i64, i64, fp, vp]
     lib.mm_leakyposteriors_f32.restype = C.c_int

@@ -451,7 +451,7 @@ static Geometry pick_geometry(mm_batch_t h) {
 }
 
 // ---- one plan per entry that runs on the item form: its launch geometry and where its state vectors live
-enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter, Window, VitWindow, Weighted, Segment, ArcClass, Scored };
+enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter, Window, VitWindow, Weighted, Segment, ArcClass, Scored, ClassCost };
 struct ItemPlan {
     ItemEntry e;
     int NW, NI;        // waves per workgroup, register-resident items per wave of the instance (8 or 0)
@@ -469,6 +469,7 @@ struct ItemPlan {
 // arc kernel's extra.  Weighted: the arc kernel's size + one row of state posteriors (mm_weighted_lds_bytes), 8 waves like Arcs.
 // ArcClass: the arc entry's plan (its term rows take what LDS the plan leaves, or the workspace: arcclass_cap).
 // Scored: the arc entry's plan as well; the two score rows come behind it (scored_class_cap), the term rows behind them (scored_term_cap).
+// ClassCost: the cost entry's plan; the two cost rows come behind it (classcost_class_cap).
 // `global` never depends on max_items, nor does NI except Tropical's (8: the whole graph is register-resident): mm_batch_create
 // asks before the item forms are up, and ensure_item_forms raises max_items later -- only NW follows it.
 static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
@@ -482,16 +483,18 @@ static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
         if (e == ItemEntry::Window || e == ItemEntry::Segment) return mm_window_lds_bytes(S1p, P1p);
         if (e == ItemEntry::VitWindow) return mm_vitwindow_lds_bytes(S1p, P1p);
         if (e == ItemEntry::Weighted) return mm_weighted_lds_bytes(S1p, P1p);
-        return e == ItemEntry::Cost ? mm_cost_lds_bytes(S1p, P1p) : size_t(lds_plan(S1p, P1p, e != ItemEntry::Export).total) * 4;
+        return e == ItemEntry::Cost || e == ItemEntry::ClassCost ? mm_cost_lds_bytes(S1p, P1p) : size_t(lds_plan(S1p, P1p, e != ItemEntry::Export).total) * 4;
     };
     const bool derived = e == ItemEntry::Arcs || e == ItemEntry::Sample || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy ||
-                         e == ItemEntry::Filter || e == ItemEntry::Window || e == ItemEntry::Weighted || e == ItemEntry::Segment || e == ItemEntry::ArcClass || e == ItemEntry::Scored;
+                         e == ItemEntry::Filter || e == ItemEntry::Window || e == ItemEntry::Weighted || e == ItemEntry::Segment || e == ItemEntry::ArcClass || e == ItemEntry::Scored ||
+                         e == ItemEntry::ClassCost;
     ItemPlan pl{e, g.NW, g.NI, false, false, 0};
     pl.global = bytes(h->max_S1p) + (e == ItemEntry::Arcs || e == ItemEntry::ArcClass || e == ItemEntry::Scored ? MM_ARC_LDS_EXTRA : 0) > lds_max || h->dbg.bigv || (derived && g.NI == 0);
     pl.lds_bytes = bytes(pl.global ? 0 : h->max_S1p);
     // (8 items' arcs and their sums / the pair arithmetic / the leak term and its sums per wave: compiled for 8 waves per CU)
     if (e == ItemEntry::Arcs || e == ItemEntry::Cost || e == ItemEntry::Leaky || e == ItemEntry::Entropy || e == ItemEntry::Filter ||
-        e == ItemEntry::Window || e == ItemEntry::Weighted || e == ItemEntry::Segment || e == ItemEntry::ArcClass || e == ItemEntry::Scored)
+        e == ItemEntry::Window || e == ItemEntry::Weighted || e == ItemEntry::Segment || e == ItemEntry::ArcClass || e == ItemEntry::Scored ||
+        e == ItemEntry::ClassCost)
         pl.NW = std::min(g.NW, 8);
     if (e == ItemEntry::Sample) pl.stage = !pl.global && !h->dbg.sample_nostage && size_t(h->max_S1p) * 8 <= lds_max;
     if (e == ItemEntry::Tropical || e == ItemEntry::VitWindow) {
@@ -505,7 +508,7 @@ static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
 }
 // ... for an entry about to launch: refuses what the plan cannot run.  (Cost and Entropy keep their global vectors in the workspace
 // at 8 floats per state, the others in h->ws_big at 4: bind_big, ItemWs)
-static bool ws_holds_big(ItemEntry e) { return e == ItemEntry::Cost || e == ItemEntry::Entropy; }
+static bool ws_holds_big(ItemEntry e) { return e == ItemEntry::Cost || e == ItemEntry::Entropy || e == ItemEntry::ClassCost; }
 static int item_plan_check(mm_batch_t h, const ItemPlan &pl) {
     if (pl.global && !ws_holds_big(pl.e) && !h->ws_big)
         return fail(MM_ERR_UNSUPPORTED, "FSM too large for the LDS and no global-memory vectors were allocated");
@@ -536,6 +539,15 @@ static int64_t scored_term_cap(const ItemPlan &pl, int64_t C) {
     const size_t used = scored_lds_bytes(pl, C);
     return used >= MM_LDS_MAX ? 0 : int64_t((MM_LDS_MAX - used) / (2 * sizeof(float)));
 }
+
+// mm_classcost_f32: the most classes whose two cost rows (C + 1 floats each, padded to 4) fit the LDS behind the cost kernels' plan
+// -- and a 16-bit class id
+static int64_t classcost_class_cap(const ItemPlan &pl) {
+    if (pl.lds_bytes + 2 * 4 * sizeof(float) > MM_LDS_MAX) return 0;
+    const int64_t row = int64_t((MM_LDS_MAX - pl.lds_bytes) / (2 * sizeof(float))) & ~int64_t(3);  // floats of one row
+    return std::min<int64_t>(row - 1, 65534);
+}
+static size_t classcost_lds_bytes(const ItemPlan &pl, int64_t C) { return pl.lds_bytes + size_t(mm_scored_urow(C)) * 2 * sizeof(float); }
 
 // item / tropical kernels: `kernel` keeps the state vectors in LDS; `big` is the same kernel with the vectors in global
 // memory, for FSMs beyond the LDS (the reference has no size limit: src/linalg.jl:170-181)
@@ -2719,6 +2731,16 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
         else
             s += "; term cap " + std::to_string(scored_term_cap(pl, h->cls_C)) +
                  (h->cls_max_M > scored_term_cap(pl, h->cls_C) ? "; terms in global memory" : "; terms in LDS");
+    } else if (entry == 16) {  // mm_classcost_f32
+        if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_classcost_f32 runs on log-semiring batches only");
+        const ItemPlan pl = item_plan(h, ItemEntry::ClassCost);
+        const std::string inst = "<" + std::to_string(pl.NI) + "," + where_of(pl.global) + ">";
+        const int64_t cap = classcost_class_cap(pl);
+        s = "mm_classcost_fwd_kernel" + inst + " (forward: alpha~ and r, every arc with its class's entry of the transition's cost row) + mm_classcost_bwd_kernel" +
+            inst + " (backward: beta~ and s with the class costs, gamma and grad per pdf); state vectors " + (pl.global ? "in global memory" : "in LDS") +
+            "; class cap " + std::to_string(cap);
+        if (h->cls_image.empty()) s += "; no classes set";
+        else if (h->cls_C > cap) s += "; " + std::to_string(h->cls_C) + " classes exceed the cap";
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -3162,6 +3184,7 @@ static int item_entry_begin(mm_batch_t h, const char *who, ItemEntry e, const fl
 // total: no less than what mm_pdfposteriors_f32 needs for as many frames.  (mm_batch_reserve does not cover it.)  Filter keeps
 // nothing: its offsets stay in registers, total = 0 whatever N -- the workspace is neither grown nor touched.  ArcClass: what Leaky
 // keeps, and the two term rows of every utterance when the plan has more ranks than the LDS holds; Scored: the same.
+// ClassCost: what Cost keeps.
 struct ItemWs { size_t c = 0, acc = 0, post1 = 0, r = 0, o = 0, big = 0, plane[2] = {0, 0}, initp = 0, utts = 0, terms = 0, total = 0; };
 // Weighted: the arc entry's areas, then what the call's weights need (wplanes / wiplanes: 0 none given, 1 one vector for the batch
 // -- the planes of ONE FSM --, 2 a vector per utterance): the {col, w} planes of both item forms, the dense init vectors, the call's
@@ -3931,6 +3954,70 @@ int mm_scoredposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t v
     sp.ttl = ttl;
     return mm_launch_scored(h->B, pl.NW, pl.NI, pl.global, scored_lds_bytes(pl, h->cls_C), tg ? 0 : size_t(h->cls_max_M) * 2 * sizeof(float), p, sp,
                             static_cast<hipStream_t>(stream));
+}
+
+// ---- expected arc-class cost and its gradient (mm_kernel_classcost.hip)
+int mm_batch_cost_class_cap(mm_batch_t h, int64_t *cap) {
+    if (!h || !cap) return fail(MM_ERR_INVALID, "mm_batch_cost_class_cap: NULL argument");
+    if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_cost_class_cap: log-semiring batches only");
+    *cap = classcost_class_cap(item_plan(h, ItemEntry::ClassCost));
+    return MM_OK;
+}
+
+int mm_classcost_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, const float *A, int64_t asb,
+                     int64_t asn, int64_t asc, const float *D, int64_t dsb, int64_t dsn, float *risk, float *grad, float *gamma, int64_t gsb,
+                     int64_t gsn, int64_t gsp, float *ttl, void *stream) {
+    const std::string who = "mm_classcost_f32";
+    ItemPlan pl;
+    int rc = item_entry_begin(h, who.c_str(), ItemEntry::ClassCost, V, N, stream, [&]() {
+        if (!A || !risk || !grad) return fail(MM_ERR_INVALID, who + ": A / risk / grad is NULL");
+        if (h->cls_image.empty()) return fail(MM_ERR_INVALID, who + ": no classes set (mm_batch_set_arc_classes)");
+        const int64_t P = h->max_P1 - 1;
+        if (const int rc = check_strides(who, "a", asb, h->B, asn, N, asc, h->cls_C)) return rc;
+        if (D && dsn < P) return fail(MM_ERR_DIM, who + ": d_stride_n " + std::to_string(dsn) + " < " + std::to_string(P) + " pdfs");
+        if (const int rc = check_strides(who, "g", gsb, h->B, gsn, N, gsp, P)) return rc;
+        return int(MM_OK);
+    }, &pl);
+    if (rc) return rc;
+    const int64_t cap = classcost_class_cap(pl);
+    if (h->cls_C > cap || h->sc_image.empty())
+        return fail(MM_ERR_UNSUPPORTED, who + ": " + std::to_string(h->cls_C) + " classes exceed the cap of " + std::to_string(cap) +
+                                            " classes whose cost rows fit the LDS beside the kernel's plan (mm_batch_cost_class_cap)");
+    // (the refusal of ensure_score_planes, in this entry's name)
+    if (!h->d_sc && capturing(stream))
+        return fail(MM_ERR_INVALID, "the class planes of this batch are not on the device yet: run " + who + " once outside a stream capture");
+    rc = ensure_score_planes(h, stream);
+    if (rc) return rc;
+    const ItemWs W = item_ws_layout(h, pl, N);
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    rc = item_ws_bind(h, pl, W, p, stream);
+    if (rc) return rc;
+    char *ws = static_cast<char *>(h->ws);
+    ClassCostParams cp{};
+    cp.sc = static_cast<const ScoredDev *>(h->d_sc.get());
+    cp.A = A;
+    cp.asb = asb;
+    cp.asn = asn;
+    cp.asc = asc;
+    cp.C = h->cls_C;
+    cp.urow = mm_scored_urow(h->cls_C);
+    cp.D = D;
+    cp.dsb = dsb;
+    cp.dsn = dsn;
+    cp.risk = risk;
+    cp.grad = grad;
+    cp.gamma = gamma;
+    cp.gsb = gsb;
+    cp.gsn = gsn;
+    cp.gsp = gsp;
+    cp.ttl = ttl;
+    cp.ws_r = reinterpret_cast<float *>(ws + W.r);
+    cp.ws_o = reinterpret_cast<double *>(ws + W.o);
+    if (pl.global) {
+        cp.ws_big = reinterpret_cast<float *>(ws + W.big);
+        cp.big_stride = 8ll * h->max_S1p;
+    }
+    return mm_launch_classcost(h->B, pl.NW, pl.NI, pl.global, classcost_lds_bytes(pl, h->cls_C), p, cp, static_cast<hipStream_t>(stream));
 }
 
 // ---- pdf posteriors of the leaky HMM (mm_kernel_leaky.hip)

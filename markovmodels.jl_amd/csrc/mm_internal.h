@@ -314,6 +314,28 @@ struct CostParams {
 int mm_launch_cost(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, const RunParams &p, const CostParams &cp, hipStream_t stream);
 size_t mm_cost_lds_bytes(int S1p, int P1p);
 
+// ---- expected arc-class cost and its gradient (mm_classcost_tu.hip: mm_classcost_fwd_kernel, mm_classcost_bwd_kernel on the item form)
+struct ClassCostParams {
+    const ScoredDev *sc;  // [B] the class planes of the plan (as ScoredParams::sc)
+    const float *A;       // [b * asb + t * asn + c * asc], rows t < len_b only
+    long long asb, asn, asc;
+    int C;                // classes of the plan
+    int urow;             // floats of one cost row in LDS: mm_scored_urow(C)
+    const float *D;       // [b * dsb + n * dsn + p], frames below len_b only; NULL: zeros
+    long long dsb, dsn;
+    float *risk;   // [B]
+    float *grad;   // strides as gamma's
+    float *gamma;  // NULL: not asked for
+    long long gsb, gsn, gsp;
+    float *ttl;    // NULL: not asked for
+    float *ws_r;   // as CostParams
+    double *ws_o;
+    float *ws_big;
+    long long big_stride;
+};
+// lds_bytes: the cost kernels' plan (mm_cost_lds_bytes) + the two cost rows
+int mm_launch_classcost(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, const RunParams &p, const ClassCostParams &cp, hipStream_t stream);
+
 // ---- posterior path entropy and its gradient (mm_entropy_tu.hip: mm_entropy_fwd_kernel, mm_entropy_bwd_kernel on the item form)
 struct EntropyParams {
     float *entropy;  // [B]

@@ -487,12 +487,13 @@ class BatchedFSM:
             check(lib.mm_batch_set_arc_classes(self._h, flat.ctypes.data, offs.ctypes.data, int(C)))
         return int(C)
 
-    def info(self, scored=False) -> dict:
+    def info(self, scored=False, classcost=False) -> dict:
         """What the batch knows about its arc-class plan (mm_batch_arc_class_info): ``arcclass_cap`` = the most classified entries
         of one utterance whose per-frame terms ``arcclassposteriors`` keeps in LDS (beyond it: in the workspace), ``arcclass_max_M``
         = the most any utterance of the current plan has (-1: no plan), ``arcclass_C``.  With ``scored`` also ``score_class_cap`` = the most
         classes ``scoredposteriors`` takes (mm_batch_score_class_cap: their score rows fit the LDS beside the kernel's plan); the
-        plain call keeps the three keys it has always had.  Log batches only."""
+        plain call keeps the three keys it has always had.  With ``classcost`` also ``cost_class_cap`` = the most classes ``classcost``
+        takes (mm_batch_cost_class_cap: their cost rows fit the LDS behind the cost kernels' plan).  Log batches only."""
         cap, m, c = C.c_int64(), C.c_int64(), C.c_int32()
         check(lib.mm_batch_arc_class_info(self._h, C.byref(cap), C.byref(m), C.byref(c)))
         out = dict(arcclass_cap=cap.value, arcclass_max_M=m.value, arcclass_C=c.value)
@@ -500,6 +501,10 @@ class BatchedFSM:
             sc = C.c_int64()
             check(lib.mm_batch_score_class_cap(self._h, C.byref(sc)))
             out["score_class_cap"] = sc.value
+        if classcost:
+            cc = C.c_int64()
+            check(lib.mm_batch_cost_class_cap(self._h, C.byref(cc)))
+            out["cost_class_cap"] = cc.value
         return out
 
     def arcclassposteriors(self, V, lens=None):
@@ -632,6 +637,44 @@ class BatchedFSM:
         gamma = torch.empty((B, N, P), dtype=torch.float32, device=Vt.device) if want_gamma else None
         check(lib.mm_expectedcost_f32(*_head(self._h, Vt, lt, N), Ct.data_ptr(), Ct.stride(0), Ct.stride(1), risk.data_ptr(),
                                       grad.data_ptr(), _ptr(gamma), *grad.stride(), ttl.data_ptr(), self._stream(torch)))
+        return _results((risk, grad, ttl) + ((gamma,) if want_gamma else ()), as_numpy)
+
+    def classcost(self, V, A, lens=None, D=None, want_gamma=False):
+        """Expected arc-class cost under the path posterior and its gradient (mm_classcost_f32): ``(risk[B], grad[B, N, P],
+        ttl[B])``, plus ``gamma[B, N, P]`` when ``want_gamma``.  Under the classes ``set_arc_classes`` gave, ``A[b, t, c]``
+        (``[B, N, C]`` float32 on the device, any strides) is what utterance b pays for taking an entry of class c between frames t
+        and t + 1 (0-based; t = len - 1: the arc into the phony final state); ``D[b, n, p]`` (optional) what it pays for a state of
+        pdf p at frame n, exactly ``expectedcost``'s ``cost``.  Both finite where they are read; rows t >= len are not read.  An
+        entry of class -1 and the phony self-loop cost nothing.  ``risk[b]`` is the posterior expectation of a path's summed cost,
+        ``grad`` its derivative with respect to ``V``, ``gamma`` (the pdf posteriors) its derivative with respect to ``D``; its
+        derivative with respect to ``A`` is the xi of ``arcclassposteriors``.  With ``A = -onehot(reference classes)`` on the
+        denominator graph this is lattice-free MPE (``mbr.mpe_loss``).  No atomics: bit-identical from call to call.  Log batches
+        only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        nc = max(1, self.info()["arcclass_C"])  # (no plan: the library refuses the call)
+        At = A if isinstance(A, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(A, dtype=np.float32))
+        At = At.to(device=Vt.device)
+        if At.dtype != torch.float32:
+            raise TypeError("A must be float32")
+        if tuple(At.shape) != (B, N, nc):
+            raise _lib.DimensionMismatch(-2, f"A must be [B={B}, N={N}, C={nc}], got {tuple(At.shape)}")
+        Dt = None
+        if D is not None:
+            Dt = D if isinstance(D, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(D, dtype=np.float32))
+            Dt = Dt.to(device=Vt.device)
+            if Dt.dtype != torch.float32:
+                raise TypeError("D must be float32")
+            if tuple(Dt.shape) != (B, N, P):
+                raise _lib.DimensionMismatch(-2, f"D must be [B={B}, N={N}, P={P}], got {tuple(Dt.shape)}")
+            if Dt.stride(2) != 1:
+                Dt = Dt.contiguous()
+        risk = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        ttl = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        grad = _out_buffer(None, (B, N, P), Vt.device)
+        gamma = _out_buffer(None, (B, N, P), Vt.device) if want_gamma else None
+        check(lib.mm_classcost_f32(*_head(self._h, Vt, lt, N), At.data_ptr(), *At.stride(), _ptr(Dt), *(Dt.stride()[:2] if Dt is not None else (0, 0)),
+                                   risk.data_ptr(), grad.data_ptr(), _ptr(gamma), *grad.stride(), ttl.data_ptr(), self._stream(torch)))
         return _results((risk, grad, ttl) + ((gamma,) if want_gamma else ()), as_numpy)
 
     def pathentropy(self, V, lens=None, want_grad=True, want_gamma=False):
@@ -882,7 +925,7 @@ class BatchedFSM:
         import ctypes
 
         buf = ctypes.create_string_buffer(1024)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13, "arcclass": 14, "scored": 15}[semiring], buf, 1024))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13, "arcclass": 14, "scored": 15, "classcost": 16}[semiring], buf, 1024))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -1291,6 +1334,16 @@ def scoredposteriors(fsm, Vhats, classes, U, Chats=None, C=None):
     V, lens = _need_expanded(Vhats, bf.semiring)
     bf.set_arc_classes(classes, C)
     return bf.scoredposteriors(V, U, lens)
+
+
+def classcost(fsm, Vhats, classes, A, Chats=None, C=None, D=None):
+    """Expected arc-class cost of every utterance under its path posterior, and the gradient: ``(risk[B], grad[B, N, P], ttl[B])`` --
+    see ``BatchedFSM.set_arc_classes`` / ``BatchedFSM.classcost``.  ``fsm``, the V_hats and ``classes`` as for
+    ``arcclassposteriors``; ``A`` the class costs ``[B, N, C]``, ``D`` the pdf costs ``[B, N, P]`` (None: none).  NumPy arrays out."""
+    bf = _as_batch(fsm, Chats)
+    V, lens = _need_expanded(Vhats, bf.semiring)
+    bf.set_arc_classes(classes, C)
+    return bf.classcost(V, A, lens, D=D)
 
 
 def weightedposteriors(fsm, Vhats, W, Chats=None, W_init=None, seqlengths=None):

@@ -11,6 +11,13 @@ variate for objectives estimated from `samplepaths`.
     d risk_b / d V[b, n, p]    = grad[b, n, p]    (a covariance: Cov(cost of the whole path, [pdf_n = p]))
     d risk_b / d cost[b, n, p] = gamma[b, n, p]   (the pdf posterior)
 
+Costs that sit on an arc rather than on a frame's pdf -- a phone or a word that is right or wrong where its arc is entered
+(lattice-free MPE / MWE), insertion and length penalties, an expected number of boundaries -- go through `expected_class_cost`
+(mm_classcost_f32): under the arc classes of `BatchedFSM.set_arc_classes`,
+
+    risk_b = E_{pi ~ P(pi | V_b)} [ sum_n D_b(n, pdf(pi_n)) + sum_t A_b(t, class of the arc taken at transition t) ],
+    d risk_b / d A[b, t, c] = xi[b, c, t]   (the arc-class posterior of `arcclassposteriors`)
+
 Both are launches on the caller's stream; in a data-parallel job the per-rank sums go through `dist.allreduce_logz`.
 """
 from __future__ import annotations
@@ -64,4 +71,74 @@ def smbr_loss(V, ref_pdfs, den_batch, lens: Optional["torch.Tensor"] = None):
     cost = torch.zeros((B, N, P), dtype=torch.float32, device=V.device)
     cost.scatter_(2, ref.clamp(0, P - 1)[:, :, None], -1.0)
     loss, risk, ttl = expected_cost(V, cost, den_batch, lens)
+    return loss, -risk, ttl
+
+
+def _class_function():
+    import torch
+
+    class _ExpectedClassCost(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, V, A, D, batch, lens):
+            want_gamma = D is not None and bool(D.requires_grad)
+            want_xi = bool(A.requires_grad)
+            Vd = V.detach()
+            out = batch.classcost(Vd, A.detach(), lens, D=None if D is None else D.detach(), want_gamma=want_gamma)
+            risk, grad, ttl = out[:3]
+            saved = [grad] + list(out[3:])
+            if want_xi:  # d risk / d A = xi: one arcclassposteriors call, only when A asks for a gradient
+                xi, _ = batch.arcclassposteriors(Vd, lens)
+                xi = xi.permute(0, 2, 1).clone()  # [B, N, C]
+                if lens is not None:
+                    L = torch.as_tensor(lens, device=xi.device).long()
+                    xi = xi * (torch.arange(xi.shape[1], device=xi.device)[None, :] < L[:, None])[:, :, None]
+                saved.append(xi)
+            ctx.want_gamma, ctx.want_xi = want_gamma, want_xi
+            ctx.save_for_backward(*saved)
+            ctx.mark_non_differentiable(ttl)
+            return risk.double().sum().to(V.dtype), risk, ttl
+
+        @staticmethod
+        def backward(ctx, g_total, g_risk, _g_ttl):
+            saved = list(ctx.saved_tensors)
+            grad = saved.pop(0)
+            gamma = saved.pop(0) if ctx.want_gamma else None
+            xi = saved.pop(0) if ctx.want_xi else None
+            w = g_total if g_risk is None else g_total + g_risk[:, None, None]
+            return grad * w, (xi * w) if xi is not None else None, (gamma * w) if gamma is not None else None, None, None
+
+    return _ExpectedClassCost
+
+
+def expected_class_cost(V, A, batch, lens: Optional["torch.Tensor"] = None, D=None):
+    """V: [B, N, P], A: [B, N, C], D: [B, N, P] or None, float32 on the HIP device (requires_grad as needed); batch: a BatchedFSM of B
+    utterances (log semiring) with its arc classes set (``set_arc_classes``).  Returns (sum_b risk_b, risk[B], ttl[B]).  Backward
+    hands ``grad * g`` to V, ``gamma * g`` to D when D requires a gradient (the posteriors are only computed then), and ``xi * g`` to
+    A: xi comes from ONE ``arcclassposteriors`` call, made in forward only when A requires a gradient, and is zeroed for t >= len
+    (the rows the entry never reads; an utterance without an accepting path has xi = 0 already).  Utterances without an accepting
+    path have risk 0, gradient 0 and ttl = -inf."""
+    return _class_function().apply(V, A, D, batch, lens)
+
+
+def mpe_loss(V, ref_classes, batch, lens: Optional["torch.Tensor"] = None):
+    """Lattice-free MPE / MWE: V [B, N, P] float32 log-likelihoods on the HIP device, ref_classes int [B, N] the reference's arc
+    class at every transition t (the arc from frame t to frame t + 1; t = len - 1: the arc into the final state), batch the
+    denominator BatchedFSM with its arc classes set.  The cost is A = -onehot(ref_classes[b, t]), built on the device; entries < 0
+    and entries at t >= len_b cost nothing.  Returns (loss, accuracy[B], ttl[B]): loss = -(expected number of transitions whose
+    class equals the reference's), summed over the batch; accuracy[b] that expectation for utterance b.  Utterances with
+    ttl = -inf contribute nothing and are the caller's to filter, as in `smbr_loss`."""
+    import torch
+
+    B, N, P = V.shape
+    nc = max(1, batch.info()["arcclass_C"])
+    ref = torch.as_tensor(ref_classes, device=V.device).long()
+    if tuple(ref.shape) != (B, N):
+        raise ValueError(f"ref_classes must be [B={B}, N={N}], got {tuple(ref.shape)}")
+    hit = (ref >= 0) & (ref < nc)
+    if lens is not None:
+        L = torch.as_tensor(lens, device=V.device).long()
+        hit = hit & (torch.arange(N, device=V.device)[None, :] < L[:, None])
+    A = torch.zeros((B, N, nc), dtype=torch.float32, device=V.device)
+    A.scatter_(2, ref.clamp(0, nc - 1)[:, :, None], -hit.to(torch.float32)[:, :, None])
+    loss, risk, ttl = expected_class_cost(V, A, batch, lens)
     return loss, -risk, ttl
