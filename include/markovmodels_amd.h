@@ -125,9 +125,12 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * + mm_weighted_scatter_kernel.
  * 13 = mm_segmentposteriors_f32 (log batches only): mm_window_fwd_kernel<NI,lds|global> + mm_segment_bwd_kernel<...>.
  * 14 = mm_arcclassposteriors_f32 (log batches only): mm_log_kernel<MODE_FB,NI,1> + mm_arcclass_kernel<NI,lds|global>; the text ends
- * in where the current class plan's term rows live ("terms in LDS" / "terms in global memory" / "no classes set").
+ * in where the current class plan's term rows live ("terms in LDS" / "terms in global memory" / "no classes set"); ahead of that
+ * ending, with a plan set, "class sums on L lanes": the lanes that sum one class in the class pass, the distinct values over the
+ * batch's utterances in ascending order ("class sums on 8, 64 lanes").
  * 15 = mm_scoredposteriors_f32 (log batches only): mm_scored_fwd_kernel<NI,lds|global> + mm_scored_bwd_kernel<NI,lds|global>; the text
- * names the class cap and, for the current class plan, the term cap and where the term rows live (the endings of entry 14).
+ * names the class cap and, for the current class plan within the cap, the term cap, the lanes per class and where the term rows
+ * live (the endings of entry 14).
  * 16 = mm_classcost_f32 (log batches only): mm_classcost_fwd_kernel<NI,lds|global> + mm_classcost_bwd_kernel<NI,lds|global>; the text
  * names the class cap and says "exceed the cap" when the current class plan has more classes ("no classes set" without a plan).
  * Informational (bench.py quotes it). */

@@ -369,6 +369,8 @@ struct mm_batch_s {
     DevMem d_sc;
     int cls_C = 0;
     int64_t cls_max_M = 0, cls_terms = 0;
+    // the lanes a class's sum runs on (ClassDev::lgl, a bit per value), over the utterances of the plan: what kernels() names
+    uint32_t cls_lgl_mask = 0;
 };
 
 static bool on_pairs(mm_batch_t h) { return h->fb == Fb::Pairs || h->fb == Fb::Split; }
@@ -2623,6 +2625,13 @@ static VitLaunch vit_launch_of(mm_batch_t h) {
     vl.bp_row = int((size_t(h->max_S1p) + 255) & ~size_t(255));  // bytes of a row of one-byte back-pointers, padded to 256
     return vl;
 }
+// "; class sums on 8, 64 lanes": the distinct widths of the class pass over the utterances of the current class plan
+static std::string class_lanes_text(mm_batch_t h) {
+    std::string s;
+    for (int lgl = 0; lgl < 32; ++lgl)
+        if (h->cls_lgl_mask >> lgl & 1u) s += (s.empty() ? "" : ", ") + std::to_string(1 << lgl);
+    return "; class sums on " + s + " lanes";
+}
 int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
     if (!h || !buf || n < 2) return fail(MM_ERR_INVALID, "mm_batch_kernels: bad argument");
     if (entry == 0) h = twin_of(h);  // (ProbSemiring: the fast entry runs the log twins' kernels)
@@ -2717,7 +2726,8 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
         const std::string ni = std::to_string(pl.NI);
         s = "mm_log_kernel<MODE_FB," + ni + ",1> (forward) + mm_arcclass_kernel<" + ni + "," + where_of(pl.global) +
             "> (backward: the classified arcs' terms by rank, a row of class sums per frame); state vectors " + (pl.global ? "in global memory" : "in LDS") +
-            (h->cls_image.empty() ? "; no classes set" : h->cls_max_M > arcclass_cap(pl) ? "; terms in global memory" : "; terms in LDS");
+            (h->cls_image.empty() ? "; no classes set"
+                                  : class_lanes_text(h) + (h->cls_max_M > arcclass_cap(pl) ? "; terms in global memory" : "; terms in LDS"));
     } else if (entry == 15) {  // mm_scoredposteriors_f32
         if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_scoredposteriors_f32 runs on log-semiring batches only");
         const ItemPlan pl = item_plan(h, ItemEntry::Scored);
@@ -2729,7 +2739,7 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
         if (h->cls_image.empty()) s += "; no classes set";
         else if (h->cls_C > cap) s += "; " + std::to_string(h->cls_C) + " classes exceed the cap";
         else
-            s += "; term cap " + std::to_string(scored_term_cap(pl, h->cls_C)) +
+            s += "; term cap " + std::to_string(scored_term_cap(pl, h->cls_C)) + class_lanes_text(h) +
                  (h->cls_max_M > scored_term_cap(pl, h->cls_C) ? "; terms in global memory" : "; terms in LDS");
     } else if (entry == 16) {  // mm_classcost_f32
         if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_classcost_f32 runs on log-semiring batches only");
@@ -3419,6 +3429,7 @@ int mm_batch_set_arc_classes(mm_batch_t h, const int32_t *cls, const int64_t *of
         Blob sbl;
         (void)sbl.add(sdescs);
         int64_t terms = 0, max_M = 0;
+        uint32_t lgl_mask = 0;
         for (size_t b = 0; b < B; ++b) {
             mm_fsm_s &f = *h->fsms[b];
             const int32_t *cb = cls + (offsets ? offsets[b] : 0);
@@ -3456,6 +3467,7 @@ int mm_batch_set_arc_classes(mm_batch_t h, const int32_t *cls, const int64_t *of
             d.C = C;
             d.cphony = m->cphony;
             d.lgl = m->M >= 32ll * C ? 6 : (m->M >= 2ll * C ? 3 : 0);
+            lgl_mask |= 1u << d.lgl;
             terms += m->M;
             max_M = std::max<int64_t>(max_M, m->M);
         }
@@ -3468,6 +3480,7 @@ int mm_batch_set_arc_classes(mm_batch_t h, const int32_t *cls, const int64_t *of
         h->cls_C = C;
         h->cls_max_M = max_M;
         h->cls_terms = terms;
+        h->cls_lgl_mask = lgl_mask;
         return int(MM_OK);
     });
 }

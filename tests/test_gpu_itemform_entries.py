@@ -6,7 +6,7 @@ references (vitwindow: the float32 restatement, bit for bit) the entries already
   H. the 70 000-state graph of test_gpu_itemform.case_random_big, alone and in one batch with a 40-state graph in either order
      (case_mixed), for the same six entries: <0,global> with no environment switch, every utterance's state_out / end_out slice at
      its state_offsets;
-  P. the pdf count at the block size: P = NT - 1, NT, NT + 1 for all ten item-form entries and pdfposteriors on the item kernel.
+  P. the pdf count at the block size: P = NT - 1, NT, NT + 1 for all thirteen item-form entries and pdfposteriors on the item kernel.
 
 Every test asserts by name, from kernels() of the batch that ran, the instance it claims to run.  No comparison here has a bar of
 its own: they are the _check / check_against_reference / _check_batch helpers of the entries' own test files, check_gamma,
@@ -53,7 +53,9 @@ ITEM = ti.ITEM
 TWO_WAVES = {"MM_DEBUG": "1", "MM_NWAVES": "2"}
 LEAK = 0.1
 NEW_ENTRIES = ["leaky", "entropy", "filter", "window", "segment", "vitwindow"]
-ALL_ENTRIES = ["pdfposteriors", "arcs", "sample", "cost", "leaky", "entropy", "filter", "window", "segment", "weighted", "vitwindow"]
+ALL_ENTRIES = ["pdfposteriors", "arcs", "sample", "cost", "leaky", "entropy", "filter", "window", "segment", "weighted", "vitwindow",
+               "arcclass", "scored", "classcost"]
+CLASS_ENTRIES = ("arcclass", "scored", "classcost")  # (run by tests/test_gpu_class_entries.boundary_entry: destination-pdf classes, C = P + 1)
 UNCAPPED = ("pdfposteriors", "sample", "vitwindow")  # (the entries whose plan keeps up to 16 waves)
 WIDE_NAMES = ["wide", "ergodic300", "lexicon"]
 # segmentposteriors' end modes per utterance: the three of them across the group's batches of two
@@ -319,5 +321,9 @@ def test_pdf_count_at_the_block_size(mm, wl, oracle, torch, entry, block, off):
         ti._cost_is(_with_env(env, lambda: ti._cost_check(mm, wl, oracle, case))[0].kernels("cost"), 8, "lds")
     elif entry == "weighted":
         _with_env(env, lambda: tw._run_case(mm, wl, torch, gs, V, lens, 89, "<8,lds>"))  # (asserts its instance itself)
+    elif entry in CLASS_ENTRIES:
+        import test_gpu_class_entries as tce
+
+        tce.boundary_entry(entry, mm, wl, oracle, case, env, NT)  # (asserts its instance, lanes per class and term rows itself)
     else:
         assert_instance(entry, run_entry(entry, mm, wl, oracle, gs, V, lens, env, what, (2, 1)), 8, "lds")

@@ -245,7 +245,9 @@ def _boundary_gammas(entry, mm, wl, oracle, case):
     gs, V, cost, lens, _ = case
     g, N = gs[0], V.shape[1]
     o, oc = oracle
-    if entry in ("pdfposteriors", "arcs", "sample"):  # (the oracle's posteriors: what _pdf_check and _size_check compare against)
+    if entry in ("pdfposteriors", "arcs", "sample", "arcclass", "scored", "classcost"):  # (the oracle's posteriors: what _pdf_check and
+        # _size_check compare against; the arc-class entry's xi by destination pdf is gamma one frame on, the scored entry is run with
+        # U NULL as well as with scores, and the class costs do not touch gamma)
         return list(oc.batch_shared(graphs.to_oracle(o, g), g.state2pdf, g.P, V, lens, dtype=np.float64)[0])
     if entry == "cost":
         f = wl.to_fsm(mm, g)

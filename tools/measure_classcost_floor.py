@@ -1,6 +1,7 @@
 """The float32 floor of the expected class-cost recursion, on the CPU: tests/classcost_reference.py's float32 mode (r', t', the class
 term and every sum over them in float32, the offsets in float64) against its float64 mode, on the very inputs of
-tests/test_gpu_classcost.py (its case functions, with D given and with D NULL).  The worst |grad_f32 - grad_f64| / G_b it prints is
+tests/test_gpu_classcost.py (its case functions, with D given and with D NULL) and on the classcost inputs of
+tests/test_gpu_class_entries.py (classcost_cases: class counts at the block size, the 70 000-state graph, wide rows, P at the block size).  The worst |grad_f32 - grad_f64| / G_b it prints is
 classcost_reference.GRAD_F32_FLOOR; 10 x that (capped at 1e-4) is the absolute part of the gradient's bar.  No GPU involved: the
 kernel is never the source of its own tolerance.
 
@@ -49,11 +50,12 @@ def main():
     mm = ge.load_package()
     wl = importlib.import_module(mm.__name__ + ".workloads")
     import classcost_reference as ccr
+    import test_gpu_class_entries as tce
     import test_gpu_classcost as t
 
     rows, worst = [], 0.0
     cap = cap_of_the_cap_case(mm, wl, args.cap)
-    for name, _, _, _, gs, clss, nc, V, lens in t.all_cases(mm, wl, cap):
+    for name, _, _, _, gs, clss, nc, V, lens in t.all_cases(mm, wl, cap) + tce.classcost_cases(mm, wl):
         fs = {id(g): wl.to_fsm(mm, g) for g in gs}
         N = V.shape[1]
         A, D = t._costs(40, len(gs), N, nc, V.shape[2])
