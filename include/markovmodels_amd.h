@@ -984,6 +984,16 @@ int mm_debug_row_product_ex(mm_fsm_t fsm, int direction, int flags, const float 
  * cost of the most / least loaded wave, modelled LDS cycles per gather before / after the bank-aware placement}. */
 int mm_debug_split_product(mm_fsm_t fsm, int H, int direction, const float *in, float *out, double stats[8]);
 
+/* Test aid (host only, no GPU): the pdf-major table of the pair form of `direction` (mm_rows.h RowGraph::pdftab: what the
+ * pair kernels' phase B sums the posteriors through), packed like mm_debug_row_product_ex packs the pair forms, both directions,
+ * the forward form's partner fields filled.  rows receives the number of rows S1; tab [S1] the table (8 * own position |
+ * (8 * position in the other direction's numbering) << 16, rows in pdf-major order); pdfse [2 * (P + 1)] the (first, end) of
+ * each pdf's range; slots [S1][2] the two slot-table words of every lane that finishes a row, in the order of the slot table
+ * (word 1's high half, / 8, is the row's place in tab).  The forms are packed afresh from the FSM's unpruned matrices by the same
+ * make_rows / set_partner code as the forms a batch uploads (those are packed from the pruned matrices): the same construction,
+ * not the very table a kernel reads. */
+int mm_debug_pair_pdftab(mm_fsm_t fsm, int direction, int64_t *rows, uint32_t *tab, uint16_t *pdfse, uint32_t *slots);
+
 /* Test aid (host only, no GPU): the product evaluated THROUGH THE WAVE FORM of the wave kernel (one wave per direction:
  * segments of 64 / g rows, at most 4 arcs per lane and segment, log2 weights, lane-group log-sum-exp).  stats (may be
  * NULL) receives {arc slots per lane, segments, real arcs / arc slots, modelled LDS cycles per gather}.

@@ -81,6 +81,7 @@ SYMBOLS = [
     "mm_debug_row_product",
     "mm_debug_row_product_ex",
     "mm_debug_split_product",
+    "mm_debug_pair_pdftab",
     "mm_debug_wave_product",
     "mm_debug_stream_product",
     "mm_debug_stream_team_product",
@@ -235,6 +236,8 @@ def _load():
     lib.mm_debug_stream_team_product.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
     lib.mm_debug_split_product.restype = C.c_int
     lib.mm_debug_split_product.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+    lib.mm_debug_pair_pdftab.restype = C.c_int
+    lib.mm_debug_pair_pdftab.argtypes = [vp, C.c_int, C.POINTER(i64), vp, vp, vp]
     lib.mm_debug_row_product_ex.restype = C.c_int
     lib.mm_debug_row_product_ex.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
     return lib

@@ -1118,7 +1118,7 @@ static int quad_variant(mm_fsm_t f, int dir, int KQ, bool verbose, QuadVariant *
 // the device image of a row-lane form: sections of one blob (offsets in RowBlob) ...
 struct RowBlob {
     Blob bl;
-    size_t o_w, o_a, o_s, o_sc, o_ptr, o_col, o_cw, o_pdf, o_pse, o_init, o_ord, o_pt;
+    size_t o_w, o_a, o_s, o_sc, o_ptr, o_col, o_cw, o_pdf, o_pse, o_init, o_ord, o_pt, o_tab;
 };
 static void row_variant_blob(RowVariant &v, bool pad, RowBlob &rb) {
     // (zero rows up to MM_ROW_KA_PAD arc slots: the kernels load their whole register window unconditionally)
@@ -1131,6 +1131,7 @@ static void row_variant_blob(RowVariant &v, bool pad, RowBlob &rb) {
     rb.o_ptr = bl.add(v.g.rowptr), rb.o_col = bl.add(v.g.col), rb.o_cw = bl.add(v.g.cw);
     rb.o_pdf = bl.add(v.g.rowpdf), rb.o_pse = bl.add(v.g.pdfse), rb.o_init = bl.add(v.init), rb.o_ord = bl.add(v.g.order);
     rb.o_pt = bl.add(v.ptab);
+    rb.o_tab = bl.add(v.g.pdftab);
 }
 // ... and the form's device descriptor once the blob sits at `base`
 static void row_variant_bind(mm_fsm_t f, RowVariant &v, const RowBlob &rb, char *base, float thr) {
@@ -1147,6 +1148,7 @@ static void row_variant_bind(mm_fsm_t f, RowVariant &v, const RowBlob &rb, char 
     d.init = reinterpret_cast<const float *>(base + rb.o_init);
     d.order = reinterpret_cast<const int *>(base + rb.o_ord);
     d.ptab = v.ptab.empty() ? nullptr : reinterpret_cast<const unsigned *>(base + rb.o_pt);
+    d.pdftab = v.g.pdftab.empty() ? nullptr : reinterpret_cast<const unsigned *>(base + rb.o_tab);
     d.KA = v.g.KA;
     d.NWC = v.g.NWC;
     d.nslotrows = v.g.nslotrows;
@@ -1744,6 +1746,35 @@ int mm_debug_row_product_ex(mm_fsm_t f, int direction, int flags, const float *i
         stats[6] = g.conflict_before;
         stats[7] = g.conflict_after;
     }
+    return MM_OK;
+}
+
+int mm_debug_pair_pdftab(mm_fsm_t f, int direction, int64_t *rows, uint32_t *tab, uint16_t *pdfse, uint32_t *slots) {
+    if (!f || direction < 0 || direction > 1 || !rows || !tab || !pdfse || !slots) return fail(MM_ERR_INVALID, "mm_debug_pair_pdftab: bad argument");
+    if (f->semiring != MM_LOG) return fail(MM_ERR_INVALID, "mm_debug_pair_pdftab: log-semiring FSMs only");
+    // both directions as pack_both() builds them (the forward form's partner halves come from the backward numbering), with the
+    // options and matrices of mm_debug_row_product_ex
+    DebugOpts dbg;
+    dbg.no_pdf_halves = process_debug_opts().no_pdf_halves;
+    RowGraph g[2];
+    const std::vector<int32_t> none;
+    const Csr *m = f->mat;
+    if ((f->S1 + 1) * 4 > MM_ROW_RS || !make_rows(f->S1, m[0].rowptr, m[0].col, m[0].val, f->s2p, f->P1, false, none, pair_pack_opts(dbg, 0, false), g[0]) ||
+        !make_rows(f->S1, m[1].rowptr, m[1].col, m[1].val, f->s2p, f->P1, true, g[0].pos, pair_pack_opts(dbg, 1, false), g[1]))
+        return fail(MM_ERR_UNSUPPORTED, "mm_debug_pair_pdftab: the FSM does not fit the pair form");
+    set_partner(g[0], g[1].pos);
+    const RowGraph &r = g[direction];
+    if (int64_t(r.pdftab.size()) != f->S1 || int64_t(r.pdfse.size()) != 2 * f->P1) return fail(MM_ERR_UNSUPPORTED, "mm_debug_pair_pdftab: table sizes");
+    *rows = f->S1;
+    std::copy(r.pdftab.begin(), r.pdftab.end(), tab);
+    std::copy(r.pdfse.begin(), r.pdfse.end(), pdfse);
+    int64_t n = 0;
+    for (size_t e = 0; e + 1 < r.slots.size(); e += 2) {
+        if (int((r.slots[e] & 0xffffu) / uint32_t(r.scale)) == r.trash) continue;
+        if (n < f->S1) slots[2 * n] = r.slots[e], slots[2 * n + 1] = r.slots[e + 1];
+        ++n;
+    }
+    if (n != f->S1) return fail(MM_ERR_UNSUPPORTED, "mm_debug_pair_pdftab: finishing lanes");
     return MM_OK;
 }
 
@@ -2586,7 +2617,8 @@ static std::string fb_kernels(mm_batch_t h) {
     }
     case Fb::Pairs: {
         const std::string k = std::to_string(mm_pair_nj(h->max_P1));
-        return "mm_fbp_kernel<" + k + ",A>, then <" + k + ",B> (forward and backward agents in one grid), mm_pair_finish_kernel, then for marked "
+        const std::string small = pair_small_instances(pair_launch_of(h)) ? ", the instances for graphs of up to 127 states" : "";
+        return "mm_fbp_kernel<" + k + ",A>, then <" + k + ",B> (forward and backward agents in one grid" + small + "), mm_pair_finish_kernel, then for marked "
             "utterances only " +
             (h->dpair_ok ? "mm_fbd_kernel<" + k + ",A>, then <" + k + ",B> (float64, one utterance per workgroup" +
                                (h->wpair_ok ? std::string("); FIRST and alone while the inputs are hard: mm_fbw_kernel<") + k + ",A>, then <" + k +

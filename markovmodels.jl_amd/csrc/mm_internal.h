@@ -115,6 +115,8 @@ struct PairLaunch {
     int nwc = 1, slotrows = 0, max_P1 = 0, pair_ka = 0, H = 1;
     bool small = false;  // every FSM has at most 127 states: the instance whose service wave copies and scans one row of 64 float4
 };
+// whether a launch runs the small-graph instances (mm_launch_pairs, mm_launch_pair_export, and what mm_batch_kernels says)
+inline bool pair_small_instances(const PairLaunch &pl) { return pl.H == 1 && pl.small && pl.max_P1 <= 128; }
 int mm_launch_pairs(const PairLaunch &pl, const RunParams &p, hipStream_t s0);
 // alpha / beta export on the pair kernels (phase A of one direction over all frames + a layout pass): dir 0 alpha, 1 beta
 bool mm_pair_export_fits(const PairLaunch &pl);

@@ -51,11 +51,17 @@ __device__ __forceinline__ void ldsw2(unsigned addr, float a, float b) {
 constexpr int pair_pc(int NJ) { return NJ > 4 ? 64 * NJ : 256; }
 // (teams of 8: the team's vector of pairs is 48 KB, twice: a ring of two partner vectors there as well)
 constexpr int pair_nr(int RS, int PC) { return (PC > 256 || RS > 16384) ? 2 : 3; }
-template <int RS, int PHASE, int RSH = 2 * RS, int PC = 256>
+// NQ (the one-workgroup phase-B instances with linear finishes): no q vector.  The pdf sums of step t - 1 multiply, during step t,
+// the step's own vector -- PP, intact until the barrier -- with the partner row of step t - 1, through the form's pdf-major table
+// (TAB: own position | partner position << 16).  The partner ring therefore holds 4 rows (the row of step t + 2 lands while the
+// row of step t - 1 is read), and the service wave keeps a second copy of the staged factors in a ring of 4 (EQ: the pdf sums
+// divide by the factors of step t - 1 while EM of that parity is staged for step t + 1).  4 rows + table + factor ring take
+// what 3 rows + 2 q vectors took: the slot table stays where it was.
+template <int RS, int PHASE, int RSH = 2 * RS, int PC = 256, bool NQ = false>
 struct PairLay {
     static constexpr unsigned RS2 = 2 * RS;
     static constexpr unsigned PC4 = 4u * PC, PC8 = 8u * PC;
-    static constexpr int NR = pair_nr(RS, PC);       // vectors of the partner-row ring
+    static constexpr int NR = NQ ? 4 : pair_nr(RS, PC);  // vectors of the partner-row ring
     static constexpr unsigned RAWS = 2u * PC4;       // bytes of one ring entry of the raw emissions (both utterances)
     static constexpr unsigned XPS = 2u * PC;         // (teams) floats of one slot of published per-pdf partial sums
     static constexpr unsigned PP(int par) { return unsigned(par) * RS2; }                          // p pairs [pos][2]
@@ -79,7 +85,10 @@ struct PairLay {
     static constexpr unsigned FIX = PDFSE + PC4;
     static constexpr unsigned AL(int k) { return FIX + unsigned(k) * RSH; }                        // partner rows (phase B), k < NR
     static constexpr unsigned Q(int par) { return FIX + unsigned(NR) * RSH + unsigned(par) * RSH; }  // q pairs [qpos][2] (phase B)
-    static constexpr unsigned SLOTS = PHASE ? FIX + unsigned(NR + 2) * RSH : FIX;
+    static constexpr unsigned TAB = FIX + 4u * RSH;                                                // (NQ) pdf-major table, RSH / 8 words
+    static constexpr unsigned EQ(int k) { return FIX + 4u * RSH + RSH / 2u + unsigned(k) * PC8; }  // (NQ) staged factors of step k & 3
+    static_assert(!NQ || (pair_nr(RS, PC) == 3 && 4u * PC8 <= RSH / 2u), "the no-q layout replaces a ring of 3 and two q vectors");
+    static constexpr unsigned SLOTS = PHASE ? FIX + unsigned(pair_nr(RS, PC) + 2) * RSH : FIX;
 };
 inline size_t pair_lds_bytes(int RS, int phase, int nslotrows, int RSH = 0, int PC = 256) {
     const size_t fix = size_t(4 * RS) + size_t(8 * 4 * PC) + size_t(4 * 8 * PC) + 256 + (pair_nr(RS, PC) == 2 ? 64 : 128) + size_t(4 * PC);
@@ -108,6 +117,13 @@ typedef __attribute__((address_space(1))) mm_u64 mm_gu64;
 #ifndef MM_PAIR_LINFIN
 #define MM_PAIR_LINFIN 1
 #endif
+#ifndef MM_PAIR_NOQ
+#define MM_PAIR_NOQ 1  // 0: the one-workgroup linear phase-B instances keep their q vector (the code before the pdf-major table)
+#endif
+// table words of the no-q pdf sums that a lane keeps in registers across the steps.  Measured on config 3: 2 words 128 VGPRs / 0
+// spilled and 2.485 - 2.500 ms per call, 0 words 125 / 0 and 2.515 - 2.555 ms; 3 and 4 words spill 12 and 8 VGPRs.
+constexpr int kPairPdfRegs = 2;
+static_assert(kPairPdfRegs >= 0 && kPairPdfRegs <= 2, "more than 2 table words in registers spill in phase B");
 #ifndef MM_PAIR_SCAN_BATCH
 #define MM_PAIR_SCAN_BATCH 8  // 16-byte LDS reads the service wave's scan keeps in flight
 #endif
@@ -328,9 +344,10 @@ __device__ __forceinline__ float wave_max_of2(float a, float b) {
 // tell them apart), and the service wave's own chain of round trips is what bounds a step since the finishes went linear --, the
 // two maxima share one DPP ladder, and a pdf's two factors leave in ONE 8-byte write.
 // (ADAPT: X = minus the smallest finite log2 factor of the step; else a fixed bound, MM_LINF_EMIN, and marks for what is below it)
-template <int NJ, bool ADAPT>
+// (COPY: the factors also go to dst2 -- the ring the no-q pdf sums divide by, which outlives the parity buffer)
+template <int NJ, bool ADAPT, bool COPY = false>
 __device__ __forceinline__ void pair_stage_em2(unsigned dst, unsigned raw0, unsigned raw1, int n, int len0, int len1, int P, int lane, float S0,
-                                               float S1, float (&E)[2], float &X, int *mark0, int *mark1) {
+                                               float S1, float (&E)[2], float &X, int *mark0, int *mark1, unsigned dst2 = 0u) {
     float v0[NJ], v1[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
@@ -358,7 +375,9 @@ __device__ __forceinline__ void pair_stage_em2(unsigned dst, unsigned raw0, unsi
         const int q = lane + 64 * j;
         if (q <= P) {
             const float x0 = v0[j] - e0 - S0, x1 = v1[j] - e1 - S1;
-            ldsw2(dst + 8u * (unsigned)q, fast_exp2(x0), fast_exp2(x1));
+            const float f0 = fast_exp2(x0), f1 = fast_exp2(x1);
+            ldsw2(dst + 8u * (unsigned)q, f0, f1);
+            if constexpr (COPY) ldsw2(dst2 + 8u * (unsigned)q, f0, f1);
             n0 = max_nc(n0, v0[j] > MM_NINF ? -x0 : 0.f);
             n1 = max_nc(n1, v1[j] > MM_NINF ? -x1 : 0.f);
         }
@@ -651,6 +670,89 @@ __device__ __forceinline__ void pair_pdf_sums(unsigned qbase, unsigned pdfse_bas
     }
 }
 
+// The pdf sums without a q vector (the one-workgroup phase-B instances with linear finishes).  The step's vector in LDS is
+// p = s * e_pdf, so  sum_{state in pdf} s * al = sum (p[own position] / e_pdf) * al[partner position]:  per state one gather from the
+// step's own vector and one from the partner row, through the form's pdf-major table (own position | partner position << 16, the
+// ranges of pdfse).  p is scaled back BEFORE it meets al: the partner's value carries the same frame's emission, and p * al would
+// hold e_pdf squared -- a pdf whose factor is 2^-70 would leave the float range where s * al does not.  A factor that is zero or
+// subnormal (an emission of -inf) gives exactly 0.  Lanes per pdf, group sum and the order of the additions as in pair_pdf_sums.
+// tw: the lane's first NTW table words of the FIRST pass (its states are the same in every step), pair_pdf_lane(): their gathers
+// leave at once, the lane's next states up to the fourth follow through the table in LDS, further ones in a loop.  An entry
+// beyond the pdf's range reads the trash position of the own vector (trash8), which holds 0: its finishes multiply by the factor 0.
+// What that rests on: trash8 < 2^16, so the entry's partner half is 0 and its second gather reads position 0 of the partner row,
+// which must be finite for 0 * al to be 0.  An inf or NaN there (an overflow in the other agent: its utterances are marked anyway)
+// reaches every pdf with such a lane, not only the pdf of position 0 as a q vector would have it; the frame sum is then NaN and
+// mm_pair_finish_kernel marks the utterance either way.
+// The reciprocal: a staged factor is 2^(v - E - S) with v <= E, at most 2^-S; |S| stays far below 126 on unmarked utterances (the
+// normaliser follows the vector's maximum, whose range the step's marks guard), so v_rcp_f32 never meets a factor above 2^126,
+// which it would flush to 0.
+template <int LG, int NTW>
+__device__ __forceinline__ void pair_pdf_lane(unsigned (&tw)[NTW ? NTW : 1], unsigned tab_base, unsigned pdfse_base, int P1, int wave, int lane, unsigned trash8) {
+    constexpr int LP = 1 << LG, PPW = 64 >> LG;
+    const int pdf = wave * PPW + (lane >> LG);
+    const unsigned se = ldsru(pdfse_base + 4u * (unsigned)(pdf < P1 ? pdf : 0));  // first | end << 16
+    const unsigned i0 = (se & 0xffffu) + (unsigned)(lane & (LP - 1)), i1 = pdf < P1 ? se >> 16 : 0u;
+#pragma unroll
+    for (int k = 0; k < NTW; ++k) {
+        const unsigned i = i0 + (unsigned)(LP * k);
+        const unsigned w = ldsru(tab_base + 4u * (i < i1 ? i : 0u));
+        tw[k] = i < i1 ? w : trash8;
+    }
+}
+__device__ __forceinline__ void pdf_term(mm_f32x2 &s, const mm_f32x2 &v, const mm_f32x2 &r, const mm_f32x2 &a) {
+    mm_f32x2 sv;
+    asm("v_pk_mul_f32 %0, %1, %2" : "=v"(sv) : "v"(v), "v"(r));
+    asm("v_pk_fma_f32 %0, %1, %2, %0" : "+v"(s) : "v"(sv), "v"(a));
+}
+// one pass: the pdfs p0 .. p0 + PPW - 1 of the wave
+template <int LG, int NTW>
+__device__ __forceinline__ void pair_pdf_pass(const unsigned (&tw)[NTW ? NTW : 1], int p0, unsigned pbase, unsigned albase, unsigned ebase, unsigned tab_base,
+                                              unsigned pdfse_base, unsigned psum_base, int P1, int lane, unsigned trash8) {
+    constexpr int LP = 1 << LG;
+    const int pdf = p0 + (lane >> LG);
+    mm_f32x2 s = {0.f, 0.f};
+    if (pdf < P1) {
+        mm_f32x2 v[4], a[4];
+#pragma unroll
+        for (int k = 0; k < NTW; ++k) {  // (these gathers wait for nothing)
+            v[k] = ldsr2(pbase + (tw[k] & 0xffffu));
+            a[k] = ldsr2(albase + (tw[k] >> 16));
+        }
+        const unsigned se = ldsru(pdfse_base + 4u * pdf);  // first | end << 16
+        const mm_f32x2 e = ldsr2(ebase + 8u * (unsigned)pdf);
+        const unsigned i0 = (se & 0xffffu) + (unsigned)(lane & (LP - 1)), i1 = se >> 16;
+        unsigned w[4];
+#pragma unroll
+        for (int k = NTW; k < 4; ++k) w[k] = ldsru(tab_base + 4u * (i0 + LP * k < i1 ? i0 + LP * k : 0u));
+        mm_f32x2 r;  // 1 / e_pdf of the two utterances, 0 for a factor that is zero or subnormal
+        r.x = e.x >= 1.17549435e-38f ? __builtin_amdgcn_rcpf(e.x) : 0.f;
+        r.y = e.y >= 1.17549435e-38f ? __builtin_amdgcn_rcpf(e.y) : 0.f;
+#pragma unroll
+        for (int k = NTW; k < 4; ++k) {
+            if (!(i0 + LP * k < i1)) w[k] = trash8;
+            v[k] = ldsr2(pbase + (w[k] & 0xffffu));
+            a[k] = ldsr2(albase + (w[k] >> 16));
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) pdf_term(s, v[k], r, a[k]);
+        for (unsigned i = i0 + 4u * LP; i < i1; i += LP) {
+            const unsigned wi = ldsru(tab_base + 4u * i);
+            pdf_term(s, ldsr2(pbase + (wi & 0xffffu)), r, ldsr2(albase + (wi >> 16)));
+        }
+    }
+    const float s0 = grp_sum(s.x, LG), s1 = grp_sum(s.y, LG);
+    if (pdf < P1 && (lane & (LP - 1)) == 0) ldsw2(psum_base + 8u * pdf, s0, s1);
+}
+template <int LG, int NTW>
+__device__ __forceinline__ void pair_pdf_sums_lin(const unsigned (&tw)[NTW ? NTW : 1], unsigned pbase, unsigned albase, unsigned ebase, unsigned tab_base,
+                                                  unsigned pdfse_base, unsigned psum_base, int P1, int wave, int NWC, int lane, unsigned trash8) {
+    constexpr int PPW = 64 >> LG;
+    const unsigned none[1] = {0u};
+    if (wave * PPW < P1) pair_pdf_pass<LG, NTW>(tw, wave * PPW, pbase, albase, ebase, tab_base, pdfse_base, psum_base, P1, lane, trash8);
+    for (int p0 = (wave + NWC) * PPW; p0 < P1; p0 += NWC * PPW)
+        pair_pdf_pass<LG, 0>(none, p0, pbase, albase, ebase, tab_base, pdfse_base, psum_base, P1, lane, trash8);
+}
+
 // The arcs of a compute wave for two utterances (8-byte gathers, D pairs of arcs ahead of the FMAs), statically unrolled
 // (the graph registers need static indices).  A segment may end after any pair of arcs; pair_two() / MM_PAIR_TWO test
 // the end mask once per TWO pairs.  Every wave runs the whole window: the pairs behind its last segment have weight 0
@@ -805,7 +907,10 @@ __device__ __forceinline__ void pair_agent(const RunParams &p, int pair, int hse
     extern __shared__ float lds[];
     const int DIR = DIRT < 0 ? __builtin_amdgcn_readfirstlane(rdir) : DIRT;
     const unsigned long long x_tmo = p.x_timeout;  // (teams) ticks of s_memrealtime a poll waits before it gives the team up
-    using L = PairLay<RS, PHASE, RSH, pair_pc(NJ)>;
+    // NOQ: phase B of one workgroup with linear finishes keeps no q vector -- the finish is phase A's without the store, and the
+    // pdf sums multiply the step's vector with the partner row themselves (PairLay NQ, pair_pdf_sums_lin)
+    constexpr bool NOQ = MM_PAIR_NOQ != 0 && PHASE == 1 && H == 1 && MM_PAIR_LINFIN != 0 && NJ <= 4;
+    using L = PairLay<RS, PHASE, RSH, pair_pc(NJ), NOQ>;
 #ifndef MM_PAIR_DA
 #define MM_PAIR_DA 3
 #endif
@@ -883,8 +988,12 @@ __device__ __forceinline__ void pair_agent(const RunParams &p, int pair, int hse
 
     // ---- LDS set-up
     for (unsigned q = tid * 4u; q < 2u * L::RS2; q += NT * 4u) ldsw(L::PP(0) + q, 0.f);
-    if constexpr (PHASE == 1)
+    if constexpr (PHASE == 1 && !NOQ)
         for (unsigned q = tid * 4u; q < 2u * RSH; q += NT * 4u) ldsw(L::Q(0) + q, 0.f);
+    if constexpr (NOQ) {  // the form's pdf-major table
+        const auto tab = as_global(uni(ud.rp[DIR].pdftab));
+        for (int q = tid; q < S1 && q < (int)(RSH / 8u); q += NT) ldswu(L::TAB + 4u * q, tab[q]);
+    }
     if (tid < 32) ldsw(L::MS(0) + 4u * tid, 0.f);
     if (tid < 4) ldswu(L::MX(0) + 4u * tid, 0u);
     if (tid < 4) ldsw(L::EM(tid >> 1) + 8u * P1p + 4u * (tid & 1), LINF ? 0.f : MM_NINF);  // the emission slot of lanes without a row
@@ -1015,8 +1124,8 @@ __device__ __forceinline__ void pair_agent(const RunParams &p, int pair, int hse
                 pair_stage_em_wide<NJ, LINF>(L::EM(t & 1), L::RAW(0, 0) + L::RAWS * (unsigned)(t & 3), L::RAW(0, 1) + L::RAWS * (unsigned)(t & 3), frame_of(t),
                                              U[0].len, U[1].len, P, sl, E, S[0], S[1], redo0, redo1);
             } else if constexpr (LINF) {
-                pair_stage_em2<NJ, ADAPT>(L::EM(t & 1), L::RAW(0, 0) + L::RAWS * (unsigned)(t & 3), L::RAW(0, 1) + L::RAWS * (unsigned)(t & 3), frame_of(t),
-                                          U[0].len, U[1].len, P, sl, S[0], S[1], E, X, redo0, redo1);
+                pair_stage_em2<NJ, ADAPT, NOQ>(L::EM(t & 1), L::RAW(0, 0) + L::RAWS * (unsigned)(t & 3), L::RAW(0, 1) + L::RAWS * (unsigned)(t & 3), frame_of(t),
+                                               U[0].len, U[1].len, P, sl, S[0], S[1], E, X, redo0, redo1, NOQ ? L::EQ(t & 3) : 0u);
             } else {
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
@@ -1061,7 +1170,7 @@ __device__ __forceinline__ void pair_agent(const RunParams &p, int pair, int hse
         for (int t = t0; t <= t0 + 3; ++t) dma_raw(t);
         if constexpr (PHASE == 1) {
             dma_partner(t0 + 1);
-            if constexpr (L::NR == 3) dma_partner(t0 + 2);  // (a ring of 2: step t0 + 1 requests the row of t0 + 2 at its top)
+            if constexpr (L::NR >= 3) dma_partner(t0 + 2);  // (a ring of 2: step t0 + 1 requests the row of t0 + 2 at its top)
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const PairHand h = hand[u];
@@ -1445,6 +1554,10 @@ __device__ __forceinline__ void pair_agent(const RunParams &p, int pair, int hse
         __syncthreads();  // (2)
         if constexpr (H > 1) xplain = __builtin_amdgcn_readfirstlane(ldsru(L::XFLAG)) != 0u;
         bool cdead = H > 1 && (p.x_sleep & 0x200) != 0;  // (split kernels) a poll of this wave timed out: it waits no more
+        // (no-q instances) the table words of the lane's first states in the first pass of the pdf sums: the same in every step
+        constexpr int NTW = kPairPdfRegs;
+        unsigned ptw[NTW ? NTW : 1] = {0u};
+        if constexpr (NOQ) pair_pdf_lane<(NJ > 2 ? 2 : 3), NTW>(ptw, L::TAB, L::PDFSE, P1, wave, lane, 8u * (unsigned)S1);
         auto step = [&](auto RDc, int t) {
             constexpr int RD = decltype(RDc)::value, WR = 1 - RD;
             float vmx0 = 0.f, vmx1 = 0.f;  // (teams) maxima of what this wave writes into the step's vector
@@ -1460,7 +1573,7 @@ __device__ __forceinline__ void pair_agent(const RunParams &p, int pair, int hse
                 // which need its slot word as their address, never wait for a load issued just before them
                 unsigned sa = slot_base;
                 unsigned info, info2 = 0u, infoN, info2N = 0u;
-                if constexpr (PHASE == 1) {  // (both words of a slot in one 8-byte read: one LDS instruction less per finish)
+                if constexpr (PHASE == 1 && !NOQ) {  // (both words of a slot in one 8-byte read: one LDS instruction less per finish)
                     const mm_u32x2 w0 = ldsr2u(sa), w1 = ldsr2u(sa + 512u);
                     info = w0.x;
                     info2 = w0.y;
@@ -1479,7 +1592,7 @@ __device__ __forceinline__ void pair_agent(const RunParams &p, int pair, int hse
                 // (split kernels) where the team reads this step's rows, and the step's tag as a sign
                 float *xw = H > 1 ? xsend + (long long)(t & 1) * p.x_slot - 2 * xbase : nullptr;
                 const float xsg = (H > 1 && split_tag(t, t0, 1)) ? -1.f : 1.f;
-                if constexpr (PHASE == 1) al = ldsr2((info2 & 0xffffu) + alb);
+                if constexpr (PHASE == 1 && !NOQ) al = ldsr2((info2 & 0xffffu) + alb);
                 float *rowP = rowsP + (long long)(f <= p.N + (XPT ? 1 : 0) ? f : 0) * 2 * S1p;  // (frame N + 1 is stored by the export only)
                 // even / odd arcs (phase B has no registers to spare: one chain there)
                 float worst = 0.f;
@@ -1511,7 +1624,7 @@ __device__ __forceinline__ void pair_agent(const RunParams &p, int pair, int hse
                         if constexpr (PHASE == 0) {
                             if constexpr (XPT) *reinterpret_cast<mm_f32x2 *>(reinterpret_cast<char *>(rowP) + pos8) = DIR ? sv : pv;
                             else *reinterpret_cast<mm_f32x2 *>(reinterpret_cast<char *>(rowP) + pos8) = pv;
-                        } else {
+                        } else if constexpr (!NOQ) {
                             asm("v_pk_mul_f32 %0, %1, %2" : "=v"(qv) : "v"(sv), "v"(al));  // A .* B   (:154)
                             ldsw2((info2 >> 16) + L::Q(WR), qv.x, qv.y);
                         }
@@ -1546,7 +1659,7 @@ __device__ __forceinline__ void pair_agent(const RunParams &p, int pair, int hse
                     // (a plain copy is coalesced away and paid for with register moves on the no-finish path of EVERY pair)
                     asm volatile("v_mov_b32 %0, %1" : "=v"(info) : "v"(infoN));
                     e = ldsr2((info >> 16) + L::EM(WR));
-                    if constexpr (PHASE == 1) {
+                    if constexpr (PHASE == 1 && !NOQ) {
                         asm volatile("v_mov_b32 %0, %1" : "=v"(info2) : "v"(info2N));
                         al = ldsr2((info2 & 0xffffu) + alb);
                         const mm_u32x2 w1 = ldsr2u(sa + 512u);
@@ -1569,9 +1682,14 @@ __device__ __forceinline__ void pair_agent(const RunParams &p, int pair, int hse
                 }
             }
             if constexpr (PHASE == 1)  // C' * (A .* B) of the previous step (:155)
-                if (t - 1 > t0)
+                if (t - 1 > t0) {
+                    if constexpr (NOQ)
+                        pair_pdf_sums_lin<(NJ > 2 ? 2 : 3), NTW>(ptw, L::PP(RD), L::AL(0) + (unsigned)((t - 1) & 3) * (unsigned)RSH, L::EQ(0) + (unsigned)((t - 1) & 3) * L::PC8,
+                                                            L::TAB, L::PDFSE, L::PSUM(RD), P1, wave, NWC, lane, 8u * (unsigned)S1);
+                    else
                     pair_pdf_sums<(NJ > 4 ? 1 : (NJ > 2 ? 2 : 3))>(L::Q(RD), L::PDFSE, L::PSUM(RD), P1, wave, NWC, lane, H > 1 ? xps_send + ((t - 1) & 3) * (int)L::XPS : nullptr,
                                   (H > 1 && split_tag(t - 1, t0, 2)) ? -1.f : 1.f);
+                }
             if constexpr (H > 1 && MM_SPLIT_CWPOLL) {
                 // The rows of the other sets of this step: chunk j (128 granules) of the q-th other set is item q * NG2 + j, and
                 // compute wave w receives the items w, w + NWC, ... -- all chunks are polled at the same time, one load in flight
@@ -1715,9 +1833,14 @@ __device__ __forceinline__ void pair_agent(const RunParams &p, int pair, int hse
             }
         }
         if constexpr (PHASE == 1) {
-            if (t1 > t0)
+            if (t1 > t0) {
+                if constexpr (NOQ)
+                    pair_pdf_sums_lin<(NJ > 2 ? 2 : 3), NTW>(ptw, L::PP(t1 & 1), L::AL(0) + (unsigned)(t1 & 3) * (unsigned)RSH, L::EQ(0) + (unsigned)(t1 & 3) * L::PC8, L::TAB,
+                                                        L::PDFSE, L::PSUM(t1 & 1), P1, wave, NWC, lane, 8u * (unsigned)S1);
+                else
                 pair_pdf_sums<(NJ > 4 ? 1 : (NJ > 2 ? 2 : 3))>(L::Q(t1 & 1), L::PDFSE, L::PSUM(t1 & 1), P1, wave, NWC, lane, H > 1 ? xps_send + (t1 & 3) * (int)L::XPS : nullptr,
                               (H > 1 && split_tag(t1, t0, 2)) ? -1.f : 1.f);
+            }
             __syncthreads();  // (a)
         }
     }

@@ -30,7 +30,7 @@ static int launch_pairs_ka(const PairLaunch &pl, const RunParams &p, hipStream_t
 }
 int mm_launch_pairs(const PairLaunch &pl, const RunParams &p, hipStream_t s0) {
     if (pl.pair_ka > MM_PAIR_KA) return MM_ERR_UNSUPPORTED;
-    if (pl.max_P1 <= 128) return pl.small ? launch_pairs_ka<2, true>(pl, p, s0) : launch_pairs_ka<2, false>(pl, p, s0);
+    if (pl.max_P1 <= 128) return pair_small_instances(pl) ? launch_pairs_ka<2, true>(pl, p, s0) : launch_pairs_ka<2, false>(pl, p, s0);
     if (pl.max_P1 <= 250) return launch_pairs_ka<4, false>(pl, p, s0);
     if (pl.max_P1 > MM_PAIR_P1MAX) return MM_ERR_UNSUPPORTED;
     return launch_pairs_ka<8, false>(pl, p, s0);
@@ -51,7 +51,7 @@ static int launch_pair_export(const PairLaunch &pl, const RunParams &p, int dir,
 bool mm_pair_export_fits(const PairLaunch &pl) { return pl.H == 1 && pl.pair_ka <= MM_PAIR_KA && pl.max_P1 <= 250; }
 int mm_launch_pair_export(const PairLaunch &pl, const RunParams &p, int dir, hipStream_t s0) {
     if (!mm_pair_export_fits(pl)) return MM_ERR_UNSUPPORTED;
-    if (pl.max_P1 <= 128) return pl.small ? launch_pair_export<2, true>(pl, p, dir, s0) : launch_pair_export<2, false>(pl, p, dir, s0);
+    if (pl.max_P1 <= 128) return pair_small_instances(pl) ? launch_pair_export<2, true>(pl, p, dir, s0) : launch_pair_export<2, false>(pl, p, dir, s0);
     return launch_pair_export<4, false>(pl, p, dir, s0);
 }
 size_t mm_pair_lds_bytes(int phase, int nslotrows, int max_P1) {

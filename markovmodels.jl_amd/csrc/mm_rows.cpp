@@ -730,6 +730,13 @@ bool make_rows(int64_t nrows, const std::vector<int64_t> &rowptr, const std::vec
                 }
             }
     }
+    // pair forms: the rows in pdf-major order, what slot words 0 and 1 hold as positions (own | partner << 16) -- the table the
+    // linear phase-B instances sum the posteriors through (set_partner() fills the forward form's partner halves)
+    if (want_q && opt.pair) {
+        g.pdftab.assign(size_t(nsub), 0u);
+        for (int32_t r : myrows)
+            g.pdftab[size_t(qpos[r])] = uint32_t(SC * (g.pos_base + g.pos[r])) | (uint32_t(SC * (fwd_pos.empty() ? 0 : fwd_pos[r])) << 16);
+    }
     PROF_LAP(1);
     // ---- CSR in internal numbering (exact fallback)
     g.rowptr.assign(size_t(nsub) + 1, 0);
@@ -1111,6 +1118,8 @@ void set_partner(RowGraph &g, const std::vector<int32_t> &partner_pos) {
         const uint32_t p = (g.slots[e] & 0xffffu) / SC;
         if (int(p) == g.trash) continue;
         g.slots[e + 1] = (g.slots[e + 1] & 0xffff0000u) | uint32_t(SC * partner_pos[g.order[p - uint32_t(g.pos_base)]]);
+        const size_t q = (g.slots[e + 1] >> 16) / SC;  // the row's place in pdf-major order
+        if (q < g.pdftab.size()) g.pdftab[q] = (g.pdftab[q] & 0xffffu) | (g.slots[e + 1] << 16);
     }
 }
 

@@ -72,6 +72,8 @@ struct RowGraph {
     std::vector<int32_t> rowptr, col;
     std::vector<float> cw;
     std::vector<uint16_t> pdfse;  // backward: [2 * P1] (first, end) of each pdf in pdf-major order
+    std::vector<uint32_t> pdftab; // pair forms: [rows] in pdf-major order (the ranges of pdfse), the row's fields of slot words 0 and 1:
+                                  // 8 * position | (8 * position in the other direction's numbering) << 16
     double conflict_before = 0, conflict_after = 0;  // modelled LDS cycles per gather instruction
     double pad_eff = 0;           // real arcs / arc slots
     float wmin_log2 = 0;          // smallest log2 weight of an arc

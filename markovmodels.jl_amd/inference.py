@@ -210,6 +210,20 @@ class CompiledFSM:
         check(lib.mm_debug_row_product_ex(self._h, direction, flags, x.ctypes.data, out.ctypes.data, stats.ctypes.data))
         return out, stats
 
+    def pair_pdf_table(self, direction: int = 0):
+        """The pdf-major table of the pair form (what phase B of the pair kernels sums the posteriors through; test aid).
+        Returns (table [S1] = 8 * position | (8 * partner position) << 16, pdfse [P + 1, 2] = (first, end) of each pdf's range,
+        slot words [S1, 2] of the lanes that finish a row)."""
+        import ctypes as C
+
+        tab = np.zeros(self.S1, dtype=np.uint32)
+        pdfse = np.zeros((self.P1, 2), dtype=np.uint16)
+        slots = np.zeros((self.S1, 2), dtype=np.uint32)
+        rows = C.c_int64(0)
+        check(lib.mm_debug_pair_pdftab(self._h, direction, C.byref(rows), tab.ctypes.data, pdfse.ctypes.data, slots.ctypes.data))
+        assert rows.value == self.S1
+        return tab, pdfse, slots
+
     def split_product(self, x: np.ndarray, direction: int = 0, H: int = 2):
         """Host evaluation of the product through the split pair forms (teams of H workgroups; test aid).  Returns
         (out, stats = [KA, positions of the team's vector, segments, arcs / arc slots, max / min wave cost, LDS
