@@ -133,6 +133,8 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * live (the endings of entry 14).
  * 16 = mm_classcost_f32 (log batches only): mm_classcost_fwd_kernel<NI,lds|global> + mm_classcost_bwd_kernel<NI,lds|global>; the text
  * names the class cap and says "exceed the cap" when the current class plan has more classes ("no classes set" without a plan).
+ * 17 = mm_classpath_f32 (tropical batches only): mm_classpath_fwd_kernel<NI,lds|global> + mm_classpath_trace_kernel; the text names
+ * the class cap and says "exceed the cap" when the plan of mm_batch_set_path_classes has more classes ("no classes set" without one).
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -771,6 +773,65 @@ int mm_viterbiwindow_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, i
                          const float *state_in, const int32_t *closed, const int32_t *commit, int commit_converged, float *state_out,
                          float *mcommit, int32_t *ncommit, int32_t *path, int64_t path_stride_b, float *score, int32_t *converged,
                          void *stream);
+
+/* Best paths that report arc classes, under per-frame arc-class scores: the tropical twin of mm_scoredposteriors_f32.  What a
+ * decoder or an aligner hands on is the sequence of labels with their times -- words, phones, transition-ids, boundaries: things
+ * that sit on ARCS -- and the states do not determine it, because parallel entries between the same two states are allowed and the
+ * back-pointers of mm_viterbi_f32 keep the source state alone.  A plan (mm_batch_set_path_classes) gives every stored entry
+ * k = (i_k -> j_k) of an FSM's T_hat -- the phony-final column and the phony self-loop included, in the order mm_arcposteriors_f32
+ * reports them -- a class cls[k] in {-1, 0, ..., C-1}.  For utterance b of length len, frames 1-based in the formulas and t 0-based
+ * as in mm_arcclassposteriors_f32, f the phony final state:
+ *
+ *   d_1(j)  = alpha_hat(j) + lhs_1(j)
+ *   x_n(k)  = (T_hat[k] + d_{n-1}(i_k)) + U[b, n-2, cls k]     one float32 add, then one more; class -1 and the
+ *                                                              phony self-loop: no second add.  U == NULL: no second add at all
+ *   d_n(j)  = (max_{k into j} x_n(k)) + lhs_n(j)                n = 2 .. len+1
+ *   bp_n(j) = source state, bc_n(j) = class of THE maximiser: the lowest source state; among parallel maximisers from that
+ *             state the lowest class id, with -1 ordered behind every class.  (-1, -1) if the max is -inf
+ *   score   = d_{len+1}(f);  s_{len+1} = f;  s_n = bp_{n+1}(s_{n+1});  path(n-1) = s_n;
+ *   classes(t) = bc_{t+2}(s_{t+2}),  t = 0 .. len-1      (t = len-1: the arc into the phony final state)
+ *
+ * path[b, n] for n >= len and classes[b, t] for t >= len are -1.  An utterance without a path (len = 0 included) has path and classes
+ * all -1 and score = -inf.  U is finite or -inf; rows t >= len of U are never read; nothing is NaN.  Float adds and a max only,
+ * nothing that can contract; natural log throughout (the score row is staged unscaled, as the tropical kernels stage emissions);
+ * no atomics: a repeated call returns the same bits.
+ * Consequences: (a) with U NULL, path and score are mm_viterbi_f32's, bit for bit, whatever the plan.  (b) With U[b, t, c] = u_c,
+ * path and score are those of mm_viterbi_f32 on the FSM with weights w_k + u_cls[k] -- bit for bit wherever every sum is exact
+ * (weights, scores and emissions that are multiples of 1/16 of moderate size).  (c) U = -inf at (t, c) removes the class from that
+ * transition: classes[b, t] != c, or the utterance has no path.  (d) score = the float32 sum along the returned path in the
+ * recursion's order (exact on such a grid).  (e) Relabelling the classes by an order-preserving map changes `classes` by that map
+ * and nothing else.
+ *
+ * mm_batch_set_path_classes: MM_TROPICAL batches only (others: MM_ERR_UNSUPPORTED; mm_batch_set_arc_classes keeps refusing tropical
+ * batches).  Arguments and error codes of mm_batch_set_arc_classes; C > 65534: MM_ERR_UNSUPPORTED.  Host work only: it builds the
+ * 16-bit class plane of the forward item form of every distinct (FSM, class array) -- an unclassified entry, the phony self-loop
+ * and every padding slot carry the id C --; the first mm_classpath_f32 call behind it puts the planes on the device in one
+ * allocation and one copy (never during a stream capture: MM_ERR_INVALID).  Calling it again replaces the plan.
+ * mm_batch_path_class_info: C = the classes of the current plan (0: none), cap = the largest C whose two score rows fit the LDS
+ * behind the forward kernel's plan (either pointer may be NULL).
+ *
+ *   V, lens, N   as mm_viterbi_f32
+ *   U            device, element (b, t, c) at U[b*u_stride_b + t*u_stride_n + c*u_stride_c], natural log; strides checked as
+ *                mm_scoredposteriors_f32 checks them (MM_ERR_DIM).  NULL: no scores
+ *   path, score  as mm_viterbi_f32's.  NULL: MM_ERR_INVALID.  path_stride_b < N: MM_ERR_DIM
+ *   classes      device int32, out, element (b, t) at classes[b*classes_stride_b + t]; classes_stride_b < N: MM_ERR_DIM.  NULL: not
+ *                written -- a plan is then required only if U is given
+ * U or classes without a plan: MM_ERR_INVALID.  U with more classes than the cap: MM_ERR_UNSUPPORTED, the message names the cap.
+ * Log and ProbSemiring batches: MM_ERR_UNSUPPORTED.  Argument errors that need no device are reported before the NULL-batch check.
+ * Runs on the item form of every FSM, one workgroup per utterance: mm_classpath_fwd_kernel<NI,lds|global> (mm_viterbiwindow_f32's
+ * step from the FSM's own start; the score row of a transition is C + 1 floats in LDS, double-buffered and fetched one step ahead,
+ * its slot [C] holds 0; the maximiser's class travels with its source through the lane and group reduction; per frame the
+ * back-pointer row and a 16-bit class row leave for the workspace) and mm_classpath_trace_kernel (one lane per utterance follows
+ * the back-pointers from f).  Workspace, grown by the call and NOT covered by mm_batch_workspace_bytes (mm_batch_reserve does not
+ * size it: a first call does): int32 and 16-bit rows (sum_b S1p_b) x (N + 1) each.  Stream contract of the arc entries: launches
+ * on `stream` only, no host synchronisation; capturable in a hipGraph after a first call has put the item forms and the planes on
+ * the device and sized the workspace (a capture before that returns MM_ERR_INVALID); a replay after U was overwritten in place
+ * follows the new scores. */
+int mm_batch_set_path_classes(mm_batch_t batch, const int32_t *cls, const int64_t *offsets, int32_t C);
+int mm_batch_path_class_info(mm_batch_t batch, int32_t *C, int64_t *cap);
+int mm_classpath_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                     const float *U, int64_t u_stride_b, int64_t u_stride_n, int64_t u_stride_c, int32_t *path, int64_t path_stride_b,
+                     int32_t *classes, int64_t classes_stride_b, float *score, void *stream);
 
 /* totalsum(alpha, T, omega, n) / totalcumsum(alpha, T, omega, n) (src/algorithms.jl:8-29;
  * totalweightsum(fsm, n) = totalcumsum, :36), one value per FSM of the batch, in the batch's semiring

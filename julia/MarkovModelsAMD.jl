@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, set_arc_classes!, arc_class_info, arcclassposteriors, score_class_cap, scoredposteriors, cost_class_cap, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, set_arc_classes!, arc_class_info, arcclassposteriors, score_class_cap, scoredposteriors, cost_class_cap, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, set_path_classes!, path_class_info, classpath, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -826,6 +826,61 @@ function viterbiwindow(b::ROCBatch{K}, V::ROCArray{Float32,3}, lens = nothing; s
         pointer(state_out), pointer(mcommit), pointer(ncommit), pointer(path), N, pointer(score), pointer(converged),
         AMDGPU.stream().stream))
     Array(path) .+ Int32(1), Array(score), Array(converged), Array(ncommit), Array(mcommit), state_out
+end
+
+"""
+    set_path_classes!(b::ROCBatch{<:TropicalSemiring}, classes, C = nothing) -> C
+
+The class of every stored entry of `T̂` for `classpath` (mm_batch_set_path_classes in the header): the arguments of
+`set_arc_classes!`, on a tropical batch; at most 65534 classes.  Host work only; calling it again replaces the plan.
+"""
+function set_path_classes!(b::ROCBatch{K}, classes::AbstractVector, C = nothing) where K <: TropicalSemiring
+    shared = !(eltype(classes) <: AbstractVector)
+    parts = shared ? [classes] : classes
+    flat = Int32[]
+    offs = Int64[0]
+    for c in parts
+        append!(flat, Int32.(c))
+        push!(offs, length(flat))
+    end
+    nc = C === nothing ? max(1, Int(maximum(flat; init = Int32(0))) + 1) : Int(C)
+    op = shared ? Ptr{Int64}(C_NULL) : pointer(offs)
+    GC.@preserve flat offs check(ccall((:mm_batch_set_path_classes, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int64}, Int32),
+        b.handle, pointer(flat), op, Int32(nc)))
+    nc
+end
+
+"(C, cap) of the batch's path-class plan (mm_batch_path_class_info): the classes of the plan (0: none), the most classes whose score rows `classpath` takes"
+function path_class_info(b::ROCBatch)
+    c, cap = Ref{Int32}(0), Ref{Int64}(0)
+    check(ccall((:mm_batch_path_class_info, LIB), Cint, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int64}), b.handle, c, cap))
+    (C = Int(c[]), cap = cap[])
+end
+
+"""
+    classpath(b::ROCBatch{<:TropicalSemiring}, V, U = nothing, lens = nothing) -> (paths, classes, scores)
+
+Best paths that report arc classes, under per-frame arc-class scores (mm_classpath_f32 in the header): under the classes of
+`set_path_classes!` the entry taken between frames t and t + 1 adds `U[c, t, u]` to its own weight (`U` a `C × N × B`
+`ROCArray{Float32,3}`, finite or `-Inf`; `nothing`: no scores -- paths and scores are then `bestpath`'s).  States are returned
+1-based (0: no state); `classes[t, u]` is the 0-based class of the entry taken at transition t, -1 for an unclassified entry,
+beyond the length and without a path.
+"""
+function classpath(b::ROCBatch{K}, V::ROCArray{Float32,3}, U = nothing, lens = nothing) where K <: TropicalSemiring
+    P, N, B = size(V)
+    nc = max(1, path_class_info(b).C)
+    U === nothing || size(U) == (nc, N, B) || throw(DimensionMismatch("U must be $nc × $N × $B"))
+    path = ROCArray{Int32}(undef, N, B)
+    classes = ROCArray{Int32}(undef, N, B)
+    score = ROCArray{Float32}(undef, B)
+    lp = lens === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(lens))
+    up = U === nothing ? Ptr{Float32}(C_NULL) : Ptr{Float32}(pointer(U))
+    check(ccall((:mm_classpath_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Float32}, Int64, Int64, Int64, Ptr{Int32}, Int64, Ptr{Int32}, Int64,
+         Ptr{Float32}, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, lp, N, up, nc * N, nc, 1, pointer(path), N, pointer(classes), N, pointer(score),
+        AMDGPU.stream().stream))
+    Array(path) .+ Int32(1), Array(classes), Array(score)
 end
 
 """

@@ -72,6 +72,9 @@ SYMBOLS = [
     "mm_maxstateposteriors_f32",
     "mm_viterbi_f32",
     "mm_viterbiwindow_f32",
+    "mm_batch_set_path_classes",
+    "mm_batch_path_class_info",
+    "mm_classpath_f32",
     "mm_totalsum_f32",
     "mm_set_rccl",
     "mm_allreduce_logz",
@@ -210,6 +213,12 @@ def _load():
         fn.argtypes = [vp, fp, i64, i64, vp, i64, fp, i64, vp]
     lib.mm_viterbi_f32.restype = C.c_int
     lib.mm_viterbi_f32.argtypes = [vp, fp, i64, i64, vp, i64, vp, i64, fp, vp, i64, vp]
+    lib.mm_batch_set_path_classes.restype = C.c_int
+    lib.mm_batch_set_path_classes.argtypes = [vp, vp, vp, i32]
+    lib.mm_batch_path_class_info.restype = C.c_int
+    lib.mm_batch_path_class_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i64)]
+    lib.mm_classpath_f32.restype = C.c_int
+    lib.mm_classpath_f32.argtypes = [vp, fp, i64, i64, vp, i64, fp, i64, i64, i64, vp, i64, vp, i64, fp, vp]
     lib.mm_viterbiwindow_f32.restype = C.c_int
     lib.mm_viterbiwindow_f32.argtypes = [vp, fp, i64, i64, vp, i64, fp, vp, vp, C.c_int, fp, fp, vp, vp, i64, fp, vp, vp]
     lib.mm_totalsum_f32.restype = C.c_int

@@ -453,7 +453,7 @@ static Geometry pick_geometry(mm_batch_t h) {
 }
 
 // ---- one plan per entry that runs on the item form: its launch geometry and where its state vectors live
-enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter, Window, VitWindow, Weighted, Segment, ArcClass, Scored, ClassCost };
+enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter, Window, VitWindow, Weighted, Segment, ArcClass, Scored, ClassCost, ClassPath };
 struct ItemPlan {
     ItemEntry e;
     int NW, NI;        // waves per workgroup, register-resident items per wave of the instance (8 or 0)
@@ -472,6 +472,8 @@ struct ItemPlan {
 // ArcClass: the arc entry's plan (its term rows take what LDS the plan leaves, or the workspace: arcclass_cap).
 // Scored: the arc entry's plan as well; the two score rows come behind it (scored_class_cap), the term rows behind them (scored_term_cap).
 // ClassCost: the cost entry's plan; the two cost rows come behind it (classcost_class_cap).
+// ClassPath (tropical batches): the tropical kernel's geometry, its LDS plan + the two 16-bit class rows; the two score rows come
+// behind them (classpath_class_cap).
 // `global` never depends on max_items, nor does NI except Tropical's (8: the whole graph is register-resident): mm_batch_create
 // asks before the item forms are up, and ensure_item_forms raises max_items later -- only NW follows it.
 static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
@@ -484,6 +486,7 @@ static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
         if (e == ItemEntry::Filter) return mm_filter_lds_bytes(S1p, P1p);
         if (e == ItemEntry::Window || e == ItemEntry::Segment) return mm_window_lds_bytes(S1p, P1p);
         if (e == ItemEntry::VitWindow) return mm_vitwindow_lds_bytes(S1p, P1p);
+        if (e == ItemEntry::ClassPath) return mm_classpath_lds_bytes(S1p, P1p);
         if (e == ItemEntry::Weighted) return mm_weighted_lds_bytes(S1p, P1p);
         return e == ItemEntry::Cost || e == ItemEntry::ClassCost ? mm_cost_lds_bytes(S1p, P1p) : size_t(lds_plan(S1p, P1p, e != ItemEntry::Export).total) * 4;
     };
@@ -499,7 +502,7 @@ static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
         e == ItemEntry::ClassCost)
         pl.NW = std::min(g.NW, 8);
     if (e == ItemEntry::Sample) pl.stage = !pl.global && !h->dbg.sample_nostage && size_t(h->max_S1p) * 8 <= lds_max;
-    if (e == ItemEntry::Tropical || e == ItemEntry::VitWindow) {
+    if (e == ItemEntry::Tropical || e == ItemEntry::VitWindow || e == ItemEntry::ClassPath) {
         // register-resident items when the whole graph fits 8 items per wave -- as many waves as there is work for (latency), at most
         // 8 items each --, else streamed
         pl.NI = g.NI == 8 && h->max_items <= 8 * MM_MAX_WAVES ? 8 : 0;
@@ -550,6 +553,10 @@ static int64_t classcost_class_cap(const ItemPlan &pl) {
     return std::min<int64_t>(row - 1, 65534);
 }
 static size_t classcost_lds_bytes(const ItemPlan &pl, int64_t C) { return pl.lds_bytes + size_t(mm_scored_urow(C)) * 2 * sizeof(float); }
+
+// mm_classpath_f32: the most classes whose two score rows fit the LDS behind the forward kernel's plan -- and a 16-bit class id
+static int64_t classpath_class_cap(const ItemPlan &pl) { return classcost_class_cap(pl); }
+static size_t classpath_lds_bytes(const ItemPlan &pl, int64_t C, bool scored) { return pl.lds_bytes + (scored ? size_t(mm_scored_urow(C)) * 2 * sizeof(float) : 0); }
 
 // item / tropical kernels: `kernel` keeps the state vectors in LDS; `big` is the same kernel with the vectors in global
 // memory, for FSMs beyond the LDS (the reference has no size limit: src/linalg.jl:170-181)
@@ -814,8 +821,9 @@ static int fsm_create_impl(int semiring, int64_t S1, int64_t nnz, int layout, in
         given.val[k] = rd_val(val, val_bytes, k) * scale;
     }
     // (the caller's arrays as given, 0-based: the arc posteriors report in their entry order)
-    const std::vector<int64_t> given_ptr = semiring == MM_LOG ? given.rowptr : std::vector<int64_t>();
-    const std::vector<int32_t> given_idx = semiring == MM_LOG ? given.col : std::vector<int32_t>();
+    const bool entry_order = semiring == MM_LOG || semiring == MM_TROPICAL;  // (tropical: the class planes of mm_batch_set_path_classes)
+    const std::vector<int64_t> given_ptr = entry_order ? given.rowptr : std::vector<int64_t>();
+    const std::vector<int32_t> given_idx = entry_order ? given.col : std::vector<int32_t>();
     sort_rows(given, S1);
     // MM_CSC(T_hat) is CSR(T_hat') = the forward matrix; MM_CSR(T_hat) the backward one
     Csr other = transpose(given, S1);
@@ -898,9 +906,10 @@ static int fsm_create_impl(int semiring, int64_t S1, int64_t nnz, int layout, in
     }
     f->mat[0] = fwd;
     f->mat[1] = bwd;
-    if (semiring == MM_LOG) {
+    {
         // the caller's entry behind every entry of bwd (sort_rows and transpose are stable: a row of bwd lists its arcs by
-        // destination, the arcs of one (source, destination) in the caller's order)
+        // destination, the arcs of one (source, destination) in the caller's order) -- tropical FSMs too: the class planes of
+        // mm_batch_set_path_classes go by the caller's entries
         f->bwd_caller.resize(size_t(nnz));
         if (layout == MM_CSR) {
             std::vector<int64_t> ks;
@@ -918,6 +927,8 @@ static int fsm_create_impl(int semiring, int64_t S1, int64_t nnz, int layout, in
             if (given_idx[size_t(k)] == S1 - 1) f->kphony = k;
         f->init_order.resize(size_t(n_init));
         for (int64_t k = 0; k < n_init; ++k) f->init_order[size_t(k)] = int32_t(rd_index(init_idx, index_bytes, k) - index_base);
+    }
+    if (semiring == MM_LOG) {
         // useful states: forward reachable (over out-arcs = rows of T_hat) and co-reachable (over in-arcs)
         std::vector<char> reach(S1, 0), coreach(S1, 0);
         std::vector<int32_t> stack;
@@ -2783,6 +2794,16 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
             "; class cap " + std::to_string(cap);
         if (h->cls_image.empty()) s += "; no classes set";
         else if (h->cls_C > cap) s += "; " + std::to_string(h->cls_C) + " classes exceed the cap";
+    } else if (entry == 17) {  // mm_classpath_f32
+        if (h->semiring != MM_TROPICAL) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_classpath_f32 runs on tropical batches only");
+        const ItemPlan pl = item_plan(h, ItemEntry::ClassPath);
+        const int64_t cap = classpath_class_cap(pl);
+        s = "mm_classpath_fwd_kernel<" + std::to_string(pl.NI) + "," + where_of(pl.global) +
+            "> (tropical forward: every arc scored by its class's entry of the transition's score row, back-pointer and class rows stored) + "
+            "mm_classpath_trace_kernel (path and classes by one lane per utterance); state vectors " +
+            (pl.global ? "in global memory" : "in LDS") + "; class cap " + std::to_string(cap);
+        if (h->sc_image.empty()) s += "; no classes set";
+        else if (h->cls_C > cap) s += "; " + std::to_string(h->cls_C) + " classes exceed the cap";
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -2853,6 +2874,17 @@ static VitWindowWs vitwindow_ws_layout(mm_batch_t h, int64_t N) {
     W.m = 2 * W.best;
     W.end = W.m + align_up(size_t(h->B) * size_t(N + 2) * 4, 256);
     W.total = W.end + align_up(size_t(h->B) * 4, 256);
+    return W;
+}
+
+// Where mm_classpath_f32 keeps what it keeps in h->ws for N frames (tropical batches): the int32 back-pointer rows and the 16-bit class
+// rows (both (sum_b S1p_b) x (N + 1)) and, for a plan with global vectors, the two class rows of every utterance's current frames
+struct ClassPathWs { size_t bc = 0, cbuf = 0, total = 0; };
+static ClassPathWs classpath_ws_layout(mm_batch_t h, int64_t N, bool global) {
+    ClassPathWs W;
+    W.bc = align_up(size_t(h->total_s1p) * size_t(N + 1) * 4, 256);
+    W.cbuf = W.bc + align_up(size_t(h->total_s1p) * size_t(N + 1) * 2, 256);
+    W.total = W.cbuf + (global ? align_up(size_t(h->B) * 2 * size_t(h->max_S1p) * 2, 256) : 0);
     return W;
 }
 
@@ -3427,10 +3459,23 @@ static ClassPlanHost make_class_plan(mm_fsm_s &f, const int32_t *cls, int32_t C)
     return pl;
 }
 
-int mm_batch_set_arc_classes(mm_batch_t h, const int32_t *cls, const int64_t *offsets, int32_t C) {
-    const std::string who = "mm_batch_set_arc_classes";
-    if (!h || !cls) return fail(MM_ERR_INVALID, who + ": NULL argument");
-    if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, who + ": log-semiring batches only");
+// The class planes of one (FSM, class array) in the blob of a setter: the forward item form's and, with the class plan `pl` of
+// mm_batch_set_arc_classes, the backward form's and the ranks' classes (pl NULL -- mm_batch_set_path_classes --: the forward plane alone,
+// the other offsets 0)
+struct MadePlanes { size_t o_plane[2], o_rcls; };
+static MadePlanes add_class_planes(Blob &sbl, const mm_fsm_s &f, const int32_t *cb, int32_t C, const ClassPlanHost *pl) {
+    MadePlanes mp{{0, 0}, 0};
+    mp.o_plane[0] = sbl.add(make_class_plane(f, 0, cb, C));
+    if (!pl) return mp;
+    std::vector<uint16_t> rcls(pl->recs.size());
+    for (int32_t c = 0; c < C; ++c)
+        for (int32_t r = pl->cptr[size_t(c)]; r < pl->cptr[size_t(c) + 1]; ++r) rcls[size_t(r)] = uint16_t(c);
+    mp.o_plane[1] = sbl.add(make_class_plane(f, 1, cb, C));
+    mp.o_rcls = sbl.add(rcls);
+    return mp;
+}
+// what both setters refuse, after their own semiring check
+static int check_class_args(const std::string &who, mm_batch_t h, const int32_t *cls, const int64_t *offsets, int32_t C) {
     if (C < 1) return fail(MM_ERR_INVALID, who + ": need C >= 1 classes, got " + std::to_string(C));
     const size_t B = size_t(h->B);
     for (size_t b = 0; b < B; ++b) {
@@ -3446,6 +3491,15 @@ int mm_batch_set_arc_classes(mm_batch_t h, const int32_t *cls, const int64_t *of
                 return fail(MM_ERR_INVALID, who + ": class id " + std::to_string(cb[k]) + " of entry " + std::to_string(k) + " of utterance " + std::to_string(b) +
                                                 " is outside [-1, " + std::to_string(C) + ")");
     }
+    return MM_OK;
+}
+
+int mm_batch_set_arc_classes(mm_batch_t h, const int32_t *cls, const int64_t *offsets, int32_t C) {
+    const std::string who = "mm_batch_set_arc_classes";
+    if (!h || !cls) return fail(MM_ERR_INVALID, who + ": NULL argument");
+    if (h->semiring != MM_LOG) return fail(MM_ERR_UNSUPPORTED, who + ": log-semiring batches only");
+    if (const int rc = check_class_args(who, h, cls, offsets, C)) return rc;
+    const size_t B = size_t(h->B);
     return no_throw(who.c_str(), [&]() {
         // one plan per distinct (FSM, class array); the image: [B] descriptors, then per plan its records and class pointers
         struct Made { const mm_fsm_s *f; const int32_t *cls; size_t o_recs, o_cptr; int M, cphony; };
@@ -3455,7 +3509,6 @@ int mm_batch_set_arc_classes(mm_batch_t h, const int32_t *cls, const int64_t *of
         (void)bl.add(descs);  // (at 0; filled in below)
         // the class planes of the scored entry, laid out the same way (none for more classes than a 16-bit id holds)
         const bool planes = C <= 65534;
-        struct MadePlanes { size_t o_plane[2], o_rcls; };
         std::vector<MadePlanes> made_sc;
         std::vector<ScoredDev> sdescs(B);
         Blob sbl;
@@ -3473,16 +3526,7 @@ int mm_batch_set_arc_classes(mm_batch_t h, const int32_t *cls, const int64_t *of
                 const size_t o_recs = bl.add(pl.recs);
                 made.push_back(Made{&f, cb, o_recs, bl.add(pl.cptr), int(pl.recs.size()), pl.cphony});
                 m = &made.back();
-                if (planes) {
-                    std::vector<uint16_t> rcls(pl.recs.size());
-                    for (int32_t c = 0; c < C; ++c)
-                        for (int32_t r = pl.cptr[size_t(c)]; r < pl.cptr[size_t(c) + 1]; ++r) rcls[size_t(r)] = uint16_t(c);
-                    MadePlanes mp;
-                    mp.o_plane[0] = sbl.add(make_class_plane(f, 0, cb, C));
-                    mp.o_plane[1] = sbl.add(make_class_plane(f, 1, cb, C));
-                    mp.o_rcls = sbl.add(rcls);
-                    made_sc.push_back(mp);
-                }
+                if (planes) made_sc.push_back(add_class_planes(sbl, f, cb, C, &pl));
             }
             if (planes) {
                 const MadePlanes &mp = made_sc[size_t(m - made.data())];
@@ -3924,10 +3968,10 @@ int mm_batch_score_class_cap(mm_batch_t h, int64_t *cap) {
 
 // the class planes on the device: one allocation, one copy -- made by the first call behind mm_batch_set_arc_classes, never during a
 // capture (as ensure_class_plan)
-static int ensure_score_planes(mm_batch_t h, void *stream) {
+static int ensure_score_planes(mm_batch_t h, void *stream, const char *who = "mm_scoredposteriors_f32") {
     if (h->d_sc) return MM_OK;
     if (capturing(stream))
-        return fail(MM_ERR_INVALID, "the class planes of this batch are not on the device yet: run mm_scoredposteriors_f32 once outside a stream capture");
+        return fail(MM_ERR_INVALID, std::string("the class planes of this batch are not on the device yet: run ") + who + " once outside a stream capture");
     void *d = nullptr;
     HIP_TRY(hipMalloc(&d, h->sc_image.size()));
     DevMem own(d);
@@ -3936,11 +3980,11 @@ static int ensure_score_planes(mm_batch_t h, void *stream) {
     auto at = [&](const unsigned short *off) { return reinterpret_cast<const unsigned short *>(static_cast<char *>(d) + reinterpret_cast<size_t>(off)); };
     for (int64_t b = 0; b < h->B; ++b) {
         descs[b].plane[0] = at(descs[b].plane[0]);
-        descs[b].plane[1] = at(descs[b].plane[1]);
+        descs[b].plane[1] = at(descs[b].plane[1]);  // (a plan of mm_batch_set_path_classes has the forward plane alone: nobody reads the others)
         descs[b].rcls = at(descs[b].rcls);
     }
     if (hipMemcpy(d, img.data(), img.size(), hipMemcpyHostToDevice) != hipSuccess)
-        return fail(MM_ERR_HIP, "mm_scoredposteriors_f32: upload of the class planes failed");
+        return fail(MM_ERR_HIP, std::string(who) + ": upload of the class planes failed");
     h->d_sc = std::move(own);
     return MM_OK;
 }
@@ -4483,6 +4527,115 @@ int mm_viterbiwindow_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn,
     wp.ws_m = reinterpret_cast<float *>(ws + W.m);
     wp.ws_end = reinterpret_cast<int *>(ws + W.end);
     return mm_launch_vitwindow(h->B, pl.NW, pl.NI, pl.global, pl.lds_bytes, h->max_S1p, p, wp, static_cast<hipStream_t>(stream));
+}
+
+// ---- best paths with arc classes under per-frame arc-class scores (mm_kernel_classpath.hip)
+// The plan of a tropical batch: the 16-bit class plane of the forward item form of every distinct (FSM, class array), in the
+// batch's sc_image / d_sc / cls_C (mm_batch_set_arc_classes, which fills them for log batches, refuses tropical ones).
+int mm_batch_set_path_classes(mm_batch_t h, const int32_t *cls, const int64_t *offsets, int32_t C) {
+    const std::string who = "mm_batch_set_path_classes";
+    if (!h || !cls) return fail(MM_ERR_INVALID, who + ": NULL argument");
+    if (h->semiring != MM_TROPICAL) return fail(MM_ERR_UNSUPPORTED, who + ": tropical batches only");
+    if (const int rc = check_class_args(who, h, cls, offsets, C)) return rc;
+    if (C > 65534) return fail(MM_ERR_UNSUPPORTED, who + ": " + std::to_string(C) + " classes exceed the 65534 a 16-bit class id holds");
+    const size_t B = size_t(h->B);
+    return no_throw(who.c_str(), [&]() {
+        struct Made { const mm_fsm_s *f; const int32_t *cls; MadePlanes mp; };
+        std::vector<Made> made;
+        std::vector<ScoredDev> sdescs(B);
+        Blob sbl;
+        (void)sbl.add(sdescs);  // (at 0; filled in below)
+        for (size_t b = 0; b < B; ++b) {
+            mm_fsm_s &f = *h->fsms[b];
+            const int32_t *cb = cls + (offsets ? offsets[b] : 0);
+            const Made *m = nullptr;
+            for (const Made &c : made)
+                if (c.f == &f && (c.cls == cb || std::equal(cb, cb + f.nnz, c.cls))) m = &c;
+            if (!m) {
+                ensure_packed(&f);
+                made.push_back(Made{&f, cb, add_class_planes(sbl, f, cb, C, nullptr)});
+                m = &made.back();
+            }
+            ScoredDev &sd = sdescs[b];
+            sd.plane[0] = reinterpret_cast<const unsigned short *>(m->mp.o_plane[0]);
+            sd.plane[1] = reinterpret_cast<const unsigned short *>(m->mp.o_plane[1]);
+            sd.rcls = reinterpret_cast<const unsigned short *>(m->mp.o_rcls);
+        }
+        memcpy(sbl.host.data(), sdescs.data(), sizeof(ScoredDev) * B);
+        h->sc_image = std::move(sbl.host);
+        h->d_sc = DevMem();  // (the next mm_classpath_f32 call uploads the new planes)
+        h->cls_C = C;
+        return int(MM_OK);
+    });
+}
+
+int mm_batch_path_class_info(mm_batch_t h, int32_t *C, int64_t *cap) {
+    if (!h) return fail(MM_ERR_INVALID, "mm_batch_path_class_info: NULL batch");
+    if (h->semiring != MM_TROPICAL) return fail(MM_ERR_UNSUPPORTED, "mm_batch_path_class_info: tropical batches only");
+    if (C) *C = h->sc_image.empty() ? 0 : h->cls_C;
+    if (cap) *cap = classpath_class_cap(item_plan(h, ItemEntry::ClassPath));
+    return MM_OK;
+}
+
+int mm_classpath_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, const float *U, int64_t usb,
+                     int64_t usn, int64_t usc, int32_t *path, int64_t path_stride_b, int32_t *classes, int64_t classes_stride_b, float *score,
+                     void *stream) {
+    const std::string who = "mm_classpath_f32";
+    // what the arguments alone show comes first, then the batch's refusals
+    if (!path || !score) return fail(MM_ERR_INVALID, who + ": path/score is NULL");
+    if (path_stride_b < N) return fail(MM_ERR_DIM, who + ": path_stride_b < N");
+    if (classes && classes_stride_b < N) return fail(MM_ERR_DIM, who + ": classes_stride_b < N");
+    if (h && h->semiring != MM_TROPICAL)
+        return fail(MM_ERR_UNSUPPORTED, who + ": tropical batches only (this batch is " + (h->semiring == MM_LOG ? "log-semiring" : "ProbSemiring") + ")");
+    int rc = check_run(h, who.c_str(), V, N, MM_TROPICAL);
+    if (rc) return rc;
+    const bool planned = !h->sc_image.empty();
+    if ((U || classes) && !planned) return fail(MM_ERR_INVALID, who + ": no classes set (mm_batch_set_path_classes)");
+    if (U)
+        if ((rc = check_strides(who, "u", usb, h->B, usn, N, usc, h->cls_C))) return rc;
+    rc = ensure_item_forms(h, stream);
+    if (rc) return rc;
+    const ItemPlan pl = item_plan(h, ItemEntry::ClassPath);
+    const int64_t cap = classpath_class_cap(pl);
+    if (U && h->cls_C > cap)
+        return fail(MM_ERR_UNSUPPORTED, who + ": " + std::to_string(h->cls_C) + " classes exceed the cap of " + std::to_string(cap) +
+                                            " classes whose score rows fit the LDS beside the kernel's plan (mm_batch_path_class_info)");
+    if (pl.global && !h->ws_big) {  // (mm_batch_create allocates them for the other entries' plans alone, as ensure_weight_forms)
+        if (capturing(stream))
+            return fail(MM_ERR_INVALID, "the global vectors of this batch are not on the device yet: run " + who + " once outside a stream capture");
+        if (hipMalloc(&h->ws_big, size_t(h->B) * 4 * size_t(h->max_S1p) * sizeof(float)) != hipSuccess) {
+            h->ws_big = nullptr;
+            return fail(MM_ERR_HIP, who + ": device allocation failed");
+        }
+    }
+    rc = item_plan_check(h, pl);
+    if (!rc && planned) rc = ensure_score_planes(h, stream, who.c_str());
+    const ClassPathWs W = classpath_ws_layout(h, N, pl.global);
+    if (!rc) rc = ensure_ws(h, std::max(W.total, mm_batch_workspace_bytes(h, N)), stream);
+    if (rc) return rc;
+    RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    bind_big(h, pl, p);
+    p.path = path;
+    p.path_stride_b = path_stride_b;
+    p.score = score;
+    ClassPathParams cp{};
+    cp.sc = planned ? static_cast<const ScoredDev *>(h->d_sc.get()) : nullptr;
+    cp.U = U;
+    cp.usb = usb;
+    cp.usn = usn;
+    cp.usc = usc;
+    cp.C = planned ? h->cls_C : 0;
+    cp.urow = mm_scored_urow(cp.C);
+    cp.classes = classes;
+    cp.csb = classes_stride_b;
+    char *ws = static_cast<char *>(h->ws);
+    cp.ws_bp = reinterpret_cast<int *>(ws);
+    cp.ws_bc = reinterpret_cast<unsigned short *>(ws + W.bc);
+    cp.ws_cbuf = reinterpret_cast<unsigned short *>(ws + W.cbuf);
+    cp.cbuf_stride = 2ll * h->max_S1p;
+    // (a plan without scores and without classes asked for: the plain step)
+    const int mode = U ? 2 : (classes ? 1 : 0);
+    return mm_launch_classpath(h->B, pl.NW, pl.NI, pl.global, mode, classpath_lds_bytes(pl, cp.C, U != nullptr), p, cp, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -434,6 +434,28 @@ int mm_launch_vitwindow(int64_t B, int NW, int NI, bool bigv, size_t lds_bytes, 
 size_t mm_vitwindow_lds_bytes(int S1p, int P1p);
 bool mm_vitwindow_flags_global(int S1p);  // the trace kernel's flags do not fit the LDS: they live in RunParams::ws_big
 
+// ---- best paths with arc classes (mm_classpath_tu.hip: mm_classpath_fwd_kernel, mm_classpath_trace_kernel on the item form; tropical
+// batches)
+struct ClassPathParams {
+    const ScoredDev *sc;  // [B] the class planes of mm_batch_set_path_classes (plane[0] alone); NULL: no plan (mode 0)
+    const float *U;       // as ScoredParams::U; NULL: no scores
+    long long usb, usn, usc;
+    int C;                // classes of the plan (0: none)
+    int urow;             // floats of one score row in LDS: mm_scored_urow(C)
+    int *classes;         // [b * csb + t]; NULL: not asked for
+    long long csb;
+    // workspace, rows laid out like RunParams::ws_alpha (per utterance [N + 1][S1p]); row r >= 1: frame r + 1
+    int *ws_bp;               // the back-pointers
+    unsigned short *ws_bc;    // the class ids of the maximisers (C: none)
+    unsigned short *ws_cbuf;  // bigv: the two class rows of every utterance, [B][cbuf_stride]
+    long long cbuf_stride;
+};
+// mode: 0 no plan, 1 classes, 2 classes and scores.  lds_bytes: mm_classpath_lds_bytes of the geometry (state vectors in LDS, or bigv:
+// in RunParams::ws_big) + the two score rows (mode 2); path and score go where RunParams says
+int mm_launch_classpath(int64_t B, int NW, int NI, bool bigv, int mode, size_t lds_bytes, const RunParams &p, const ClassPathParams &cp,
+                        hipStream_t stream);
+size_t mm_classpath_lds_bytes(int S1p, int P1p);
+
 // ---- posteriors with call-time arc weights (mm_weighted_tu.hip: mm_weights_kernel, mm_log_kernel's forward half on the call's
 // descriptors, mm_weighted_bwd_kernel and mm_weighted_scatter_kernel on the item form)
 struct UttDesc;  // mm_kernels.hip

@@ -147,17 +147,19 @@ __device__ __forceinline__ void for_items_scored(const ItemRegs<NI> &rg, const S
 
 // The score row of transition t one step ahead: EVERY thread loads a raw value from a clamped, always valid address (row
 // 0 <= t <= tmax = len - 1: no row of a frame t >= len is ever read); stage_score_ahead stores it scaled a phase later.  The classes
-// beyond the block's threads are staged from memory.
+// beyond the block's threads are staged from memory.  (factor: log2 e here; 1 for the tropical mm_classpath_fwd_kernel)
 __device__ __forceinline__ float score_load_raw(const float *Ub, long long usn, long long usc, int t, int tmax, int C, int q) {
     const int tt = t < 0 ? 0 : (t > tmax ? tmax : t), cc = q < C ? q : C - 1;
     return Ub[(long long)tt * usn + (long long)cc * usc];
 }
-__device__ __forceinline__ void stage_score(float *dst, const float *Ub, long long usn, long long usc, int t, int C, int from, int NT) {
-    for (int q = from; q < C; q += NT) dst[q] = Ub[(long long)t * usn + (long long)q * usc] * MM_LOG2E;
+__device__ __forceinline__ void stage_score(float *dst, const float *Ub, long long usn, long long usc, int t, int C, int from, int NT,
+                                            float factor = MM_LOG2E) {
+    for (int q = from; q < C; q += NT) dst[q] = Ub[(long long)t * usn + (long long)q * usc] * factor;
 }
-__device__ __forceinline__ void stage_score_ahead(float *dst, float raw, const float *Ub, long long usn, long long usc, int t, int C, int tid, int NT) {
-    if (tid < C) dst[tid] = raw * MM_LOG2E;
-    if (C > NT) stage_score(dst, Ub, usn, usc, t, C, tid + NT, NT);
+__device__ __forceinline__ void stage_score_ahead(float *dst, float raw, const float *Ub, long long usn, long long usc, int t, int C, int tid, int NT,
+                                                  float factor = MM_LOG2E) {
+    if (tid < C) dst[tid] = raw * factor;
+    if (C > NT) stage_score(dst, Ub, usn, usc, t, C, tid + NT, NT, factor);
 }
 
 // where both kernels keep the two score rows: behind the arc kernel's plan and its waves' sums

@@ -103,6 +103,20 @@ def _per_utt(x, name, B, device):
     return t.contiguous()
 
 
+def _class_scores(U, name, shape, device):
+    """the per-frame class scores of an entry: None, or a float32 [B, N, C] tensor on the batch's device"""
+    if U is None:
+        return None
+    torch = _torch()
+    Ut = U if isinstance(U, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(U, dtype=np.float32))
+    Ut = Ut.to(device=device)
+    if Ut.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32")
+    if tuple(Ut.shape) != tuple(shape):
+        raise _lib.DimensionMismatch(-2, f"{name} must be [B={shape[0]}, N={shape[1]}, C={shape[2]}], got {tuple(Ut.shape)}")
+    return Ut
+
+
 def _results(res, as_numpy):
     """The tuple an entry returns: NumPy arrays if V came as NumPy, None members as they are."""
     return tuple(t.cpu().numpy() if t is not None else None for t in res) if as_numpy else res
@@ -482,9 +496,19 @@ class BatchedFSM:
         int array of ``nnz`` ids for a batch of one shared FSM, or a list with one array per utterance; ids in ``[-1, C)``, -1 = not
         counted, in the order of ``FSM.nzval`` (phony final column and self-loop included).  ``C`` defaults to the largest id + 1.
         Host work only; calling it again replaces the plan.  Not during a stream capture.  Returns C."""
+        return self._set_classes(lib.mm_batch_set_arc_classes, "set_arc_classes", classes, C)
+
+    def set_path_classes(self, classes, C=None):
+        """The class of every stored entry of ``T_hat`` for ``classpath`` (mm_batch_set_path_classes): the arguments of
+        ``set_arc_classes``, on a tropical batch; at most 65534 classes.  Host work only; calling it again replaces the plan.  Not
+        during a stream capture.  Returns C."""
+        return self._set_classes(lib.mm_batch_set_path_classes, "set_path_classes", classes, C)
+
+    def _set_classes(self, setter, who, classes, C):
+        """(the two class setters: one array for a shared FSM or one per utterance, flattened with offsets)"""
         torch = _torch()
         if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise _lib.MarkovModelsAMDError(-1, "set_arc_classes: the class plan cannot be replaced during a stream capture")
+            raise _lib.MarkovModelsAMDError(-1, f"{who}: the class plan cannot be replaced during a stream capture")
         shared = not isinstance(classes, (list, tuple))
         arrs = [np.ascontiguousarray(c, dtype=np.int32).ravel() for c in ([classes] if shared else classes)]
         if not shared and len(arrs) != self.B:
@@ -494,12 +518,19 @@ class BatchedFSM:
         if shared:
             if arrs[0].size != self.cfsms[0].fsm.nnz:
                 raise _lib.DimensionMismatch(-2, f"classes has {arrs[0].size} ids, the FSM {self.cfsms[0].fsm.nnz} entries")
-            check(lib.mm_batch_set_arc_classes(self._h, arrs[0].ctypes.data, None, int(C)))
+            check(setter(self._h, arrs[0].ctypes.data, None, int(C)))
         else:
             flat = np.ascontiguousarray(np.concatenate(arrs), dtype=np.int32)
             offs = np.cumsum([0] + [a.size for a in arrs]).astype(np.int64)
-            check(lib.mm_batch_set_arc_classes(self._h, flat.ctypes.data, offs.ctypes.data, int(C)))
+            check(setter(self._h, flat.ctypes.data, offs.ctypes.data, int(C)))
         return int(C)
+
+    def path_class_info(self) -> dict:
+        """``path_C`` = the classes of the plan ``set_path_classes`` gave (0: none), ``path_class_cap`` = the most classes whose
+        score rows ``classpath`` takes (mm_batch_path_class_info).  Tropical batches only."""
+        c, cap = C.c_int32(), C.c_int64()
+        check(lib.mm_batch_path_class_info(self._h, C.byref(c), C.byref(cap)))
+        return dict(path_C=c.value, path_class_cap=cap.value)
 
     def info(self, scored=False, classcost=False) -> dict:
         """What the batch knows about its arc-class plan (mm_batch_arc_class_info): ``arcclass_cap`` = the most classified entries
@@ -549,14 +580,7 @@ class BatchedFSM:
         torch, Vt, lt, as_numpy = self._prep(V, lens)
         B, N, P = Vt.shape
         nc = max(1, self.info()["arcclass_C"])  # (no plan: the library refuses the call)
-        Ut = None
-        if U is not None:
-            Ut = U if isinstance(U, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(U, dtype=np.float32))
-            Ut = Ut.to(device=Vt.device)
-            if Ut.dtype != torch.float32:
-                raise TypeError("U must be float32")
-            if tuple(Ut.shape) != (B, N, nc):
-                raise _lib.DimensionMismatch(-2, f"U must be [B={B}, N={N}, C={nc}], got {tuple(Ut.shape)}")
+        Ut = _class_scores(U, "U", (B, N, nc), Vt.device)
         if out is not None and not want_gamma:
             raise ValueError("out given with want_gamma=False")
         gamma = _out_buffer(out, (B, N, P), Vt.device) if want_gamma else None
@@ -935,11 +959,12 @@ class BatchedFSM:
         """The kernels the engine launches for this batch (informational): "log" = pdfposteriors, "tropical" = bestpath, "export" =
         alpharecursion / betarecursion, "arcs" = arcposteriors, "sample" = samplepaths, "cost" = expectedcost, "leaky" =
         leakyposteriors, "entropy" = pathentropy, "filter" = filterposteriors, "window" = windowposteriors,
-        "vitwindow" = viterbiwindow (tropical batches), "weighted" = weightedposteriors, "segment" = segmentposteriors."""
+        "vitwindow" = viterbiwindow (tropical batches), "weighted" = weightedposteriors, "segment" = segmentposteriors,
+        "classpath" = classpath (tropical batches)."""
         import ctypes
 
         buf = ctypes.create_string_buffer(1024)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13, "arcclass": 14, "scored": 15, "classcost": 16}[semiring], buf, 1024))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13, "arcclass": 14, "scored": 15, "classcost": 16, "classpath": 17}[semiring], buf, 1024))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -991,6 +1016,26 @@ class BatchedFSM:
                                        conv.data_ptr(), self._stream(torch)))
         return _results((path, score, conv, ncommit, mcommit, so), as_numpy)
 
+    def classpath(self, V, U=None, lens=None, want_classes=True):
+        """Best paths that report arc classes, under per-frame arc-class scores (mm_classpath_f32): ``(path[B, N], classes[B, N],
+        score[B])``; ``classes`` is None without ``want_classes``.  Under the classes ``set_path_classes`` gave, the entry taken
+        between frames t and t + 1 (0-based; t = len - 1: the arc into the phony final state) adds ``U[b, t, class]`` to its own
+        weight: ``U`` is ``[B, N, C]`` float32 on the device, finite or -inf (-inf removes the class at that transition; rows
+        t >= len are not read), None: no scores -- ``path`` and ``score`` are then ``viterbi``'s, bit for bit.  An entry of class -1
+        and the phony self-loop are not scored.  ``classes[b, t]`` is the class of the entry the best path takes at transition t
+        (-1: an unclassified entry); among several best arcs into a state the lowest source wins, then the lowest class id, -1
+        last.  ``path`` and ``classes`` are -1 beyond the lengths and where there is no path (``score`` = -inf).  Without a plan
+        only ``U`` None with ``want_classes`` False is accepted.  No atomics: bit-identical from call to call.  Tropical batches
+        only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        Ut = _class_scores(U, "U", (B, N, max(1, self.path_class_info()["path_C"])), Vt.device) if U is not None else None
+        path = torch.empty((B, N), dtype=torch.int32, device=Vt.device)
+        cls = torch.empty((B, N), dtype=torch.int32, device=Vt.device) if want_classes else None
+        score = torch.empty(B, dtype=torch.float32, device=Vt.device)
+        check(lib.mm_classpath_f32(*_head(self._h, Vt, lt, N), _ptr(Ut), *(Ut.stride() if Ut is not None else (0, 0, 0)), path.data_ptr(),
+                                   path.stride(0), _ptr(cls), cls.stride(0) if cls is not None else 0, score.data_ptr(), self._stream(torch)))
+        return _results((path, cls, score), as_numpy)
 
     def totalsum(self, n: int, cumulative: bool = False):
         """Per FSM of the batch: omega . v_n (totalsum) or the semiring sum over k <= n of omega . v_k
@@ -1440,6 +1485,18 @@ def bestpath(fsm, Vhats, Chats=None):
     V, lens = _need_expanded(Vhats)
     path, score = bf.viterbi(V, lens)
     return [path[b, : lens[b]].copy() for b in range(bf.B)], score
+
+
+def classbestpath(fsm, Vhats, classes, U=None, Chats=None, C=None):
+    """Best paths with the classes of their arcs -- see ``BatchedFSM.set_path_classes`` / ``BatchedFSM.classpath`` -- in
+    ``bestpath``'s call shape: per utterance the 0-based state sequence of the best path and the class of the entry taken at every
+    transition (the label sequence with its times: ``decode.events``), and the paths' weights.  ``classes``: one id array for a
+    batch that repeats one FSM, or a list with one per utterance; ``U`` the scores ``[B, N, C]`` (None: none)."""
+    bf = _as_batch(fsm, Chats)
+    V, lens = _need_expanded(Vhats)
+    bf.set_path_classes(classes, C)
+    path, cls, score = bf.classpath(V, U, lens)
+    return [path[b, : lens[b]].copy() for b in range(bf.B)], [cls[b, : lens[b]].copy() for b in range(bf.B)], score
 
 
 def windowbestpath(fsm, Vhats, Chats=None, closed=None):
