@@ -135,6 +135,9 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * names the class cap and says "exceed the cap" when the current class plan has more classes ("no classes set" without a plan).
  * 17 = mm_classpath_f32 (tropical batches only): mm_classpath_fwd_kernel<NI,lds|global> + mm_classpath_trace_kernel; the text names
  * the class cap and says "exceed the cap" when the plan of mm_batch_set_path_classes has more classes ("no classes set" without one).
+ * 18 = mm_lattice_f32 (tropical batches only): the two recursions' instances (mm_tropical_kernel<NI,lds|global>,
+ * mm_log_kernel<MODE_BETA,NI,lds|global,TROP>), mm_pick_final_kernel, mm_lattice_prune_kernel<lds|global,count>,
+ * mm_lattice_scan_kernel and mm_lattice_prune_kernel<lds|global,write>.
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -832,6 +835,60 @@ int mm_batch_path_class_info(mm_batch_t batch, int32_t *C, int64_t *cap);
 int mm_classpath_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
                      const float *U, int64_t u_stride_b, int64_t u_stride_n, int64_t u_stride_c, int32_t *path, int64_t path_stride_b,
                      int32_t *classes, int64_t classes_stride_b, float *score, void *stream);
+
+/* Beam-pruned best-path lattices (MM_TROPICAL batches): for every utterance and transition, the stored entries of T_hat that lie on
+ * some complete path whose weight is within beam_b of the best path's, with their through-scores -- the pruned hypothesis space that
+ * N-best lists, confidences, rescoring by a second model and lattice-based training read off on the host.  Conventions of
+ * mm_classpath_f32: lhs = C_hat . expand(V_b), frames 1-based in the formulas, transition t 0-based between frames t+1 and t+2
+ * (t = len-1: the arc into the phony final state f), the stored entries k = (i_k -> j_k) in the order mm_arcposteriors_f32 reports
+ * them (parallel entries between two states are entries of their own).
+ *
+ *   alpha_n, beta_n   the tropical recursions mm_alpharecursion_f32 / mm_betarecursion_f32 export (beta_n excludes frame n's emission)
+ *   best    = alpha_{N+1}(f)                                                       (mm_viterbi_f32's score)
+ *   x_t(k)  = (alpha_{t+1}(i_k) + T_hat[k]) + (lhs_{t+2}(j_k) + beta_{t+2}(j_k))   three float32 adds, in this grouping
+ *   s_t(k)  = x_t(k) - best                                                        one float32 subtraction
+ *   keep (t, k)  iff  t < len,  k is not the phony self-loop,  best > -inf,  beam_b >= 0,  x_t(k) > -inf,  s_t(k) >= -beam_b
+ *
+ * The records of all (b, t) are concatenated in row-major (b, t) order, within one (b, t) sorted by ascending k; record r holds
+ * arc[r] = k and score[r] = s_t(k).  The first record of (b, t) is the exclusive prefix sum of `counts` (the entry returns no
+ * offsets: a cumsum of counts gives them).  An utterance without a path (len = 0 included) has all counts 0 and best = -inf; a
+ * negative or NaN beam keeps nothing, +inf keeps every arc with a finite through-score; nothing is NaN.  No atomics: a repeated
+ * call returns the same bits.
+ * Where every sum is exact -- weights, emissions and beams that are multiples of 1/16 of moderate size -- every kept / dropped
+ * decision and every score is exact.  Otherwise s carries the float32 rounding of the sums behind it, about
+ * (N + 3) * 2^-24 * max|alpha|: an arc whose true score lies that close to -beam may fall on either side, and a beam of 0 is then
+ * NOT meaningful (the arcs of the best path itself score a rounding error below or above 0).
+ * Consequences: (a) the arcs mm_classpath_f32 / mm_viterbi_f32 take are kept for any beam >= 0, with score 0, on exact inputs.
+ * (b) beam = 0 on exact inputs keeps exactly the arcs of all tied best paths.  (c) The kept sets are nested in the beam.  (d) For
+ * every state j and frame n = t+2 with mu_n(j) >= -beam, mu being mm_maxstateposteriors_f32's, the maximum of s_t(k) over the kept
+ * arcs into j equals mu_n(j) (exactly on exact inputs).  (e) The result does not depend on cap: with cap < total the first cap
+ * records are those of the full call.
+ *
+ *   V, lens, N   as mm_viterbi_f32
+ *   beam         device float[B], natural log.  NULL: MM_ERR_INVALID
+ *   counts       device int32, out, element (b, t) at counts[b*counts_stride_b + t]: the kept arcs of transition t, 0 for t >= len.
+ *                Always written.  NULL: MM_ERR_INVALID.  counts_stride_b < N: MM_ERR_DIM
+ *   total        device int64[1], out: the sum of counts.  Always written.  NULL: MM_ERR_INVALID
+ *   best         device float[B], out.  NULL: not written
+ *   arc, score   device int32 / float32, out, `cap` records each (cap: a host value).  Records r >= cap are not written and nothing
+ *                at or behind arc[cap] / score[cap] is touched.  arc == NULL with cap == 0 is the count-only call; arc and score
+ *                are both given or both NULL, cap >= 0, and cap == 0 with arc NULL: MM_ERR_INVALID otherwise
+ * Log and ProbSemiring batches: MM_ERR_UNSUPPORTED.  Argument errors that need no device are reported before the NULL-batch check.
+ * Order of a call: the two recursions (mm_tropical_kernel, mm_log_kernel<MODE_BETA, .., TROP>, as mm_maxstateposteriors_f32 runs
+ * them), mm_pick_final_kernel, then mm_lattice_prune_kernel<lds|global, count> (one workgroup of 256 threads per (b, t): the rows
+ * alpha_{t+1} and lhs_{t+2} + beta_{t+2} staged in LDS, or gathered from global memory where 2 S1p floats exceed it; the arc table
+ * -- source, destination and weight planes of every distinct FSM in the caller's entry order -- streamed in 16-byte loads; compaction
+ * in entry order by ballot and mbcnt per wave, a scan of the wave counts, a running base), mm_lattice_scan_kernel (offsets and
+ * total, one workgroup, fixed order) and the same prune kernel in its write mode, skipped for the count-only call.  Both modes
+ * decide by one predicate function.
+ * Workspace, grown by the call and NOT covered by mm_batch_workspace_bytes (mm_batch_reserve does not size it: a first call does):
+ * two float32 rows (sum_b S1_b) x (N + 1), int64 [B*N + 1], float32 [B].  Stream contract of the arc entries: launches on `stream`
+ * only, no host synchronisation; capturable in a hipGraph after a first call has put the item forms and the arc table on the device
+ * (one allocation, one copy) and sized the workspace (a capture before that returns MM_ERR_INVALID); a replay after V and beam were
+ * overwritten in place follows them. */
+int mm_lattice_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                   const float *beam, int32_t *counts, int64_t counts_stride_b, int64_t *total, float *best, int32_t *arc,
+                   float *score, int64_t cap, void *stream);
 
 /* totalsum(alpha, T, omega, n) / totalcumsum(alpha, T, omega, n) (src/algorithms.jl:8-29;
  * totalweightsum(fsm, n) = totalcumsum, :36), one value per FSM of the batch, in the batch's semiring

@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, set_arc_classes!, arc_class_info, arcclassposteriors, score_class_cap, scoredposteriors, cost_class_cap, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, set_path_classes!, path_class_info, classpath, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, set_arc_classes!, arc_class_info, arcclassposteriors, score_class_cap, scoredposteriors, cost_class_cap, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, set_path_classes!, path_class_info, classpath, lattice, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -891,6 +891,41 @@ semiring, (sum of S+1) x (N+1), 0 along a best path.
 """
 maxstateposteriors(b::ROCBatch{K}, V::ROCArray{Float32,3}, lens = nothing) where K <: TropicalSemiring =
     _recursion(:mm_maxstateposteriors_f32, b, V, lens)   # one device call: tropical alpha, beta and the combination
+
+"""
+    lattice(b::ROCBatch{<:TropicalSemiring}, V, beam, lens = nothing) -> (counts, offsets, arc, score, best)
+
+Beam-pruned best-path lattices (mm_lattice_f32 in the header): for every utterance u and transition t the stored entries of `T̂`
+(1-based here, ascending, in `arcposteriors`' entry order) on a complete path within `beam[u]` of the best path, with their
+through-scores relative to it.  `beam` is a number or a vector of B, natural log.  `counts` is `N × B`; `offsets` (length
+`N·B + 1`, 0-based record numbers) is their exclusive prefix sum in (u, t) order: the records of (u, t) are
+`offsets[(u-1)N + t] + 1 : offsets[(u-1)N + t + 1]`.  Two calls: the count-only one, whose total is read back (one
+synchronisation), then the full one.
+"""
+function lattice(b::ROCBatch{K}, V::ROCArray{Float32,3}, beam, lens = nothing) where K <: TropicalSemiring
+    P, N, B = size(V)
+    bm = ROCArray(beam isa Number ? fill(Float32(beam), B) : Float32.(collect(beam)))
+    length(bm) == B || throw(DimensionMismatch("beam must be a number or a vector of $B"))
+    counts = ROCArray{Int32}(undef, N, B)
+    total = ROCArray{Int64}(undef, 1)
+    best = ROCArray{Float32}(undef, B)
+    lp = lens === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(lens))
+    check(ccall((:mm_lattice_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Float32}, Ptr{Int32}, Int64, Ptr{Int64}, Ptr{Float32}, Ptr{Int32},
+         Ptr{Float32}, Int64, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, lp, N, pointer(bm), pointer(counts), N, pointer(total), pointer(best), Ptr{Int32}(C_NULL),
+        Ptr{Float32}(C_NULL), 0, AMDGPU.stream().stream))
+    n = Array(total)[1]
+    arc = ROCArray{Int32}(undef, n)
+    score = ROCArray{Float32}(undef, n)
+    check(ccall((:mm_lattice_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Float32}, Ptr{Int32}, Int64, Ptr{Int64}, Ptr{Float32}, Ptr{Int32},
+         Ptr{Float32}, Int64, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, lp, N, pointer(bm), pointer(counts), N, pointer(total), pointer(best), pointer(arc),
+        pointer(score), n, AMDGPU.stream().stream))
+    c = Array(counts)
+    c, vcat(Int64(0), cumsum(Int64.(vec(c)))), Array(arc) .+ Int32(1), Array(score), Array(best)
+end
 
 """
     totalsum(b::ROCBatch, n) / totalcumsum(b::ROCBatch, n) -> Vector{Float32}

@@ -2,7 +2,7 @@
 
 Host-side mirror of the reference's hot-path interface (src/MarkovModels.jl:14-45:
 FSM, nstates, rawunion, CompiledFSM, batch, compile, expand, alpha-recursion,
-beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, chunkedposteriors, windowbestpath, classbestpath, arcposteriors, arcclassposteriors, scoredposteriors, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
+beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, chunkedposteriors, windowbestpath, classbestpath, lattice, arcposteriors, arcclassposteriors, scoredposteriors, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
 The directory name contains a dot, so load it with
 ``__graft_entry__.load_package()`` (importlib) rather than a plain import.
 """
@@ -11,6 +11,7 @@ from .fsm import FSM, GeneralStateMap, StateMap, arc_classes_by_destination, bou
 from .inference import (  # noqa: F401
     BatchedFSM,
     CompiledFSM,
+    Lattice,
     alpharecursion,
     arcclassposteriors,
     arcposteriors,
@@ -26,6 +27,7 @@ from .inference import (  # noqa: F401
     expand,
     expectedcost,
     filterposteriors,
+    lattice,
     leakyposteriors,
     maxstateposteriors,
     pathentropy,
@@ -55,6 +57,6 @@ from .longform import chunked_loglik  # noqa: F401
 from . import transitions  # noqa: F401
 from .transitions import constraint_scores, transition_loglik  # noqa: F401
 from . import decode  # noqa: F401
-from .decode import events, forced_alignment, segments  # noqa: F401
+from .decode import events, forced_alignment, lattice_arcs, lattice_fsm, segments  # noqa: F401
 from . import streaming  # noqa: F401
 from .streaming import FixedLagSmoother, ForwardFilter, OnlineViterbi  # noqa: F401

@@ -367,6 +367,9 @@ struct mm_batch_s {
     // more classes than a 16-bit id holds), on the device from the first scored call behind it
     std::vector<char> sc_image;
     DevMem d_sc;
+    // lattices (mm_lattice_f32, tropical batches): the utterances' LatticeDev descriptors in front of the three arc planes of every
+    // distinct FSM, on the device from the first call
+    DevMem d_lat;
     int cls_C = 0;
     int64_t cls_max_M = 0, cls_terms = 0;
     // the lanes a class's sum runs on (ClassDev::lgl, a bit per value), over the utterances of the plan: what kernels() names
@@ -453,7 +456,7 @@ static Geometry pick_geometry(mm_batch_t h) {
 }
 
 // ---- one plan per entry that runs on the item form: its launch geometry and where its state vectors live
-enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter, Window, VitWindow, Weighted, Segment, ArcClass, Scored, ClassCost, ClassPath };
+enum class ItemEntry { Fb, Export, Tropical, Arcs, Sample, Cost, Leaky, Entropy, Filter, Window, VitWindow, Weighted, Segment, ArcClass, Scored, ClassCost, ClassPath, Lattice };
 struct ItemPlan {
     ItemEntry e;
     int NW, NI;        // waves per workgroup, register-resident items per wave of the instance (8 or 0)
@@ -474,6 +477,8 @@ struct ItemPlan {
 // ClassCost: the cost entry's plan; the two cost rows come behind it (classcost_class_cap).
 // ClassPath (tropical batches): the tropical kernel's geometry, its LDS plan + the two 16-bit class rows; the two score rows come
 // behind them (classpath_class_cap).
+// Lattice (tropical batches): the tropical kernel's plan as it stands -- the forward recursion of mm_lattice_f32 is launch_tropical's; the
+// prune kernel has a placement of its own (lattice_global).
 // `global` never depends on max_items, nor does NI except Tropical's (8: the whole graph is register-resident): mm_batch_create
 // asks before the item forms are up, and ensure_item_forms raises max_items later -- only NW follows it.
 static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
@@ -502,7 +507,7 @@ static ItemPlan item_plan(mm_batch_t h, ItemEntry e) {
         e == ItemEntry::ClassCost)
         pl.NW = std::min(g.NW, 8);
     if (e == ItemEntry::Sample) pl.stage = !pl.global && !h->dbg.sample_nostage && size_t(h->max_S1p) * 8 <= lds_max;
-    if (e == ItemEntry::Tropical || e == ItemEntry::VitWindow || e == ItemEntry::ClassPath) {
+    if (e == ItemEntry::Tropical || e == ItemEntry::VitWindow || e == ItemEntry::ClassPath || e == ItemEntry::Lattice) {
         // register-resident items when the whole graph fits 8 items per wave -- as many waves as there is work for (latency), at most
         // 8 items each --, else streamed
         pl.NI = g.NI == 8 && h->max_items <= 8 * MM_MAX_WAVES ? 8 : 0;
@@ -557,6 +562,9 @@ static size_t classcost_lds_bytes(const ItemPlan &pl, int64_t C) { return pl.lds
 // mm_classpath_f32: the most classes whose two score rows fit the LDS behind the forward kernel's plan -- and a 16-bit class id
 static int64_t classpath_class_cap(const ItemPlan &pl) { return classcost_class_cap(pl); }
 static size_t classpath_lds_bytes(const ItemPlan &pl, int64_t C, bool scored) { return pl.lds_bytes + (scored ? size_t(mm_scored_urow(C)) * 2 * sizeof(float) : 0); }
+
+// mm_lattice_f32: the prune kernel gathers the two rows of a cell from global memory when they do not fit the LDS, or under MM_BIGV
+static bool lattice_global(mm_batch_t h) { return h->dbg.bigv || mm_lattice_lds_bytes(h->max_S1p) > MM_LDS_MAX; }
 
 // item / tropical kernels: `kernel` keeps the state vectors in LDS; `big` is the same kernel with the vectors in global
 // memory, for FSMs beyond the LDS (the reference has no size limit: src/linalg.jl:170-181)
@@ -2804,6 +2812,14 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
             (pl.global ? "in global memory" : "in LDS") + "; class cap " + std::to_string(cap);
         if (h->sc_image.empty()) s += "; no classes set";
         else if (h->cls_C > cap) s += "; " + std::to_string(h->cls_C) + " classes exceed the cap";
+    } else if (entry == 18) {  // mm_lattice_f32
+        if (h->semiring != MM_TROPICAL) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_lattice_f32 runs on tropical batches only");
+        const ItemPlan pl = item_plan(h, ItemEntry::Lattice);
+        const std::string where = where_of(lattice_global(h));
+        s = "mm_tropical_kernel<" + std::to_string(pl.NI) + "," + where_of(pl.global) + "> (alpha) + " + item_export_kernel(h, "MODE_BETA", true) +
+            " (beta) + mm_pick_final_kernel + mm_lattice_prune_kernel<" + where + ",count> (one workgroup per utterance and transition: the through-score of "
+            "every stored arc against the beam) + mm_lattice_scan_kernel (offsets and total) + mm_lattice_prune_kernel<" + where +
+            ",write> (the kept arcs in entry order); the two rows of a transition " + (lattice_global(h) ? "gathered from global memory" : "in LDS");
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -4636,6 +4652,126 @@ int mm_classpath_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, con
     // (a plan without scores and without classes asked for: the plain step)
     const int mode = U ? 2 : (classes ? 1 : 0);
     return mm_launch_classpath(h->B, pl.NW, pl.NI, pl.global, mode, classpath_lds_bytes(pl, cp.C, U != nullptr), p, cp, static_cast<hipStream_t>(stream));
+}
+
+// ---- beam-pruned best-path lattices (mm_kernel_lattice.hip)
+// The arc table of a tropical batch: the entries of every distinct FSM in the caller's order as three planes -- source (the phony
+// self-loop: -1), destination, weight --, from T_hat by source (mat[1]) and the caller's entry behind each of its entries
+// (bwd_caller); the utterances' LatticeDev descriptors in front.  One allocation, one copy, made by the first call -- never during a
+// capture (as ensure_score_planes).
+static int ensure_lattice_arcs(mm_batch_t h, void *stream) {
+    if (h->d_lat) return MM_OK;
+    if (capturing(stream))
+        return fail(MM_ERR_INVALID, "the arc table of this batch is not on the device yet: run mm_lattice_f32 once outside a stream capture");
+    return no_throw("mm_lattice_f32", [&]() {
+        const size_t B = size_t(h->B);
+        struct Made { const mm_fsm_s *f; size_t o_src, o_dst, o_w; };
+        std::vector<Made> made;
+        std::vector<LatticeDev> descs(B);
+        Blob bl;
+        (void)bl.add(descs);  // (at 0; filled in below)
+        for (size_t b = 0; b < B; ++b) {
+            const mm_fsm_s &f = *h->fsms[b];
+            if (f.nnz > int64_t(INT32_MAX) - 4096) return fail(MM_ERR_UNSUPPORTED, "mm_lattice_f32: more stored entries than a 32-bit entry index holds");
+            const Made *m = nullptr;
+            for (const Made &c : made)
+                if (c.f == &f) m = &c;
+            if (!m) {
+                std::vector<int32_t> src(size_t(f.nnz)), dst(size_t(f.nnz));
+                std::vector<float> w(size_t(f.nnz));
+                const Csr &bwd = f.mat[1];
+                for (int64_t i = 0; i < f.S1; ++i)
+                    for (int64_t a = bwd.rowptr[size_t(i)]; a < bwd.rowptr[size_t(i) + 1]; ++a) {
+                        const size_t k = size_t(f.bwd_caller[size_t(a)]);
+                        const int32_t j = bwd.col[size_t(a)];
+                        src[k] = (i == f.S1 - 1 && j == f.S1 - 1) ? -1 : int32_t(i);
+                        dst[k] = j;
+                        w[k] = bwd.val[size_t(a)];
+                    }
+                const size_t o_src = bl.add(src), o_dst = bl.add(dst);
+                made.push_back(Made{&f, o_src, o_dst, bl.add(w)});
+                m = &made.back();
+            }
+            descs[b] = LatticeDev{reinterpret_cast<const int *>(m->o_src), reinterpret_cast<const int *>(m->o_dst), reinterpret_cast<const float *>(m->o_w), int(f.nnz), 0};
+        }
+        void *d = nullptr;
+        HIP_TRY(hipMalloc(&d, bl.host.size()));
+        DevMem own(d);
+        for (LatticeDev &ld : descs) {  // (offsets into the image until here)
+            ld.src = reinterpret_cast<const int *>(static_cast<char *>(d) + reinterpret_cast<size_t>(ld.src));
+            ld.dst = reinterpret_cast<const int *>(static_cast<char *>(d) + reinterpret_cast<size_t>(ld.dst));
+            ld.w = reinterpret_cast<const float *>(static_cast<char *>(d) + reinterpret_cast<size_t>(ld.w));
+        }
+        memcpy(bl.host.data(), descs.data(), sizeof(LatticeDev) * B);
+        if (hipMemcpy(d, bl.host.data(), bl.host.size(), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(MM_ERR_HIP, "mm_lattice_f32: upload of the arc table failed");
+        h->d_lat = std::move(own);
+        return int(MM_OK);
+    });
+}
+
+// Where mm_lattice_f32 keeps what it keeps in h->ws for N frames: the tropical alpha and beta rows ((sum_b S1_b) x (N + 1) floats
+// each, the export layout), the int64 offsets [B * N + 1] and best [B]
+struct LatticeWs { size_t beta = 0, offs = 0, best = 0, total = 0; };
+static LatticeWs lattice_ws_layout(mm_batch_t h, int64_t N) {
+    LatticeWs W;
+    W.beta = align_up(size_t(h->total_states) * size_t(N + 1) * 4, 256);
+    W.offs = 2 * W.beta;
+    W.best = W.offs + align_up((size_t(h->B) * size_t(N) + 1) * 8, 256);
+    W.total = W.best + align_up(size_t(h->B) * 4, 256);
+    return W;
+}
+
+int mm_lattice_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, const float *beam, int32_t *counts,
+                   int64_t counts_stride_b, int64_t *total, float *best, int32_t *arc, float *score, int64_t cap, void *stream) {
+    const std::string who = "mm_lattice_f32";
+    // what the arguments alone show comes first, then the batch's refusals
+    if (!beam || !counts || !total) return fail(MM_ERR_INVALID, who + ": beam/counts/total is NULL");
+    if (counts_stride_b < N) return fail(MM_ERR_DIM, who + ": counts_stride_b < N");
+    if ((arc == nullptr) != (score == nullptr)) return fail(MM_ERR_INVALID, who + ": arc and score are both given or both NULL");
+    if (cap < 0 || (!arc && cap != 0)) return fail(MM_ERR_INVALID, who + ": cap must be >= 0, and 0 with arc NULL (the count-only call)");
+    if (h && h->semiring != MM_TROPICAL)
+        return fail(MM_ERR_UNSUPPORTED, who + ": tropical batches only (this batch is " + (h->semiring == MM_LOG ? "log-semiring" : "ProbSemiring") + ")");
+    int rc = check_run(h, who.c_str(), V, N, MM_TROPICAL);
+    if (rc) return rc;
+    if (h->B * N > int64_t(INT32_MAX)) return fail(MM_ERR_UNSUPPORTED, who + ": B * N exceeds 2^31 - 1 workgroups");
+    rc = ensure_item_forms(h, stream);
+    if (!rc) rc = ensure_lattice_arcs(h, stream);
+    const LatticeWs W = lattice_ws_layout(h, N);
+    if (!rc) rc = ensure_ws(h, std::max(W.total, mm_batch_workspace_bytes(h, N)), stream);
+    if (rc) return rc;
+    char *const ws = static_cast<char *>(h->ws);
+    float *const alpha = reinterpret_cast<float *>(ws), *const beta = reinterpret_cast<float *>(ws + W.beta);
+    float *const bestw = reinterpret_cast<float *>(ws + W.best);
+    // the two recursions as mm_maxstateposteriors_f32 runs them, then best = alpha_{N+1}(f)
+    rc = run_export(h, MODE_ALPHA, V, vsb, vsn, lens, N, alpha, h->total_states, stream);
+    if (rc) return rc;
+    rc = run_export(h, MODE_BETA, V, vsb, vsn, lens, N, beta, h->total_states, stream);
+    if (rc) return rc;
+    const int bt = 64;
+    hipLaunchKernelGGL(mm_pick_final_kernel, dim3(unsigned((h->B + bt - 1) / bt)), dim3(bt), 0, static_cast<hipStream_t>(stream), h->d_utts, int(h->B),
+                       alpha, (long long)h->total_states, int(N), bestw);
+    HIP_TRY(hipGetLastError());
+    if (best) {
+        hipLaunchKernelGGL(mm_pick_final_kernel, dim3(unsigned((h->B + bt - 1) / bt)), dim3(bt), 0, static_cast<hipStream_t>(stream), h->d_utts,
+                           int(h->B), alpha, (long long)h->total_states, int(N), best);
+        HIP_TRY(hipGetLastError());
+    }
+    const RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    LatticeParams lp{};
+    lp.arcs = static_cast<const LatticeDev *>(h->d_lat.get());
+    lp.alpha = alpha;
+    lp.beta = beta;
+    lp.row_stride = h->total_states;
+    lp.beam = beam;
+    lp.best = bestw;
+    lp.counts = counts;
+    lp.csb = counts_stride_b;
+    lp.offs = reinterpret_cast<long long *>(ws + W.offs);
+    lp.arc = arc;
+    lp.score = score;
+    lp.cap = cap;
+    return mm_launch_lattice(h->B, lattice_global(h), h->max_S1p, p, lp, reinterpret_cast<long long *>(total), static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

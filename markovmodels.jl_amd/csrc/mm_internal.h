@@ -456,6 +456,32 @@ int mm_launch_classpath(int64_t B, int NW, int NI, bool bigv, int mode, size_t l
                         hipStream_t stream);
 size_t mm_classpath_lds_bytes(int S1p, int P1p);
 
+// ---- beam-pruned best-path lattices (mm_lattice_tu.hip: mm_lattice_prune_kernel in its count and its write mode, mm_lattice_scan_kernel
+// between them; tropical batches)
+struct LatticeDev {  // one utterance's arc table (mm_engine.hip ensure_lattice_arcs): the entries of T_hat in the caller's order
+    const int *src;    // [nnz] source state; -1: the phony self-loop
+    const int *dst;    // [nnz] destination state
+    const float *w;    // [nnz] weight, natural log
+    int nnz, pad;
+};
+struct LatticeParams {
+    const LatticeDev *arcs;    // [B]
+    const float *alpha, *beta; // the exported tropical recursions, row n (frame n + 1) at n * row_stride, an utterance at UttDesc::state_off
+    long long row_stride;
+    const float *beam;         // [B]
+    const float *best;         // [B] alpha_{N+1}(f)
+    int *counts;               // [b * csb + t]
+    long long csb;
+    long long *offs;           // [B * N + 1] the exclusive scan of the counts
+    int *arc;                  // NULL: the count-only call
+    float *score;
+    long long cap;
+};
+// count pass, scan (offs and *total), write pass (skipped when lp.arc is NULL).  global: the two rows of a cell are gathered from
+// global memory, else staged in mm_lattice_lds_bytes(max_S1p) of LDS
+int mm_launch_lattice(int64_t B, bool global, int max_S1p, const RunParams &p, const LatticeParams &lp, long long *total, hipStream_t stream);
+size_t mm_lattice_lds_bytes(int S1p);
+
 // ---- posteriors with call-time arc weights (mm_weighted_tu.hip: mm_weights_kernel, mm_log_kernel's forward half on the call's
 // descriptors, mm_weighted_bwd_kernel and mm_weighted_scatter_kernel on the item form)
 struct UttDesc;  // mm_kernels.hip

@@ -5,11 +5,15 @@ labels with their times (``events``), the runs between boundary arcs (``segments
 A class track is ``classes[B, N]``: ``classes[b, t]`` is the class of the entry the best path of utterance b takes between frames t
 and t + 1 (0-based; t = len - 1: the arc into the phony final state), -1 for an unclassified entry, beyond the length and where
 there is no path.
+
+And from the ``Lattice`` of ``BatchedFSM.lattice`` (mm_lattice_f32): one utterance's kept arcs as host arrays (``lattice_arcs``) and
+as an acyclic tropical FSM that goes back into ``compile`` / ``batch`` for rescoring (``lattice_fsm``).
 """
 from __future__ import annotations
 
 import numpy as np
 
+from .fsm import FSM, _entry_ends
 from .transitions import constraint_scores
 
 
@@ -63,3 +67,45 @@ def forced_alignment(bf, V, marks, lens=None):
             allowed[b, int(t), :] = False
             allowed[b, int(t), int(c)] = keep  # (two different marks at one transition: nothing is allowed)
     return bf.classpath(V, constraint_scores(allowed), lens)
+
+
+def lattice_arcs(bf, lat, b):
+    """One utterance of a ``Lattice`` (``BatchedFSM.lattice``) on the host: the arrays ``(t, arc, src, dst, score)`` of its records in
+    their order -- the transition (0-based; the last one holds the arcs into the phony final state), the stored entry k of the
+    utterance's FSM (the order of ``FSM.nzval``), its source and destination state, and its through-score relative to the best path."""
+    counts, offsets, arc, score = _host(lat.counts), _host(lat.offsets), _host(lat.arc), _host(lat.score)
+    N = counts.shape[1]
+    lo, hi = int(offsets[b * N]), int(offsets[(b + 1) * N])
+    if hi > arc.shape[0]:
+        raise ValueError(f"lattice_arcs: utterance {b} ends at record {hi}, the lattice holds {arc.shape[0]} (max_arcs cut it)")
+    k = arc[lo:hi].astype(np.int64)
+    src, dst = _entry_ends(bf.cfsms[b].fsm)
+    return np.repeat(np.arange(N, dtype=np.int64), counts[b]), k, src[k], dst[k], score[lo:hi].copy()
+
+
+def lattice_fsm(bf, lat, b):
+    """One utterance of a ``Lattice`` as a graph: ``(fsm, state2pdf)``, a tropical ``FSM`` whose states are the (frame, state) pairs
+    the kept arcs touch, in (frame, state) order and labelled so -- acyclic, a state of frame n is only ever visited at frame n, so
+    with ``state2pdf`` (the original state's pdf) it reads the SAME ``V`` and goes straight back into ``compile`` / ``batch``:
+    ``bestpath`` on it returns the original best score, and a second model's ``V`` rescores the pruned space.  The initial weights
+    are the alpha_hat of the sources of transition 0, the final weights the weights of the arcs into the phony final state, every
+    other kept arc keeps its weight (parallel entries merge into their maximum).  An utterance without a path has no lattice:
+    ValueError."""
+    t, k, src, dst, _ = lattice_arcs(bf, lat, b)
+    if k.size == 0:
+        raise ValueError(f"lattice_fsm: utterance {b} has no arc within the beam")
+    cf = bf.cfsms[b]
+    f, S1 = cf.fsm, cf.S1
+    w = np.asarray(f.nzval, dtype=np.float32)[k]
+    last = t == t.max()  # (the arcs into the phony final state)
+    keys = np.unique(np.concatenate([t * S1 + src, (t[~last] + 1) * S1 + dst[~last]]))
+    node = lambda frame, state: np.searchsorted(keys, frame * S1 + state)
+    a_hat = dict(zip((int(s) for s in f.alpha_idx), (float(v) for v in f.alpha_val)))
+    first = np.unique(src[t == 0])
+    initws = [(int(node(0, s)), a_hat[int(s)]) for s in first]
+    a, c = node(t[~last], src[~last]), node(t[~last] + 1, dst[~last])
+    arcs = [((int(x), int(y)), float(v)) for x, y, v in zip(a, c, w[~last])]
+    finalws = [(int(x), float(v)) for x, v in zip(node(t[last], src[last]), w[last])]
+    labels = [(int(q // S1), int(q % S1)) for q in keys]
+    s2p = np.asarray(cf.C_hat.state2pdf, dtype=np.int64)[keys % S1]
+    return FSM(initws, arcs, finalws, labels, semiring="tropical", dtype=np.float32), s2p

@@ -17,7 +17,7 @@ from __future__ import annotations
 
 import ctypes as C
 from collections import OrderedDict  # noqa: F401
-from typing import List, Optional, Sequence, Union
+from typing import List, NamedTuple, Optional, Sequence, Union
 
 import numpy as np
 
@@ -115,6 +115,48 @@ def _class_scores(U, name, shape, device):
     if tuple(Ut.shape) != tuple(shape):
         raise _lib.DimensionMismatch(-2, f"{name} must be [B={shape[0]}, N={shape[1]}, C={shape[2]}], got {tuple(Ut.shape)}")
     return Ut
+
+
+def _beam_vector(beam, B, device):
+    """The ``beam`` of a lattice call as a contiguous float32 [B] tensor on V's device: a number (every utterance's beam) or a [B]
+    tensor / array."""
+    import torch
+
+    if isinstance(beam, torch.Tensor):
+        t = beam.to(device=device, dtype=torch.float32)
+    elif np.ndim(beam) == 0:
+        return torch.full((B,), float(beam), dtype=torch.float32, device=device)
+    else:
+        t = torch.as_tensor(np.asarray(beam, dtype=np.float32)).to(device)
+    if t.dim() == 0:
+        return t.expand(B).contiguous()
+    if t.dim() != 1 or t.numel() != B:
+        raise _lib.DimensionMismatch(-2, f"beam must be a number or a [{B}] vector, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _record_cap(max_arcs):
+    """``max_arcs`` of a lattice call: None, or a record count >= 0."""
+    if max_arcs is None:
+        return None
+    cap = int(max_arcs)
+    if cap < 0:
+        raise ValueError(f"max_arcs must be >= 0, got {max_arcs}")
+    return cap
+
+
+class Lattice(NamedTuple):
+    """What ``BatchedFSM.lattice`` returns.  ``counts[B, N]`` int32: the kept arcs of every transition; ``offsets[B * N + 1]`` int64:
+    their exclusive prefix sum in row-major (b, t) order -- the records of (b, t) are ``offsets[b * N + t] : offsets[b * N + t + 1]``,
+    ``offsets[-1]`` the total; ``arc`` int32 / ``score`` float32: per record the stored entry k of the utterance's FSM (ascending
+    within a transition) and its through-score relative to the best path (<= 0 up to rounding); ``best[B]``: the best path's
+    weight."""
+
+    counts: object
+    offsets: object
+    arc: object
+    score: object
+    best: object
 
 
 def _results(res, as_numpy):
@@ -960,11 +1002,11 @@ class BatchedFSM:
         alpharecursion / betarecursion, "arcs" = arcposteriors, "sample" = samplepaths, "cost" = expectedcost, "leaky" =
         leakyposteriors, "entropy" = pathentropy, "filter" = filterposteriors, "window" = windowposteriors,
         "vitwindow" = viterbiwindow (tropical batches), "weighted" = weightedposteriors, "segment" = segmentposteriors,
-        "classpath" = classpath (tropical batches)."""
+        "classpath" = classpath (tropical batches), "lattice" = lattice (tropical batches)."""
         import ctypes
 
         buf = ctypes.create_string_buffer(1024)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13, "arcclass": 14, "scored": 15, "classcost": 16, "classpath": 17}[semiring], buf, 1024))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13, "arcclass": 14, "scored": 15, "classcost": 16, "classpath": 17, "lattice": 18}[semiring], buf, 1024))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -1036,6 +1078,47 @@ class BatchedFSM:
         check(lib.mm_classpath_f32(*_head(self._h, Vt, lt, N), _ptr(Ut), *(Ut.stride() if Ut is not None else (0, 0, 0)), path.data_ptr(),
                                    path.stride(0), _ptr(cls), cls.stride(0) if cls is not None else 0, score.data_ptr(), self._stream(torch)))
         return _results((path, cls, score), as_numpy)
+
+    def lattice(self, V, beam, lens=None, max_arcs=None):
+        """Beam-pruned best-path lattices (mm_lattice_f32): a ``Lattice`` of ``counts[B, N]``, ``offsets[B * N + 1]``, ``arc``,
+        ``score`` and ``best[B]``.  For every utterance b and transition t (0-based, between frames t and t + 1; t = len - 1: the arc
+        into the phony final state) it lists the stored entries k of the FSM -- in ``arcposteriors``' entry order, ascending -- that lie
+        on a complete path weighing at least ``best[b] - beam[b]``, each with its through-score minus ``best[b]``.  ``beam`` is a
+        number or a ``[B]`` tensor, natural log; negative or NaN keeps nothing, inf keeps every arc on any complete path.  On
+        unrounded inputs the scores carry float32 rounding of about ``(N + 3) * 2**-24 * max|alpha|``: a beam of 0 is not meaningful
+        there.  ``max_arcs`` None: the method makes the count-only call, READS THE TOTAL BACK (one host synchronisation), allocates
+        exactly, and calls again.  ``max_arcs`` given: one call into buffers of that many records and no synchronisation until the
+        total is compared -- ``MarkovModelsAMDError`` if it exceeds ``max_arcs``; inside a stream capture the comparison is left out
+        (records beyond ``max_arcs`` are never written; compare ``offsets[-1]`` after the replay), which makes this the capturable
+        form.  ``decode.lattice_arcs`` / ``decode.lattice_fsm`` read one utterance off the result.  No atomics: bit-identical from
+        call to call.  Tropical batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        dev = Vt.device
+        bt = _beam_vector(beam, B, dev)
+        cap = _record_cap(max_arcs)
+        counts = torch.empty((B, N), dtype=torch.int32, device=dev)
+        total = torch.empty(1, dtype=torch.int64, device=dev)
+        best = torch.empty(B, dtype=torch.float32, device=dev)
+
+        def call(arc, score, n):
+            check(lib.mm_lattice_f32(*_head(self._h, Vt, lt, N), bt.data_ptr(), counts.data_ptr(), counts.stride(0), total.data_ptr(),
+                                     best.data_ptr(), _ptr(arc), _ptr(score), n, self._stream(torch)))
+
+        capturing = torch.cuda.is_current_stream_capturing()
+        if cap is None:
+            call(None, None, 0)
+            cap = int(total.item())
+        arc = torch.empty(cap, dtype=torch.int32, device=dev)
+        score = torch.empty(cap, dtype=torch.float32, device=dev)
+        call(arc, score, cap)
+        if max_arcs is not None and not capturing:
+            n = int(total.item())
+            if n > cap:
+                raise _lib.MarkovModelsAMDError(-1, f"lattice: {n} arcs are within the beam, max_arcs is {cap}")
+            arc, score = arc[:n], score[:n]
+        offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counts.reshape(-1), 0, dtype=torch.int64)])
+        return Lattice(*_results((counts, offsets, arc, score, best), as_numpy))
 
     def totalsum(self, n: int, cumulative: bool = False):
         """Per FSM of the batch: omega . v_n (totalsum) or the semiring sum over k <= n of omega . v_k
@@ -1520,6 +1603,16 @@ def maxstateposteriors(fsm, Vhats, Chats=None):
         raise TypeError("maxstateposteriors needs TropicalSemiring FSMs")
     V, lens = _need_expanded(Vhats)
     return bf.maxstateposteriors(V, lens)
+
+
+def lattice(fsm, Vhats, beam, Chats=None):
+    """Beam-pruned best-path lattices -- see ``BatchedFSM.lattice`` -- in ``maxstateposteriors``' call shape: the ``Lattice`` of the
+    batch (NumPy members), every arc on a complete path within ``beam`` of the best one.  Tropical FSMs."""
+    bf = _as_batch(fsm, Chats)
+    if bf.semiring != "tropical":
+        raise TypeError("lattice needs TropicalSemiring FSMs")
+    V, lens = _need_expanded(Vhats)
+    return bf.lattice(V, beam, lens)
 
 
 def _total(fsm, n, cumulative):
