@@ -138,6 +138,8 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * 18 = mm_lattice_f32 (tropical batches only): the two recursions' instances (mm_tropical_kernel<NI,lds|global>,
  * mm_log_kernel<MODE_BETA,NI,lds|global,TROP>), mm_pick_final_kernel, mm_lattice_prune_kernel<lds|global,count>,
  * mm_lattice_scan_kernel and mm_lattice_prune_kernel<lds|global,write>.
+ * 19 = mm_latticeposteriors_f32 (tropical batches only): mm_latpost_fb_kernel<threads> + mm_latpost_gamma_kernel<threads>; the text
+ * names the state cap and says "exceed the cap" when the batch's largest FSM has more states.
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -889,6 +891,62 @@ int mm_classpath_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64
 int mm_lattice_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
                    const float *beam, int32_t *counts, int64_t counts_stride_b, int64_t *total, float *best, int32_t *arc,
                    float *score, int64_t cap, void *stream);
+
+/* Lattice posteriors (MM_TROPICAL batches): the log-semiring forward-backward over the records of a lattice of mm_lattice_f32 (or a
+ * subset of one), under THIS call's emissions V -- a second model's, or the first one's at another acoustic scale -- and an optional
+ * extra score per record (a language-model or pronunciation rescoring, a boosting term).  One call for the whole batch returns the
+ * log posterior of every record (arc confidences; what posterior pruning and MBR decoding over the lattice read), the lattice's
+ * log-sum per utterance and the pdf occupancies, its gradient against V: lattice-based MMI as an autograd function.
+ * Conventions of mm_lattice_f32: the stored entries k = (i_k -> j_k) of T_hat in the caller's order, transitions t 0-based
+ * (t = len-1: the arcs into the phony final state f), record r of cell (b, t) is arc[r] = k with offsets[b*N + t] <= r <
+ * offsets[b*N + t + 1]; pdf(s) a state's pdf; frames 0-based below.  A lattice path of utterance b is one record r_0 .. r_{len-1}
+ * per transition with j(r_t) = i(r_{t+1}) and j(r_{len-1}) = f; it weighs
+ *
+ *   W(path) = alpha_hat(i(r_0)) + V[b, 0, pdf(i(r_0))]
+ *           + sum_{t < len-1} ( T_hat[arc[r_t]] + extra[r_t] + V[b, t+1, pdf(j(r_t))] )
+ *           + T_hat[arc[r_{len-1}]] + extra[r_{len-1}]
+ *   logz[b]        = log sum_path exp W(path)                        (-inf: no path; len = 0 included)
+ *   post[r]        = log sum_{path through r} exp W(path) - logz[b]  (<= 0; -inf: no path through r, or logz = -inf)
+ *   gamma[b, n, p] = sum_{r in cell (b, n), pdf(i(r)) = p} exp(post[r])   for n < len, 0 for n >= len and where logz = -inf
+ *
+ * alpha_hat and T_hat are the weights the tropical batch holds; extra == NULL means 0.  gamma = d logz / d V, exp(post) =
+ * d logz / d extra; for every t < len of an utterance with a path the posteriors of the cell sum to 1.  Nothing is NaN for inputs
+ * that are finite or -inf.  Where every cell holds one record and the inputs are multiples of 1/16 -- a beam of 0 with a unique best
+ * path, extra NULL, the lattice's own V -- post is exactly 0, gamma exactly 0 / 1 and logz mm_lattice_f32's best, bit for bit.
+ *
+ *   V, lens, N   as mm_lattice_f32; lens and N are those of the lattice call that produced `offsets`
+ *   offsets      device int64[B*N + 1], the exclusive prefix sum of the lattice's counts in row-major (b, t) order.  NULL: MM_ERR_INVALID
+ *   arc          device int32[nrec].  Within a cell the records ascend in k, as mm_lattice_f32 writes them; a subset of a lattice
+ *                keeps that.  NULL with nrec > 0: MM_ERR_INVALID
+ *   nrec         a host value >= 0: the records arc / extra / post hold.  Negative: MM_ERR_INVALID
+ *   extra        device float32[nrec], or NULL
+ *   post         device float32[nrec], out.  NULL with nrec > 0: MM_ERR_INVALID
+ *   logz         device float32[B], out.  NULL: MM_ERR_INVALID
+ *   gamma        device float32, out, or NULL (not computed): element (b, n, p) at gamma[b*gamma_stride_b + n*gamma_stride_n + p], all N
+ *                rows of every utterance written.  gamma_stride_n < P or gamma_stride_b < N*gamma_stride_n: MM_ERR_DIM
+ * Memory safety does not depend on the contents of the device arrays: a record whose k is outside [0, nnz_b) or is the phony
+ * self-loop is dead (its post is -inf and it contributes nothing); records at or behind nrec are never read or written (a lattice cut
+ * by mm_lattice_f32's cap goes in as it is: the result is that of the truncated lattice); offsets that decrease, are negative or reach
+ * behind nrec are clamped into [0, nrec] and made non-decreasing; lens are clamped into [0, N].  The records of cells at or behind
+ * len receive -inf; records no cell covers are not written.
+ * Log and ProbSemiring batches: MM_ERR_UNSUPPORTED.  Argument errors that need no device are reported before the NULL-batch check.
+ * The state vectors live in LDS, 16 bytes per state: an FSM of more than about 10 200 states (padded) returns MM_ERR_UNSUPPORTED
+ * with the limit in the message; mm_batch_kernels(.., 19, ..) names it.
+ * Order of a call: mm_latpost_fb_kernel (one workgroup per utterance, serial over its transitions; per step three passes over the
+ * records of the cell: gather source, destination and weight through arc[r] from mm_lattice_f32's arc table, the emission of the
+ * destination and extra[r]; per target state an integer LDS maximum on an order-preserving code of the float, then the sum of
+ * exp(x - max) in 64-bit fixed point, rint(. * 2^40), by 64-bit integer LDS adds; the vectors relative to a per-step maximum that
+ * is accumulated in double.  The forward value of a record is kept in post[r]; the backward pass overwrites it with
+ * y_r - LSE_cell(y), the cell's own log-sum -- logz is never subtracted from anything), then, when gamma is given,
+ * mm_latpost_gamma_kernel (one workgroup per (b, n): exp(post) by the source's pdf, the same fixed-point adds).  Integer maxima and
+ * integer sums do not depend on the order of arrival: a repeated call returns the same bits.  The terms a sum loses lie below 2^-41
+ * of its largest.  The work of a step is proportional to the records of its cell, not to the graph.
+ * No workspace.  Stream contract of the arc entries: launches on `stream` only, no host synchronisation; capturable in a hipGraph
+ * after a first call of this entry or of mm_lattice_f32 has put the item forms and the arc table on the device (a capture before
+ * that returns MM_ERR_INVALID); a replay after V, extra, offsets or arc were overwritten in place follows them. */
+int mm_latticeposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                             const int64_t *offsets, const int32_t *arc, int64_t nrec, const float *extra, float *post, float *logz,
+                             float *gamma, int64_t gamma_stride_b, int64_t gamma_stride_n, void *stream);
 
 /* totalsum(alpha, T, omega, n) / totalcumsum(alpha, T, omega, n) (src/algorithms.jl:8-29;
  * totalweightsum(fsm, n) = totalcumsum, :36), one value per FSM of the batch, in the batch's semiring

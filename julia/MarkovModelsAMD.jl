@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, set_arc_classes!, arc_class_info, arcclassposteriors, score_class_cap, scoredposteriors, cost_class_cap, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, set_path_classes!, path_class_info, classpath, lattice, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, set_arc_classes!, arc_class_info, arcclassposteriors, score_class_cap, scoredposteriors, cost_class_cap, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, set_path_classes!, path_class_info, classpath, lattice, latticeposteriors, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -925,6 +925,38 @@ function lattice(b::ROCBatch{K}, V::ROCArray{Float32,3}, beam, lens = nothing) w
         pointer(score), n, AMDGPU.stream().stream))
     c = Array(counts)
     c, vcat(Int64(0), cumsum(Int64.(vec(c)))), Array(arc) .+ Int32(1), Array(score), Array(best)
+end
+
+"""
+    latticeposteriors(b::ROCBatch{<:TropicalSemiring}, V, offsets, arc, lens = nothing; extra = nothing, want_gamma = true)
+        -> (post, logz, gamma)
+
+Lattice posteriors (mm_latticeposteriors_f32 in the header): the log-semiring forward-backward over the records of a lattice --
+`offsets` and `arc` as `lattice` returns them (`arc` 1-based), or a subset that keeps the order within a transition -- under the
+emissions `V` of this call and an optional score `extra` per record.  `post[r]` is the log posterior of record r, `logz` (B) the
+log-sum of the lattice's paths, `gamma` (`P × N × B`, `nothing` without `want_gamma`) the pdf occupancies: the gradient of `logz`
+against `V`; `exp.(post)` is the gradient against `extra`.  `lens` are those of the lattice call.
+"""
+function latticeposteriors(b::ROCBatch{K}, V::ROCArray{Float32,3}, offsets::AbstractVector{<:Integer}, arc::AbstractVector{<:Integer},
+                           lens = nothing; extra = nothing, want_gamma::Bool = true) where K <: TropicalSemiring
+    P, N, B = size(V)
+    length(offsets) == N * B + 1 || throw(DimensionMismatch("offsets must have N·B + 1 = $(N * B + 1) entries"))
+    n = length(arc)
+    offsets[end] <= n || throw(ArgumentError("the lattice has $(offsets[end]) records, arc holds $n"))
+    extra === nothing || length(extra) == n || throw(DimensionMismatch("extra must hold one score per record ($n)"))
+    offs = ROCArray(Int64.(collect(offsets)))
+    arcd = ROCArray(Int32.(collect(arc)) .- Int32(1))
+    ex = extra === nothing ? nothing : ROCArray(Float32.(collect(extra)))
+    post = ROCArray{Float32}(undef, n)
+    logz = ROCArray{Float32}(undef, B)
+    gamma = want_gamma ? ROCArray{Float32}(undef, P, N, B) : nothing
+    lp = lens === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(lens))
+    check(ccall((:mm_latticeposteriors_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Int64}, Ptr{Int32}, Int64, Ptr{Float32}, Ptr{Float32}, Ptr{Float32},
+         Ptr{Float32}, Int64, Int64, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, lp, N, pointer(offs), pointer(arcd), n, ex === nothing ? Ptr{Float32}(C_NULL) : pointer(ex),
+        pointer(post), pointer(logz), gamma === nothing ? Ptr{Float32}(C_NULL) : pointer(gamma), P * N, P, AMDGPU.stream().stream))
+    Array(post), Array(logz), gamma === nothing ? nothing : Array(gamma)
 end
 
 """

@@ -241,6 +241,7 @@ struct DebugOpts {
     int split_q10 = 0;              // MM_SPLIT_Q10: where the pair kernels cut the frames between the agents (1024ths; 0: the engine's choice)
     int x_sleep = 8;                // MM_SPLIT_SLEEP: split kernels, 64-clock units the exchange wave sleeps before a step's first poll
     float group_speed[4] = {0, 0, 0, 0};  // MM_GROUP_SPEED=a,b,c,d
+    int latpost_nt = 0;             // MM_LATPOST_NT: threads of mm_latpost_fb_kernel's workgroup (256, 512, 1024; 0: MM_LATPOST_NT of mm_internal.h)
     bool sample_nostage = false;    // MM_SAMPLE_NOSTAGE: mm_sample_kernel gathers alpha~ from global memory whatever the size (a measurement aid)
 };
 static DebugOpts read_debug_opts() {
@@ -269,6 +270,7 @@ static DebugOpts read_debug_opts() {
     if (const char *e = getenv("MM_FINISH_COST")) d.finish_cost = atoi(e);
     if (const char *e = getenv("MM_SPLIT_SLEEP")) d.x_sleep = atoi(e);
     if (const char *e = getenv("MM_SPLIT_Q10")) d.split_q10 = atoi(e);
+    if (const char *e = getenv("MM_LATPOST_NT")) d.latpost_nt = atoi(e);
     if (const char *e = getenv("MM_GROUP_SPEED")) sscanf(e, "%f,%f,%f,%f", &d.group_speed[0], &d.group_speed[1], &d.group_speed[2], &d.group_speed[3]);
     return d;
 }
@@ -565,6 +567,10 @@ static size_t classpath_lds_bytes(const ItemPlan &pl, int64_t C, bool scored) { 
 
 // mm_lattice_f32: the prune kernel gathers the two rows of a cell from global memory when they do not fit the LDS, or under MM_BIGV
 static bool lattice_global(mm_batch_t h) { return h->dbg.bigv || mm_lattice_lds_bytes(h->max_S1p) > MM_LDS_MAX; }
+
+// mm_latticeposteriors_f32: the workgroup of its forward-backward, and the states its three per-state LDS arrays hold
+static int latpost_nt(mm_batch_t h) { return h->dbg.latpost_nt ? h->dbg.latpost_nt : MM_LATPOST_NT; }
+static int64_t latpost_state_cap() { return int64_t((MM_LDS_MAX - mm_latpost_lds_bytes(0)) / (mm_latpost_lds_bytes(1) - mm_latpost_lds_bytes(0))); }
 
 // item / tropical kernels: `kernel` keeps the state vectors in LDS; `big` is the same kernel with the vectors in global
 // memory, for FSMs beyond the LDS (the reference has no size limit: src/linalg.jl:170-181)
@@ -2820,6 +2826,12 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
             " (beta) + mm_pick_final_kernel + mm_lattice_prune_kernel<" + where + ",count> (one workgroup per utterance and transition: the through-score of "
             "every stored arc against the beam) + mm_lattice_scan_kernel (offsets and total) + mm_lattice_prune_kernel<" + where +
             ",write> (the kept arcs in entry order); the two rows of a transition " + (lattice_global(h) ? "gathered from global memory" : "in LDS");
+    } else if (entry == 19) {  // mm_latticeposteriors_f32
+        if (h->semiring != MM_TROPICAL) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_latticeposteriors_f32 runs on tropical batches only");
+        s = "mm_latpost_fb_kernel<" + std::to_string(latpost_nt(h)) + "> (one workgroup per utterance, serial over the transitions: the forward-backward over "
+            "the records of each cell, state vectors in LDS, integer max and 64-bit fixed-point sums) + mm_latpost_gamma_kernel<" +
+            std::to_string(MM_LATPOST_GAMMA_NT) + "> (one workgroup per utterance and frame, when gamma is asked for); state cap " + std::to_string(latpost_state_cap());
+        if (mm_latpost_lds_bytes(h->max_S1p) > MM_LDS_MAX) s += "; " + std::to_string(h->max_S1p) + " states exceed the cap";
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -4772,6 +4784,46 @@ int mm_lattice_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const
     lp.score = score;
     lp.cap = cap;
     return mm_launch_lattice(h->B, lattice_global(h), h->max_S1p, p, lp, reinterpret_cast<long long *>(total), static_cast<hipStream_t>(stream));
+}
+
+// ---- lattice posteriors (mm_kernel_latpost.hip): the log-semiring forward-backward over the records of a lattice
+int mm_latticeposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, const int64_t *offsets,
+                             const int32_t *arc, int64_t nrec, const float *extra, float *post, float *logz, float *gamma, int64_t gsb, int64_t gsn,
+                             void *stream) {
+    const std::string who = "mm_latticeposteriors_f32";
+    // what the arguments alone show comes first, then the batch's refusals
+    if (!offsets || !logz) return fail(MM_ERR_INVALID, who + ": offsets/logz is NULL");
+    if (nrec < 0) return fail(MM_ERR_INVALID, who + ": nrec must be >= 0");
+    if (nrec > 0 && (!arc || !post)) return fail(MM_ERR_INVALID, who + ": arc/post is NULL with nrec > 0");
+    if (gamma && (gsn < 1 || gsb < N * gsn)) return fail(MM_ERR_DIM, who + ": gamma_stride_n < 1 or gamma_stride_b < N * gamma_stride_n");
+    if (h && h->semiring != MM_TROPICAL)
+        return fail(MM_ERR_UNSUPPORTED, who + ": tropical batches only (this batch is " + (h->semiring == MM_LOG ? "log-semiring" : "ProbSemiring") + ")");
+    int rc = check_run(h, who.c_str(), V, N, MM_TROPICAL);
+    if (rc) return rc;
+    if (gamma && gsn < h->max_P1 - 1) return fail(MM_ERR_DIM, who + ": gamma_stride_n < P");
+    if (h->B * N > int64_t(INT32_MAX)) return fail(MM_ERR_UNSUPPORTED, who + ": B * N exceeds 2^31 - 1 workgroups");
+    if (mm_latpost_lds_bytes(h->max_S1p) > MM_LDS_MAX)
+        return fail(MM_ERR_UNSUPPORTED, who + ": " + std::to_string(h->max_S1p) + " states (padded) exceed the " + std::to_string(latpost_state_cap()) +
+                                            " whose vectors fit the LDS (16 bytes per state)");
+    if (gamma && mm_latpost_gamma_lds_bytes(h->max_P1) > MM_LDS_MAX) return fail(MM_ERR_UNSUPPORTED, who + ": too many pdfs for the LDS: " + std::to_string(h->max_P1));
+    const int nt = latpost_nt(h);
+    if (nt != 256 && nt != 512 && nt != 1024) return fail(MM_ERR_INVALID, who + ": MM_LATPOST_NT must be 256, 512 or 1024");
+    rc = ensure_item_forms(h, stream);
+    if (!rc) rc = ensure_lattice_arcs(h, stream);
+    if (rc) return rc;
+    const RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    LatPostParams lp{};
+    lp.arcs = static_cast<const LatticeDev *>(h->d_lat.get());
+    lp.offs = reinterpret_cast<const long long *>(offsets);
+    lp.arc = arc;
+    lp.nrec = nrec;
+    lp.extra = extra;
+    lp.post = post;
+    lp.logz = logz;
+    lp.gamma = gamma;
+    lp.gsb = gsb;
+    lp.gsn = gsn;
+    return mm_launch_latpost(h->B, nt, h->max_S1p, h->max_P1, p, lp, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

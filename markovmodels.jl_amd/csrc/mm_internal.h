@@ -482,6 +482,27 @@ struct LatticeParams {
 int mm_launch_lattice(int64_t B, bool global, int max_S1p, const RunParams &p, const LatticeParams &lp, long long *total, hipStream_t stream);
 size_t mm_lattice_lds_bytes(int S1p);
 
+// ---- lattice posteriors (mm_latpost_tu.hip: mm_latpost_fb_kernel, one workgroup per utterance over the records of a lattice, and
+// mm_latpost_gamma_kernel, one workgroup per utterance and frame; tropical batches -- the arc table is mm_lattice_f32's)
+#define MM_LATPOST_NT 1024       // threads of a workgroup of the forward-backward, by measurement (profiles/latticeposteriors_bench.json);
+                                 // MM_LATPOST_NT under MM_DEBUG: 256, 512 or 1024
+#define MM_LATPOST_GAMMA_NT 256  // ... and of the per-pdf sums
+struct LatPostParams {
+    const LatticeDev *arcs;  // [B]
+    const long long *offs;   // [B * N + 1] the caller's cell offsets (clamped into [0, nrec] by the kernels)
+    const int *arc;          // [nrec] the caller's records
+    long long nrec;
+    const float *extra;      // [nrec] or NULL
+    float *post;             // [nrec]
+    float *logz;             // [B]
+    float *gamma;            // NULL: no per-pdf sums; row (b, n) at b * gsb + n * gsn
+    long long gsb, gsn;
+};
+// the forward-backward in its instance of `nt` threads, then the per-pdf sums when lp.gamma is given
+int mm_launch_latpost(int64_t B, int nt, int max_S1p, int max_P1, const RunParams &p, const LatPostParams &lp, hipStream_t stream);
+size_t mm_latpost_lds_bytes(int S1p);       // a head + 16 bytes per state: two 32-bit words and a 64-bit sum
+size_t mm_latpost_gamma_lds_bytes(int P1);  // a 64-bit sum per pdf
+
 // ---- posteriors with call-time arc weights (mm_weighted_tu.hip: mm_weights_kernel, mm_log_kernel's forward half on the call's
 // descriptors, mm_weighted_bwd_kernel and mm_weighted_scatter_kernel on the item form)
 struct UttDesc;  // mm_kernels.hip

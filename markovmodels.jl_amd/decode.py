@@ -7,7 +7,8 @@ and t + 1 (0-based; t = len - 1: the arc into the phony final state), -1 for an 
 there is no path.
 
 And from the ``Lattice`` of ``BatchedFSM.lattice`` (mm_lattice_f32): one utterance's kept arcs as host arrays (``lattice_arcs``) and
-as an acyclic tropical FSM that goes back into ``compile`` / ``batch`` for rescoring (``lattice_fsm``).
+as an acyclic tropical FSM that goes back into ``compile`` / ``batch`` for rescoring (``lattice_fsm``); and the lattice of the
+records above a posterior threshold (``lattice_prune``, on the posteriors of ``BatchedFSM.latticeposteriors``).
 """
 from __future__ import annotations
 
@@ -109,3 +110,42 @@ def lattice_fsm(bf, lat, b):
     labels = [(int(q // S1), int(q % S1)) for q in keys]
     s2p = np.asarray(cf.C_hat.state2pdf, dtype=np.int64)[keys % S1]
     return FSM(initws, arcs, finalws, labels, semiring="tropical", dtype=np.float32), s2p
+
+
+def lattice_prune(lat, post, threshold):
+    """Posterior pruning of a ``Lattice``: the ``Lattice`` of the records with ``post >= log(threshold)``, ``post`` being the record
+    log posteriors of ``BatchedFSM.latticeposteriors`` on ``lat`` and ``threshold`` a probability (0 keeps every record with a path
+    through it).  Counts and offsets are recomputed, ``arc`` and ``score`` keep their order, ``best`` stays: the result goes back into
+    ``latticeposteriors``, ``lattice_arcs`` and ``lattice_fsm``.  Tensor members stay tensors on their device (no host
+    synchronisation but the one that sizes the result), NumPy members stay NumPy."""
+    import math
+
+    n = lat.arc.shape[0]
+    if post.shape[0] != n or lat.score.shape[0] != n:
+        raise ValueError(f"lattice_prune: {post.shape[0]} posteriors and {lat.score.shape[0]} scores for {n} records")
+    if threshold < 0:
+        raise ValueError(f"lattice_prune: threshold must be a probability, got {threshold}")
+    bound = math.log(threshold) if threshold > 0 else -math.inf
+    B, N = lat.counts.shape
+    if hasattr(lat.arc, "cpu"):  # (tensors)
+        import torch
+
+        offsets = lat.offsets.to(lat.arc.device)
+        keep = post.to(lat.arc.device) >= bound
+        if threshold <= 0:
+            keep &= ~torch.isneginf(post.to(lat.arc.device))
+        r = torch.arange(n, device=lat.arc.device, dtype=offsets.dtype)
+        cell = torch.searchsorted(offsets[1:].contiguous(), r, right=True)
+        keep &= cell < B * N  # (records behind the last cell belong to no transition)
+        counts = torch.bincount(cell[keep], minlength=B * N)[: B * N].to(lat.counts.dtype).reshape(B, N)
+        offs = torch.cat([torch.zeros(1, dtype=offsets.dtype, device=offsets.device), torch.cumsum(counts.reshape(-1), 0, dtype=offsets.dtype)])
+        return type(lat)(counts, offs, lat.arc[keep], lat.score[keep], lat.best)
+    offsets, p = _host(lat.offsets), _host(post)
+    keep = p >= bound
+    if threshold <= 0:
+        keep &= ~np.isneginf(p)
+    cell = np.searchsorted(offsets[1:], np.arange(n, dtype=np.int64), side="right")
+    keep &= cell < B * N
+    counts = np.bincount(cell[keep], minlength=B * N)[: B * N].astype(_host(lat.counts).dtype).reshape(B, N)
+    offs = np.concatenate([[0], np.cumsum(counts.reshape(-1), dtype=np.int64)])
+    return type(lat)(counts, offs, _host(lat.arc)[keep], _host(lat.score)[keep], lat.best)

@@ -159,6 +159,24 @@ class Lattice(NamedTuple):
     best: object
 
 
+class LatticePosteriors(NamedTuple):
+    """What ``BatchedFSM.latticeposteriors`` returns.  ``post`` float32, one per record of the lattice: the log posterior of the
+    record (<= 0; -inf: no path through it); ``logz[B]``: the log-sum of the lattice's paths (-inf: none); ``gamma[B, N, P]``: the
+    pdf occupancies, the gradient of ``logz`` against ``V`` (None when not asked for)."""
+
+    post: object
+    logz: object
+    gamma: object
+
+
+def _on_device(x, dtype, device):
+    """A member of a lattice (or ``extra``) as a contiguous tensor of ``dtype`` on ``device``: a tensor, or anything NumPy reads."""
+    import torch
+
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(x))
+    return t.to(device=device, dtype=dtype).contiguous()
+
+
 def _results(res, as_numpy):
     """The tuple an entry returns: NumPy arrays if V came as NumPy, None members as they are."""
     return tuple(t.cpu().numpy() if t is not None else None for t in res) if as_numpy else res
@@ -1002,11 +1020,12 @@ class BatchedFSM:
         alpharecursion / betarecursion, "arcs" = arcposteriors, "sample" = samplepaths, "cost" = expectedcost, "leaky" =
         leakyposteriors, "entropy" = pathentropy, "filter" = filterposteriors, "window" = windowposteriors,
         "vitwindow" = viterbiwindow (tropical batches), "weighted" = weightedposteriors, "segment" = segmentposteriors,
-        "classpath" = classpath (tropical batches), "lattice" = lattice (tropical batches)."""
+        "classpath" = classpath (tropical batches), "lattice" = lattice (tropical batches), "latticeposteriors" = latticeposteriors
+        (tropical batches)."""
         import ctypes
 
         buf = ctypes.create_string_buffer(1024)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13, "arcclass": 14, "scored": 15, "classcost": 16, "classpath": 17, "lattice": 18}[semiring], buf, 1024))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13, "arcclass": 14, "scored": 15, "classcost": 16, "classpath": 17, "lattice": 18, "latticeposteriors": 19}[semiring], buf, 1024))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -1119,6 +1138,44 @@ class BatchedFSM:
             arc, score = arc[:n], score[:n]
         offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counts.reshape(-1), 0, dtype=torch.int64)])
         return Lattice(*_results((counts, offsets, arc, score, best), as_numpy))
+
+    def latticeposteriors(self, lat, V, lens=None, extra=None, want_gamma=True):
+        """Lattice posteriors (mm_latticeposteriors_f32): the log-semiring forward-backward over the records of ``lat`` -- a
+        ``Lattice`` of ``BatchedFSM.lattice`` on this batch, or a subset of one (``decode.lattice_prune``) -- under the emissions
+        ``V`` of THIS call (a second model's, or the first one's at another scale) and an optional score ``extra`` per record.
+        Returns ``LatticePosteriors(post, logz, gamma)``: ``post`` float32 per record, the log posterior of the record among the
+        lattice's paths (-inf: no path through it); ``logz[B]`` the lattice's log-sum (-inf: no path); ``gamma[B, N, P]`` the pdf
+        occupancies = d logz / d V (``want_gamma=False``: None, and the second kernel does not run); ``exp(post)`` is
+        d logz / d extra.  ``lens`` are those of the lattice call.  ``lat``'s members may be tensors or NumPy arrays; the results are
+        NumPy arrays if ``V`` came as NumPy.  ValueError when ``lat.arc`` holds fewer records than ``lat.offsets[-1]`` (a lattice
+        cut by ``max_arcs``) -- one read-back, left out inside a stream capture.  Integer maxima and fixed-point sums: bit-identical
+        from call to call.  Tropical batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        dev = Vt.device
+        offsets = _on_device(lat.offsets, torch.int64, dev)
+        arc = _on_device(lat.arc, torch.int32, dev)
+        if offsets.dim() != 1 or offsets.numel() != B * N + 1:
+            raise _lib.DimensionMismatch(-2, f"lat.offsets must be [B * N + 1 = {B * N + 1}], got {tuple(offsets.shape)}")
+        nrec = arc.numel()
+        if arc.dim() != 1:
+            raise _lib.DimensionMismatch(-2, f"lat.arc must be a vector, got {tuple(arc.shape)}")
+        et = None
+        if extra is not None:
+            et = _on_device(extra, torch.float32, dev)
+            if et.dim() != 1 or et.numel() != nrec:
+                raise _lib.DimensionMismatch(-2, f"extra must be [{nrec}], one score per record, got {tuple(et.shape)}")
+        if not torch.cuda.is_current_stream_capturing():
+            total = int(offsets[-1].item())
+            if total > nrec:
+                raise ValueError(f"latticeposteriors: the lattice has {total} records, lat.arc holds {nrec} (max_arcs cut it)")
+        post = torch.empty(nrec, dtype=torch.float32, device=dev)
+        logz = torch.empty(B, dtype=torch.float32, device=dev)
+        gamma = torch.empty((B, N, P), dtype=torch.float32, device=dev) if want_gamma else None
+        check(lib.mm_latticeposteriors_f32(*_head(self._h, Vt, lt, N), offsets.data_ptr(), arc.data_ptr(), nrec, _ptr(et), post.data_ptr(),
+                                           logz.data_ptr(), _ptr(gamma), gamma.stride(0) if want_gamma else 0, gamma.stride(1) if want_gamma else 0,
+                                           self._stream(torch)))
+        return LatticePosteriors(*_results((post, logz, gamma), as_numpy))
 
     def totalsum(self, n: int, cumulative: bool = False):
         """Per FSM of the batch: omega . v_n (totalsum) or the semiring sum over k <= n of omega . v_k
@@ -1613,6 +1670,16 @@ def lattice(fsm, Vhats, beam, Chats=None):
         raise TypeError("lattice needs TropicalSemiring FSMs")
     V, lens = _need_expanded(Vhats)
     return bf.lattice(V, beam, lens)
+
+
+def latticeposteriors(fsm, lat, Vhats, Chats=None, extra=None):
+    """Lattice posteriors -- see ``BatchedFSM.latticeposteriors`` -- in ``lattice``'s call shape: the ``LatticePosteriors`` (NumPy
+    members) of the lattice ``lat`` of the batch under the expanded emissions ``Vhats``.  Tropical FSMs."""
+    bf = _as_batch(fsm, Chats)
+    if bf.semiring != "tropical":
+        raise TypeError("latticeposteriors needs TropicalSemiring FSMs")
+    V, lens = _need_expanded(Vhats)
+    return bf.latticeposteriors(lat, V, lens, extra)
 
 
 def _total(fsm, n, cumulative):
