@@ -1832,6 +1832,11 @@ int mm_debug_wave_product(mm_fsm_t f, int direction, const float *in, float *out
         (direction == 1 && !make_rows(f->S1, f->mat[1].rowptr, f->mat[1].col, f->mat[1].val, f->s2p, f->P1, true, gf.pos, opt, g)))
         return fail(MM_ERR_UNSUPPORTED, "mm_debug_wave_product: the FSM does not fit the wave form");
     if (direction == 0) g = gf;
+    {   // (what wave_pack refuses beyond the rows: more than 256 pdfs, a pdf of more than 256 states, more than 8 pdf segments)
+        std::vector<uint32_t> tab;
+        if (f->P1 > 256 || wave_pdf_table(g, f->s2p, f->S1, f->P1, tab) <= 0)
+            return fail(MM_ERR_UNSUPPORTED, "mm_debug_wave_product: the FSM's pdf sums do not fit the wave form");
+    }
     const float NINF = -std::numeric_limits<float>::infinity();
     std::vector<float> x(size_t(f->S1) + 1, NINF), y(size_t(f->S1) + 1, NINF);
     for (int64_t i = 0; i < f->S1; ++i) x[size_t(i)] = in[g.order[size_t(i)]] * MM_LOG2E;
@@ -2610,6 +2615,12 @@ static std::string tropical_kernel(mm_batch_t h) {  // (launch_tropical)
     return "mm_tropical_kernel<" + std::to_string(pl.NI) + "," + where_of(pl.global) + ">";
 }
 
+// the wave kernel's instance (wave_launch_of): a wave batch's kernel, and what a lane batch with wave forms runs for its marked utterances
+static std::string wave_instance(mm_batch_t h) {
+    return "mm_wave_kernel<" + std::to_string(h->wave_nseg <= 2 ? 2 : 4) + "," + std::to_string(h->max_P1 <= 128 ? 2 : 4) +
+        (h->wave_nseg <= 2 && h->B > h->n_cus ? ",two per CU>" : ">");
+}
+
 static std::string fb_kernels(mm_batch_t h) {
     // what fb_exact runs, and (`redo`) what the families that hand their marked utterances to redo_on_items run
     const std::string quad = "mm_fbq_kernel<" + std::to_string(h->geo_kq[0]) + ",*,0> + mm_fbq_kernel<" + std::to_string(h->geo_kq[1]) + ",*,1>";
@@ -2619,10 +2630,10 @@ static std::string fb_kernels(mm_batch_t h) {
     switch (h->fb) {
     case Fb::Lane:
         return "mm_lane_kernel<" + std::to_string(h->lane_S <= 8 ? 8 : h->lane_S <= 16 ? 16 : h->lane_S <= 32 ? 32 : 64) +
-            "> (one wave per utterance and direction, the graph in its registers, float64)";
+            "> (one wave per utterance and direction, the graph in its registers, float64), then for marked utterances only " +
+            (h->lane_redo_wave ? wave_instance(h) : redo);
     case Fb::Wave:
-        return "mm_wave_kernel<" + std::to_string(h->wave_nseg <= 2 ? 2 : 4) + "," + std::to_string(h->max_P1 <= 128 ? 2 : 4) +
-            (h->wave_nseg <= 2 && h->B > h->n_cus ? ",two per CU>" : ">");
+        return wave_instance(h);
     case Fb::Stream:
         return "mm_stream_kernel<" + std::to_string(mm_stream_nj(h->max_P1)) + "," + std::to_string(h->stream_H) + "> (forward and backward recursions as workgroups of one grid" +
             (h->stream_H > 1 ? ", teams of " + std::to_string(h->stream_H) + " workgroups per utterance and direction" : std::string()) +

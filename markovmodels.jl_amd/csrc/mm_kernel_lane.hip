@@ -116,7 +116,7 @@ __global__ void __launch_bounds__(256) mm_lane_kernel(RunParams p) {
         s_stored[threadIdx.x] = 0;
     }
     if (!ident && wv == 0) {
-        if (lane <= P) pdfp[lane] = uni(ldp->pdf_ptr)[lane];
+        for (int q = lane; q <= P; q += 64) pdfp[q] = uni(ldp->pdf_ptr)[q];  // (P + 1 entries: 65 of them when P = 64)
         if (lane < S) pdfs[lane] = uni(ldp->pdf_states)[lane];
     }
     // the frames: the forward agent walks 1, 2, ..., the backward agent len, len - 1, ...; each stores its first nA frames

@@ -528,7 +528,11 @@ mm_wave_kernel(RunParams p) {
                 *reinterpret_cast<float *>(reinterpret_cast<char *>(rowf) + pos4) = st;
             } else {
                 float uu = st + pv[i];  // log2 (alpha beta) up to the two offsets   (:154)
-                uu = uu > MM_WAVE_NEG ? uu : MM_WAVE_NEG;
+                // (the lanes of a row's group that finish nothing write the trash position, which the pdf sums read for their
+                // unused slots: zero(K) there.  Forward, their y is zero(K) by the emission slot of zero(K); backward, st = bq is
+                // the group's value and pv the partner's position 0 -- a finite u from whichever wave wrote last.  y is zero(K)
+                // exactly where u must be: a lane without a row, a dead row, an emission of zero(K))
+                uu = (uu > MM_WAVE_NEG && y > MM_WAVE_NEG) ? uu : MM_WAVE_NEG;
                 ldsw(base + MM_WAVE_QV(WR) + pos4, uu);
             }
         });
