@@ -140,6 +140,8 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * mm_lattice_scan_kernel and mm_lattice_prune_kernel<lds|global,write>.
  * 19 = mm_latticeposteriors_f32 (tropical batches only): mm_latpost_fb_kernel<threads> + mm_latpost_gamma_kernel<threads>; the text
  * names the state cap and says "exceed the cap" when the batch's largest FSM has more states.
+ * 20 = mm_latticecost_f32 (tropical batches only): mm_latcost_fb_kernel<threads> + mm_latcost_grad_kernel<threads>; the text names
+ * the bytes of LDS per state and the state cap, and says "exceed the cap" when the batch's largest FSM has more states.
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -947,6 +949,59 @@ int mm_lattice_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t
 int mm_latticeposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
                              const int64_t *offsets, const int32_t *arc, int64_t nrec, const float *extra, float *post, float *logz,
                              float *gamma, int64_t gamma_stride_b, int64_t gamma_stride_n, void *stream);
+
+/* Lattice expected cost (MM_TROPICAL batches): the expectation of a cost that adds up along a path, over the paths of a lattice of
+ * mm_lattice_f32 weighed as mm_latticeposteriors_f32 weighs them, and its gradient -- the lattice form of mm_expectedcost_f32.  With
+ * cost[r] minus the phone or word accuracy of the record it is MPE / MWE (Povey 2003), with minus [pdf of the record's source = the
+ * alignment's pdf] state-level MBR; the loss of MBR decoding over a lattice is the same expectation.  Records, cells, offsets, arc,
+ * extra, W(path), post, logz and gamma are exactly those of mm_latticeposteriors_f32, i(r) / j(r) the source / destination of a record:
+ *
+ *   A(path)      = sum_{t < len} cost[r_t]                                   one record per transition, as in W(path)
+ *   risk[b]      = sum_path exp(W(path) - logz[b]) * A(path)
+ *   diff[r]      = exp(post[r]) * (E[A | path through r] - risk[b])          = d risk / d extra[r]   (Povey's gamma^MPE of the arc)
+ *   grad[b,n,p]  = sum_{r in cell (b, n), pdf(i(r)) = p} diff[r]             = d risk / d V[b,n,p];  exact 0 for n >= len
+ *   d risk / d cost[r] = exp(post[r])
+ *   E[A | through r] = ca_t(i(r)) + cost[r] + cb_{t+1}(j(r))
+ *     ca_0(.) = 0        ca_{t+1}(j) = sum_{r in cell t, j(r) = j} exp(x_r - a_{t+1}(j)) * (ca_t(i(r)) + cost[r])
+ *     cb_len(f) = 0      cb_t(i)     = sum_{r in cell t, i(r) = i} exp(z_r - b_t(i))     * (cost[r] + cb_{t+1}(j(r)))
+ *   risk[b] = ca_len(f)
+ *
+ * x_r and z_r are the forward and backward values of a record in mm_latticeposteriors_f32's recursions (a_t(i(r)) resp. b_{t+1}(j(r))
+ * plus the record's own weight); both sums are convex combinations plus an addition.  Identities: post, logz and gamma are bit for bit
+ * those of mm_latticeposteriors_f32 on the same inputs; every cell's diff sums to 0 and every row of grad sums to 0; risk =
+ * sum_r exp(post[r]) cost[r]; a cost that is constant within each cell (c_t) gives risk = sum_{t < len} c_t and diff = grad = 0;
+ * where every cell holds one record and the costs are multiples of 1/16, risk is the exact sum and diff and grad are exactly 0.
+ *
+ *   batch .. extra   as mm_latticeposteriors_f32
+ *   cost         device float32[nrec]; finite on the live records of cells t < len (a non-finite cost leaves that utterance's outputs
+ *                unspecified and touches no other utterance).  NULL with nrec > 0: MM_ERR_INVALID
+ *   risk         device float32[B], out.  NULL: MM_ERR_INVALID
+ *   diff         device float32[nrec], out.  NULL with nrec > 0: MM_ERR_INVALID
+ *   post, logz   as mm_latticeposteriors_f32, required
+ *   grad, gamma  device float32, out, each or both NULL (not computed): element (b, n, p) at [b*stride_b + n*stride_n + p] of either,
+ *                one pair of strides for both, all N rows of every utterance written.  stride_n < P or stride_b < N*stride_n: MM_ERR_DIM
+ * An utterance without a path (len = 0 included) gets risk 0, diff 0, grad 0, gamma 0 and logz -inf.  Dead records and the records of
+ * cells at or behind len get diff 0 and post -inf; records no cell covers are not written.  Nothing is NaN for inputs that are finite
+ * or -inf.  Memory safety does not depend on the contents of the device arrays, by mm_latticeposteriors_f32's checks: dead records,
+ * clamped and monotone offsets, lens clamped into [0, N].
+ * Log and ProbSemiring batches: MM_ERR_UNSUPPORTED.  Argument errors that need no device are reported before the NULL-batch check.
+ * The state vectors live in LDS, 28 bytes per state (the 16 of the posteriors, a signed 64-bit cost sum and a float): an FSM of more
+ * than about 5 800 states (padded) returns MM_ERR_UNSUPPORTED with the limit in the message; mm_batch_kernels(.., 20, ..) names it.
+ * Order of a call: mm_latcost_fb_kernel -- mm_latpost_fb_kernel's code with the cost part compiled in: the same three passes per step.
+ * A state's ca (forward; cb backward) is kept relative to the largest value of the step that finished it, and forward those maxima
+ * accumulate in a double that ends as the risk, so the float32 values stay near zero however long the utterance is.  Per step the
+ * block's maximum vmax of |v_r|, v_r = centred ca(i(r)) + cost[r], is taken beside the first pass; the second adds
+ * rint(exp(x_r - max) * (v_r / vmax) * 2^40) as a signed 64-bit integer per target state; the thread that finishes a state sets its
+ * value to (cost sum / sum) * vmax.  diff[r] holds v_r between the passes.  Backward, u_r = v_r + centred cb(j(r)) is the cost of
+ * the paths through r up to a constant of the cell; the cell's posterior mean u_bar of u is summed in the same fixed point and
+ * diff[r] = exp(post[r]) * (u_r - u_bar), so no offset of the forward pass is needed.  Then, when grad or gamma is given,
+ * mm_latcost_grad_kernel (one workgroup per (b, n): diff by the source's pdf as signed fixed point relative to the cell's largest
+ * |diff|, exp(post) as mm_latpost_gamma_kernel sums it).  Integer maxima and integer sums: a repeated call returns the same bits in
+ * every output.  No workspace.  Stream contract and graph capture: those of mm_latticeposteriors_f32 (a first call of this entry
+ * counts); a replay after V, extra, cost, offsets or arc were overwritten in place follows them. */
+int mm_latticecost_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                       const int64_t *offsets, const int32_t *arc, int64_t nrec, const float *extra, const float *cost, float *risk,
+                       float *diff, float *post, float *logz, float *grad, float *gamma, int64_t stride_b, int64_t stride_n, void *stream);
 
 /* totalsum(alpha, T, omega, n) / totalcumsum(alpha, T, omega, n) (src/algorithms.jl:8-29;
  * totalweightsum(fsm, n) = totalcumsum, :36), one value per FSM of the batch, in the batch's semiring

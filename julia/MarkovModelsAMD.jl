@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, set_arc_classes!, arc_class_info, arcclassposteriors, score_class_cap, scoredposteriors, cost_class_cap, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, set_path_classes!, path_class_info, classpath, lattice, latticeposteriors, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, set_arc_classes!, arc_class_info, arcclassposteriors, score_class_cap, scoredposteriors, cost_class_cap, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, set_path_classes!, path_class_info, classpath, lattice, latticeposteriors, latticecost, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -957,6 +957,44 @@ function latticeposteriors(b::ROCBatch{K}, V::ROCArray{Float32,3}, offsets::Abst
         b.handle, pointer(V), P * N, P, lp, N, pointer(offs), pointer(arcd), n, ex === nothing ? Ptr{Float32}(C_NULL) : pointer(ex),
         pointer(post), pointer(logz), gamma === nothing ? Ptr{Float32}(C_NULL) : pointer(gamma), P * N, P, AMDGPU.stream().stream))
     Array(post), Array(logz), gamma === nothing ? nothing : Array(gamma)
+end
+
+"""
+    latticecost(b::ROCBatch{<:TropicalSemiring}, V, offsets, arc, cost, lens = nothing; extra = nothing, want_grad = true,
+                want_gamma = false) -> (risk, diff, post, logz, grad, gamma)
+
+Lattice expected cost (mm_latticecost_f32 in the header): the expectation of the summed `cost` of a path's records over the paths of
+a lattice, weighed as `latticeposteriors` weighs them, and its gradient (lattice-based sMBR / MPE).  `risk` (B), `diff[r]` the
+gradient against `extra`, `post` and `logz` those of `latticeposteriors`, `grad` (`P × N × B`) the gradient against `V`, `gamma` the
+pdf occupancies (`nothing` when not asked for); `exp.(post)` is the gradient against `cost`.
+"""
+function latticecost(b::ROCBatch{K}, V::ROCArray{Float32,3}, offsets::AbstractVector{<:Integer}, arc::AbstractVector{<:Integer},
+                     cost::AbstractVector{<:Real}, lens = nothing; extra = nothing, want_grad::Bool = true,
+                     want_gamma::Bool = false) where K <: TropicalSemiring
+    P, N, B = size(V)
+    length(offsets) == N * B + 1 || throw(DimensionMismatch("offsets must have N·B + 1 = $(N * B + 1) entries"))
+    n = length(arc)
+    offsets[end] <= n || throw(ArgumentError("the lattice has $(offsets[end]) records, arc holds $n"))
+    length(cost) == n || throw(DimensionMismatch("cost must hold one cost per record ($n)"))
+    extra === nothing || length(extra) == n || throw(DimensionMismatch("extra must hold one score per record ($n)"))
+    offs = ROCArray(Int64.(collect(offsets)))
+    arcd = ROCArray(Int32.(collect(arc)) .- Int32(1))
+    cs = ROCArray(Float32.(collect(cost)))
+    ex = extra === nothing ? nothing : ROCArray(Float32.(collect(extra)))
+    risk = ROCArray{Float32}(undef, B)
+    diff = ROCArray{Float32}(undef, n)
+    post = ROCArray{Float32}(undef, n)
+    logz = ROCArray{Float32}(undef, B)
+    grad = want_grad ? ROCArray{Float32}(undef, P, N, B) : nothing
+    gamma = want_gamma ? ROCArray{Float32}(undef, P, N, B) : nothing
+    lp = lens === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(lens))
+    check(ccall((:mm_latticecost_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Int64}, Ptr{Int32}, Int64, Ptr{Float32}, Ptr{Float32}, Ptr{Float32},
+         Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Ptr{Float32}, Int64, Int64, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, lp, N, pointer(offs), pointer(arcd), n, ex === nothing ? Ptr{Float32}(C_NULL) : pointer(ex),
+        pointer(cs), pointer(risk), pointer(diff), pointer(post), pointer(logz), grad === nothing ? Ptr{Float32}(C_NULL) : pointer(grad),
+        gamma === nothing ? Ptr{Float32}(C_NULL) : pointer(gamma), P * N, P, AMDGPU.stream().stream))
+    Array(risk), Array(diff), Array(post), Array(logz), grad === nothing ? nothing : Array(grad), gamma === nothing ? nothing : Array(gamma)
 end
 
 """

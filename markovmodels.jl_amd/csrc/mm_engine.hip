@@ -571,6 +571,8 @@ static bool lattice_global(mm_batch_t h) { return h->dbg.bigv || mm_lattice_lds_
 // mm_latticeposteriors_f32: the workgroup of its forward-backward, and the states its three per-state LDS arrays hold
 static int latpost_nt(mm_batch_t h) { return h->dbg.latpost_nt ? h->dbg.latpost_nt : MM_LATPOST_NT; }
 static int64_t latpost_state_cap() { return int64_t((MM_LDS_MAX - mm_latpost_lds_bytes(0)) / (mm_latpost_lds_bytes(1) - mm_latpost_lds_bytes(0))); }
+// mm_latticecost_f32: the same workgroup, five per-state LDS arrays
+static int64_t latcost_state_cap() { return int64_t((MM_LDS_MAX - mm_latcost_lds_bytes(0)) / (mm_latcost_lds_bytes(1) - mm_latcost_lds_bytes(0))); }
 
 // item / tropical kernels: `kernel` keeps the state vectors in LDS; `big` is the same kernel with the vectors in global
 // memory, for FSMs beyond the LDS (the reference has no size limit: src/linalg.jl:170-181)
@@ -2843,6 +2845,13 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
             "the records of each cell, state vectors in LDS, integer max and 64-bit fixed-point sums) + mm_latpost_gamma_kernel<" +
             std::to_string(MM_LATPOST_GAMMA_NT) + "> (one workgroup per utterance and frame, when gamma is asked for); state cap " + std::to_string(latpost_state_cap());
         if (mm_latpost_lds_bytes(h->max_S1p) > MM_LDS_MAX) s += "; " + std::to_string(h->max_S1p) + " states exceed the cap";
+    } else if (entry == 20) {  // mm_latticecost_f32
+        if (h->semiring != MM_TROPICAL) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_latticecost_f32 runs on tropical batches only");
+        s = "mm_latcost_fb_kernel<" + std::to_string(latpost_nt(h)) + "> (one workgroup per utterance, serial over the transitions: mm_latpost_fb_kernel's "
+            "forward-backward with the cost recursions beside it, signed 64-bit fixed-point cost sums, " + std::to_string(mm_latcost_lds_bytes(1) - mm_latcost_lds_bytes(0)) +
+            " bytes of LDS per state) + mm_latcost_grad_kernel<" + std::to_string(MM_LATPOST_GAMMA_NT) +
+            "> (one workgroup per utterance and frame, when grad or gamma is asked for); state cap " + std::to_string(latcost_state_cap());
+        if (mm_latcost_lds_bytes(h->max_S1p) > MM_LDS_MAX) s += "; " + std::to_string(h->max_S1p) + " states exceed the cap";
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -4835,6 +4844,52 @@ int mm_latticeposteriors_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t 
     lp.gsb = gsb;
     lp.gsn = gsn;
     return mm_launch_latpost(h->B, nt, h->max_S1p, h->max_P1, p, lp, static_cast<hipStream_t>(stream));
+}
+
+// ---- lattice expected cost (mm_kernel_latpost.hip, the instance with costs): the risk of a lattice's paths and its gradient
+int mm_latticecost_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, const int64_t *offsets,
+                       const int32_t *arc, int64_t nrec, const float *extra, const float *cost, float *risk, float *diff, float *post, float *logz,
+                       float *grad, float *gamma, int64_t gsb, int64_t gsn, void *stream) {
+    const std::string who = "mm_latticecost_f32";
+    // what the arguments alone show comes first, then the batch's refusals
+    if (!offsets || !logz || !risk) return fail(MM_ERR_INVALID, who + ": offsets/logz/risk is NULL");
+    if (nrec < 0) return fail(MM_ERR_INVALID, who + ": nrec must be >= 0");
+    if (nrec > 0 && (!arc || !post || !cost || !diff)) return fail(MM_ERR_INVALID, who + ": arc/cost/diff/post is NULL with nrec > 0");
+    if ((grad || gamma) && (gsn < 1 || gsb < N * gsn)) return fail(MM_ERR_DIM, who + ": stride_n < 1 or stride_b < N * stride_n");
+    if (h && h->semiring != MM_TROPICAL)
+        return fail(MM_ERR_UNSUPPORTED, who + ": tropical batches only (this batch is " + (h->semiring == MM_LOG ? "log-semiring" : "ProbSemiring") + ")");
+    int rc = check_run(h, who.c_str(), V, N, MM_TROPICAL);
+    if (rc) return rc;
+    if ((grad || gamma) && gsn < h->max_P1 - 1) return fail(MM_ERR_DIM, who + ": stride_n < P");
+    if (h->B * N > int64_t(INT32_MAX)) return fail(MM_ERR_UNSUPPORTED, who + ": B * N exceeds 2^31 - 1 workgroups");
+    if (mm_latcost_lds_bytes(h->max_S1p) > MM_LDS_MAX)
+        return fail(MM_ERR_UNSUPPORTED, who + ": " + std::to_string(h->max_S1p) + " states (padded) exceed the " + std::to_string(latcost_state_cap()) +
+                                            " whose vectors fit the LDS (" + std::to_string(mm_latcost_lds_bytes(1) - mm_latcost_lds_bytes(0)) + " bytes per state)");
+    if ((grad || gamma) && mm_latcost_grad_lds_bytes(h->max_P1) > MM_LDS_MAX)
+        return fail(MM_ERR_UNSUPPORTED, who + ": too many pdfs for the LDS: " + std::to_string(h->max_P1));
+    const int nt = latpost_nt(h);
+    if (nt != 256 && nt != 512 && nt != 1024) return fail(MM_ERR_INVALID, who + ": MM_LATPOST_NT must be 256, 512 or 1024");
+    rc = ensure_item_forms(h, stream);
+    if (!rc) rc = ensure_lattice_arcs(h, stream);
+    if (rc) return rc;
+    const RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    LatPostParams lp{};
+    lp.arcs = static_cast<const LatticeDev *>(h->d_lat.get());
+    lp.offs = reinterpret_cast<const long long *>(offsets);
+    lp.arc = arc;
+    lp.nrec = nrec;
+    lp.extra = extra;
+    lp.post = post;
+    lp.logz = logz;
+    lp.gamma = gamma;
+    lp.gsb = gsb;
+    lp.gsn = gsn;
+    LatCostParams lc{};
+    lc.cost = cost;
+    lc.risk = risk;
+    lc.diff = diff;
+    lc.grad = grad;
+    return mm_launch_latcost(h->B, nt, h->max_S1p, h->max_P1, p, lp, lc, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

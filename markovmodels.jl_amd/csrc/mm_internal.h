@@ -503,6 +503,20 @@ int mm_launch_latpost(int64_t B, int nt, int max_S1p, int max_P1, const RunParam
 size_t mm_latpost_lds_bytes(int S1p);       // a head + 16 bytes per state: two 32-bit words and a 64-bit sum
 size_t mm_latpost_gamma_lds_bytes(int P1);  // a 64-bit sum per pdf
 
+// ---- lattice expected cost (mm_latcost_tu.hip: mm_latcost_fb_kernel, the forward-backward of the lattice posteriors with the cost
+// recursions ca / cb carried beside a / b, and mm_latcost_grad_kernel, the per-pdf sums of diff and of exp(post))
+struct LatCostParams {       // beside a LatPostParams, whose gamma / gsb / gsn serve grad too
+    const float *cost;       // [nrec]
+    float *risk;             // [B]
+    float *diff;             // [nrec]; between the passes the record's centred forward cost
+    float *grad;             // NULL: not computed; row (b, n) at b * gsb + n * gsn
+};
+// the forward-backward with costs in its instance of `nt` threads, then the per-pdf sums when lc.grad or lp.gamma is given
+int mm_launch_latcost(int64_t B, int nt, int max_S1p, int max_P1, const RunParams &p, const LatPostParams &lp, const LatCostParams &lc,
+                      hipStream_t stream);
+size_t mm_latcost_lds_bytes(int S1p);      // a head + 28 bytes per state: the 16 of the posteriors, a 64-bit cost sum and a float
+size_t mm_latcost_grad_lds_bytes(int P1);  // a head + two 64-bit sums per pdf
+
 // ---- posteriors with call-time arc weights (mm_weighted_tu.hip: mm_weights_kernel, mm_log_kernel's forward half on the call's
 // descriptors, mm_weighted_bwd_kernel and mm_weighted_scatter_kernel on the item form)
 struct UttDesc;  // mm_kernels.hip

@@ -169,6 +169,20 @@ class LatticePosteriors(NamedTuple):
     gamma: object
 
 
+class LatticeCost(NamedTuple):
+    """What ``BatchedFSM.latticecost`` returns.  ``risk[B]``: the expected cost of the lattice's paths (0: no path); ``diff`` float32,
+    one per record: d risk / d extra, the record's posterior times (the expected cost of the paths through it - risk); ``post`` and
+    ``logz`` as in ``LatticePosteriors`` (``exp(post)`` is d risk / d cost); ``grad[B, N, P]``: d risk / d V; ``gamma[B, N, P]``: the
+    pdf occupancies (either None when not asked for)."""
+
+    risk: object
+    diff: object
+    post: object
+    logz: object
+    grad: object
+    gamma: object
+
+
 def _on_device(x, dtype, device):
     """A member of a lattice (or ``extra``) as a contiguous tensor of ``dtype`` on ``device``: a tensor, or anything NumPy reads."""
     import torch
@@ -1021,11 +1035,11 @@ class BatchedFSM:
         leakyposteriors, "entropy" = pathentropy, "filter" = filterposteriors, "window" = windowposteriors,
         "vitwindow" = viterbiwindow (tropical batches), "weighted" = weightedposteriors, "segment" = segmentposteriors,
         "classpath" = classpath (tropical batches), "lattice" = lattice (tropical batches), "latticeposteriors" = latticeposteriors
-        (tropical batches)."""
+        (tropical batches), "latticecost" = latticecost (tropical batches)."""
         import ctypes
 
         buf = ctypes.create_string_buffer(1024)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13, "arcclass": 14, "scored": 15, "classcost": 16, "classpath": 17, "lattice": 18, "latticeposteriors": 19}[semiring], buf, 1024))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13, "arcclass": 14, "scored": 15, "classcost": 16, "classpath": 17, "lattice": 18, "latticeposteriors": 19, "latticecost": 20}[semiring], buf, 1024))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -1176,6 +1190,46 @@ class BatchedFSM:
                                            logz.data_ptr(), _ptr(gamma), gamma.stride(0) if want_gamma else 0, gamma.stride(1) if want_gamma else 0,
                                            self._stream(torch)))
         return LatticePosteriors(*_results((post, logz, gamma), as_numpy))
+
+    def latticecost(self, lat, V, cost, lens=None, extra=None, want_grad=True, want_gamma=False):
+        """Lattice expected cost (mm_latticecost_f32): the expectation of ``A(path) = sum of cost[r]`` over the paths of ``lat``,
+        weighed as ``latticeposteriors`` weighs them under ``V`` and ``extra``, and its gradient -- lattice-based sMBR / MPE.
+        ``cost`` is one float32 per record, finite.  Returns ``LatticeCost(risk, diff, post, logz, grad, gamma)``: ``risk[B]`` (0 for
+        an utterance without a path), ``diff`` per record = d risk / d extra, ``post`` / ``logz`` / ``gamma`` bit for bit those of
+        ``latticeposteriors``, ``grad[B, N, P]`` = d risk / d V (``want_grad=False`` / ``want_gamma=False``: None; with both off the
+        second kernel does not run); ``exp(post)`` is d risk / d cost.  Inputs and results as ``latticeposteriors`` handles them,
+        its ValueError for a lattice cut by ``max_arcs`` included.  Bit-identical from call to call.  Tropical batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        dev = Vt.device
+        offsets = _on_device(lat.offsets, torch.int64, dev)
+        arc = _on_device(lat.arc, torch.int32, dev)
+        if offsets.dim() != 1 or offsets.numel() != B * N + 1:
+            raise _lib.DimensionMismatch(-2, f"lat.offsets must be [B * N + 1 = {B * N + 1}], got {tuple(offsets.shape)}")
+        nrec = arc.numel()
+        if arc.dim() != 1:
+            raise _lib.DimensionMismatch(-2, f"lat.arc must be a vector, got {tuple(arc.shape)}")
+        ct = _on_device(cost, torch.float32, dev)
+        if ct.dim() != 1 or ct.numel() != nrec:
+            raise _lib.DimensionMismatch(-2, f"cost must be [{nrec}], one cost per record, got {tuple(ct.shape)}")
+        et = None
+        if extra is not None:
+            et = _on_device(extra, torch.float32, dev)
+            if et.dim() != 1 or et.numel() != nrec:
+                raise _lib.DimensionMismatch(-2, f"extra must be [{nrec}], one score per record, got {tuple(et.shape)}")
+        if not torch.cuda.is_current_stream_capturing():
+            total = int(offsets[-1].item())
+            if total > nrec:
+                raise ValueError(f"latticecost: the lattice has {total} records, lat.arc holds {nrec} (max_arcs cut it)")
+        risk = torch.empty(B, dtype=torch.float32, device=dev)
+        diff = torch.empty(nrec, dtype=torch.float32, device=dev)
+        post = torch.empty(nrec, dtype=torch.float32, device=dev)
+        logz = torch.empty(B, dtype=torch.float32, device=dev)
+        grad = torch.empty((B, N, P), dtype=torch.float32, device=dev) if want_grad else None
+        gamma = torch.empty((B, N, P), dtype=torch.float32, device=dev) if want_gamma else None
+        check(lib.mm_latticecost_f32(*_head(self._h, Vt, lt, N), offsets.data_ptr(), arc.data_ptr(), nrec, _ptr(et), ct.data_ptr(), risk.data_ptr(),
+                                     diff.data_ptr(), post.data_ptr(), logz.data_ptr(), _ptr(grad), _ptr(gamma), N * P, P, self._stream(torch)))
+        return LatticeCost(*_results((risk, diff, post, logz, grad, gamma), as_numpy))
 
     def totalsum(self, n: int, cumulative: bool = False):
         """Per FSM of the batch: omega . v_n (totalsum) or the semiring sum over k <= n of omega . v_k
@@ -1680,6 +1734,17 @@ def latticeposteriors(fsm, lat, Vhats, Chats=None, extra=None):
         raise TypeError("latticeposteriors needs TropicalSemiring FSMs")
     V, lens = _need_expanded(Vhats)
     return bf.latticeposteriors(lat, V, lens, extra)
+
+
+def latticecost(fsm, lat, Vhats, cost, Chats=None, extra=None):
+    """Lattice expected cost -- see ``BatchedFSM.latticecost`` -- in ``lattice``'s call shape: the ``LatticeCost`` (NumPy members, with
+    ``grad``, without ``gamma``) of the lattice ``lat`` of the batch under the expanded emissions ``Vhats`` and the per-record costs
+    ``cost``.  Tropical FSMs."""
+    bf = _as_batch(fsm, Chats)
+    if bf.semiring != "tropical":
+        raise TypeError("latticecost needs TropicalSemiring FSMs")
+    V, lens = _need_expanded(Vhats)
+    return bf.latticecost(lat, V, cost, lens, extra)
 
 
 def _total(fsm, n, cumulative):

@@ -12,9 +12,23 @@ per record in ``extra`` -- b times the record's phone or state error against the
     d logz_b / d V[b, n, p] = gamma[b, n, p]         (the pdf occupancies of the lattice)
     d logz_b / d extra[r]   = exp(post[r])           (the record's posterior; r a record of utterance b)
 
+and the expected cost of its paths,
+
+    risk_b = sum_{path} exp(W(path) - logz_b) A(path),   A(path) = sum of cost[r] over the path's records
+
+(mm_latticecost_f32), the lattice form of ``mbr.expected_cost``: with the cost of a record minus the phone or word accuracy of its arc
+it is MPE / MWE (Povey 2003), with minus [pdf of the record's source = the alignment's pdf at that frame] state-level MBR
+(``lattice_smbr_loss``; Vesely et al., "Sequence-discriminative training of deep neural networks", Interspeech 2013).
+
+    d risk_b / d V[b, n, p] = grad[b, n, p]       d risk_b / d extra[r] = diff[r]       d risk_b / d cost[r] = exp(post[r])
+
 A launch chain on the caller's stream.
 """
 from __future__ import annotations
+
+from typing import NamedTuple
+
+import numpy as np
 
 
 def _function():
@@ -52,3 +66,126 @@ def lattice_loglik(bf, lat, V, extra=None, lens=None):
     hands ``gamma[b] * g[b]`` to ``V`` and ``exp(post[r]) * g[b(r)]`` to ``extra``.  Utterances without a path have ``logz = -inf``
     and zero gradients; they are the caller's to filter, as in ``lfmmi_loss``.  ``bf``: a tropical ``BatchedFSM``."""
     return _function().apply(V, extra, bf, lat, lens)
+
+
+def _owner(offsets, nrec, B, N):
+    """The utterance of every record: the last b with offsets[b * N] <= r."""
+    import torch
+
+    r = torch.arange(nrec, device=offsets.device, dtype=offsets.dtype)
+    return (torch.searchsorted(offsets[::N][:B].contiguous(), r, right=True) - 1).clamp_(0, B - 1)
+
+
+def _risk_function():
+    import torch
+
+    class _LatticeRisk(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, V, extra, cost, batch, lat, lens):
+            res = batch.latticecost(lat, V.detach(), cost.detach(), lens, None if extra is None else extra.detach(), want_grad=True)
+            offsets = lat.offsets if isinstance(lat.offsets, torch.Tensor) else torch.as_tensor(lat.offsets)
+            ctx.save_for_backward(res.diff, res.post, res.logz, res.grad, offsets.to(V.device))
+            ctx.has_extra = extra is not None
+            return res.risk
+
+        @staticmethod
+        def backward(ctx, g):
+            diff, post, logz, grad, offsets = ctx.saved_tensors
+            B, N = grad.shape[0], grad.shape[1]
+            w = torch.where(torch.isneginf(logz), torch.zeros_like(g), g)  # (no path: every gradient is 0, and g may be anything)
+            gV = grad * w[:, None, None] if ctx.needs_input_grad[0] else None
+            gE = gC = None
+            if (ctx.has_extra and ctx.needs_input_grad[1]) or ctx.needs_input_grad[2]:
+                wr = w[_owner(offsets, post.numel(), B, N)]
+                if ctx.has_extra and ctx.needs_input_grad[1]:
+                    gE = diff * wr
+                if ctx.needs_input_grad[2]:
+                    gC = torch.exp(post) * wr
+            return gV, gE, gC, None, None, None
+
+    return _LatticeRisk
+
+
+def lattice_risk(bf, lat, V, cost, extra=None, lens=None):
+    """``risk[B]``, the expected cost of the paths of the lattice ``lat`` (a ``Lattice`` of ``bf.lattice``, or a subset of one) under
+    ``V`` [B, N, P] float32 on the HIP device, the per-record costs ``cost`` and the optional per-record scores ``extra`` (float32
+    tensors of one value per record), all three differentiable: backward hands ``grad[b] * g[b]`` to ``V``, ``diff[r] * g[b(r)]`` to
+    ``extra`` and ``exp(post[r]) * g[b(r)]`` to ``cost``.  Utterances without a path have risk 0 and zero gradients, as in
+    ``lattice_loglik``.  ``bf``: a tropical ``BatchedFSM``."""
+    return _risk_function().apply(V, extra, cost, bf, lat, lens)
+
+
+class RecordIndex(NamedTuple):
+    """Per record of a lattice, int64 tensors: its utterance ``b``, its transition ``t`` and the pdf of its source state ``pdf``
+    (``P``, the phony pdf, for an entry outside the FSM and for records no cell covers); ``P`` itself."""
+
+    b: object
+    t: object
+    pdf: object
+    P: int
+
+
+def _host(x):
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+
+def record_index_host(fsms, state2pdfs, P, offsets, arc):
+    """``record_index`` on host arrays: ``fsms[b]`` / ``state2pdfs[b]`` the FSM and the pdf per real state of utterance b; NumPy
+    int64 arrays ``(b, t, pdf)``."""
+    from .fsm import _entry_ends
+
+    offsets, arc = np.asarray(offsets, dtype=np.int64), np.asarray(arc, dtype=np.int64)
+    B = len(fsms)
+    N = (offsets.size - 1) // B
+    nrec = arc.size
+    off = np.maximum.accumulate(np.clip(offsets, 0, nrec))
+    cell = np.searchsorted(off, np.arange(nrec), side="right") - 1  # the last cell that starts at or before r
+    covered = (cell >= 0) & (cell < B * N)
+    cell = np.clip(cell, 0, B * N - 1)
+    bi, ti = cell // N, cell % N
+    pdf = np.full(nrec, P, dtype=np.int64)
+    for b in range(B):
+        src, _ = _entry_ends(fsms[b])
+        s2p = np.concatenate([np.asarray(state2pdfs[b], dtype=np.int64).ravel()[: fsms[b].S1 - 1], [P]])
+        m = covered & (bi == b) & (arc >= 0) & (arc < src.size)
+        pdf[m] = s2p[src[arc[m]]]
+    return bi.astype(np.int64), ti.astype(np.int64), pdf
+
+
+def record_index(bf, lat):
+    """Per record of ``lat`` its utterance, its transition and the pdf of its source state: a ``RecordIndex`` of int64 tensors on the
+    device of ``lat.arc`` (the host for NumPy members), built once per lattice on the host from the FSMs' entry lists as
+    ``decode.lattice_arcs`` reads them."""
+    import torch
+
+    bi, ti, pdf = record_index_host([c.fsm for c in bf.cfsms], [c.C_hat.state2pdf for c in bf.cfsms], bf.P, _host(lat.offsets), _host(lat.arc))
+    dev = lat.arc.device if isinstance(lat.arc, torch.Tensor) else torch.device("cpu")
+    return RecordIndex(*(torch.as_tensor(x).to(dev) for x in (bi, ti, pdf)), bf.P)
+
+
+def pdf_costs(index, D):
+    """Frame costs on records: ``D[b, t, pdf]`` [B, N, P] gathered by a ``RecordIndex`` (or a ``(b, t, pdf)`` triple), one gather,
+    differentiable in a tensor ``D``; the phony pdf ``P`` costs 0.  It puts ``expected_cost``'s frame costs, such as sMBR's
+    ``-[pdf = alignment]``, onto the records of a lattice."""
+    bi, ti, pdf = index[0], index[1], index[2]
+    if hasattr(D, "detach"):
+        import torch
+
+        Dp = torch.nn.functional.pad(D, (0, 1))
+        dev = D.device
+        return Dp[torch.as_tensor(bi).to(dev), torch.as_tensor(ti).to(dev), torch.as_tensor(pdf).to(dev)]
+    D = np.asarray(D)
+    Dp = np.concatenate([D, np.zeros(D.shape[:2] + (1,), dtype=D.dtype)], axis=2)
+    return Dp[_host(bi), _host(ti), _host(pdf)]
+
+
+def lattice_smbr_loss(bf, lat, V, ali, lens=None, index=None):
+    """State-level MBR on a lattice: ``risk[B]`` with the cost of a record ``-[pdf of its source = ali[b, t]]``, so the risk is minus
+    the expected number of frames (of the ``len``) on which the lattice's paths agree with the alignment ``ali`` [B, N] (pdf
+    indices), between ``-len`` and 0.  Differentiable in ``V``.  ``index``: ``record_index(bf, lat)`` when the caller keeps it."""
+    import torch
+
+    index = record_index(bf, lat) if index is None else index
+    a = torch.as_tensor(ali).to(V.device).long()
+    D = -torch.nn.functional.one_hot(a.clamp(0, index.P - 1), index.P).to(torch.float32) * (a >= 0)[..., None]
+    return lattice_risk(bf, lat, V, pdf_costs(index, D).to(V.device), lens=lens)
