@@ -1197,6 +1197,12 @@ int mm_debug_packed_product(mm_fsm_t fsm, int direction, const float *in, float 
  * gather instruction with arcs in CSR order, the same after the bank-aware placement}. */
 int mm_debug_quad_product(mm_fsm_t fsm, int direction, int KQ, const float *in, float *out, double stats[4]);
 
+/* Test aid (host only, no GPU): where the quad form for KQ quads per lane puts every row.  order[S1]: internal position ->
+ * state of the direction's numbering; recs[4 * S1]: per position the row record the kernel reads, {qe, i1, pdf, i2} -- 2 + the
+ * row's last quad (0: a row without arcs), 2 + its first lane-end quad before that (or 0), its pdf, 2 + the second lane end (0:
+ * none, 1: more than two -- the long walk i1, i1 + KQ, ... < qe).  MM_LOG FSMs only. */
+int mm_debug_quad_layout(mm_fsm_t fsm, int direction, int KQ, int32_t *order, uint16_t *recs);
+
 /* Test aid (host only, no GPU): the same product evaluated THROUGH THE ROW-LANE FORM of the row kernels (mm_rows.h:
  * rows sorted by size and dealt to the compute waves as segments, arcs in per-lane register slots, group sums,
  * internal numbering = finishing order), in the linear domain relative to max(in) like the kernels do.  MM_LOG FSMs

@@ -84,6 +84,7 @@ SYMBOLS = [
     "mm_allgather_ttl",
     "mm_debug_packed_product",
     "mm_debug_quad_product",
+    "mm_debug_quad_layout",
     "mm_debug_row_product",
     "mm_debug_row_product_ex",
     "mm_debug_split_product",
@@ -244,6 +245,8 @@ def _load():
     lib.mm_debug_reach_distance.argtypes = [vp, C.c_int, vp]
     lib.mm_debug_quad_product.restype = C.c_int
     lib.mm_debug_quad_product.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
+    lib.mm_debug_quad_layout.restype = C.c_int
+    lib.mm_debug_quad_layout.argtypes = [vp, C.c_int, C.c_int, vp, vp]
     lib.mm_debug_row_product.restype = C.c_int
     lib.mm_debug_row_product.argtypes = [vp, C.c_int, vp, vp, vp]
     lib.mm_debug_wave_product.restype = C.c_int

@@ -851,7 +851,7 @@ static int fsm_create_impl(int semiring, int64_t S1, int64_t nnz, int layout, in
     f->S1 = S1;
     f->nnz = nnz;
     f->P1 = P1;
-    f->S1p = int((S1 + 1 + 3) / 4 * 4);  // at least one slot beyond the last state (the row kernels' "no row" position)
+    f->S1p = padded_states(S1);  // at least one slot beyond the last state (the row kernels' "no row" position)
     f->s2p.resize(S1);
     for (int64_t s = 0; s < S1; ++s) {
         int32_t pdf = state2pdf[s] - index_base;
@@ -1725,6 +1725,23 @@ int mm_debug_quad_product(mm_fsm_t f, int direction, int KQ, const float *in, fl
     return MM_OK;
 }
 
+int mm_debug_quad_layout(mm_fsm_t f, int direction, int KQ, int32_t *order, uint16_t *recs) {
+    if (!f || !order || !recs || direction < 0 || direction > 1 || KQ < 1 || KQ > 32)
+        return fail(MM_ERR_INVALID, "mm_debug_quad_layout: bad argument");
+    if (f->semiring != MM_LOG) return fail(MM_ERR_INVALID, "mm_debug_quad_layout: log-semiring FSMs only");
+    const Csr &m = f->mat[direction];
+    const QuadGraph g = make_quads(f->S1, m.rowptr, m.col, m.val, f->s2p, f->P1, direction == 1, KQ);
+    for (int64_t i = 0; i < f->S1; ++i) {
+        order[i] = g.order[size_t(i)];
+        const RowRec &r = g.recs[size_t(i)];
+        recs[4 * i + 0] = r.qe;
+        recs[4 * i + 1] = r.i1;
+        recs[4 * i + 2] = r.pdf;
+        recs[4 * i + 3] = r.i2;
+    }
+    return MM_OK;
+}
+
 int mm_debug_row_product(mm_fsm_t f, int direction, const float *in, float *out, double stats[8]) {
     return mm_debug_row_product_ex(f, direction, 0, in, out, stats);
 }
@@ -2312,7 +2329,8 @@ static int batch_create_impl(const mm_fsm_t *fsms, int64_t B, mm_batch_t *out) {
     if (h->fast_ok) {
         for (int d = 0; d < 2; ++d) {
             QuadGeometry geo = pick_quad_geometry(nq_max[d]);
-            if (h->dbg.kq >= 1 && h->dbg.kq <= 29) geo.KQ = h->dbg.kq;
+            // (MM_KQ: a value without a kernel instance -- 4, 8, 12, 14, 16, ... -- is ignored, not left to fail at the launch)
+            if (quad_kq_has_instance(h->dbg.kq)) geo.KQ = h->dbg.kq;
             // enough waves for the quads, and for at most two rows per thread where the workgroup can be that large
             geo.NW = int(std::min<int64_t>(geo.KQ > 13 ? 8 : MM_MAX_WAVES,
                                            std::max<int64_t>({1, (nq_max[d] + 64 * geo.KQ - 1) / (64 * geo.KQ),
@@ -2625,7 +2643,13 @@ static std::string wave_instance(mm_batch_t h) {
 
 static std::string fb_kernels(mm_batch_t h) {
     // what fb_exact runs, and (`redo`) what the families that hand their marked utterances to redo_on_items run
-    const std::string quad = "mm_fbq_kernel<" + std::to_string(h->geo_kq[0]) + ",*,0> + mm_fbq_kernel<" + std::to_string(h->geo_kq[1]) + ",*,1>";
+    auto quad_instance = [&](int d) {  // (RPT as launch_quad_kq of mm_quad_tu.hip derives it)
+        const int NT = 64 * h->geo_nw[d], rpt = (h->max_S1p + NT - 1) / NT <= 2 ? 2 : 3;
+        return "mm_fbq_kernel<" + std::to_string(h->geo_kq[d]) + "," + std::to_string(rpt) + "," + std::to_string(d) + "> x " +
+            std::to_string(h->geo_nw[d]) + " waves";
+    };
+    // (which body of the exact fallback: the CSR it walks is staged in LDS for KQ <= 3 where it fits, see mm_batch_create)
+    const std::string quad = quad_instance(0) + " + " + quad_instance(1) + (h->xcsr > 0 ? " (fallback CSR in LDS)" : " (fallback CSR in global memory)");
     const std::string exact = h->quad_ok ? quad : item_fb_kernels(h, false);
     const std::string redo = item_fb_kernels(h, true);
     const std::string pair_tail = h->dpair_ok && !h->quad_ok ? redo : exact;

@@ -100,14 +100,21 @@ Packed pack_rows(int64_t nrows, const std::vector<int64_t> &rowptr, const std::v
     return out;
 }
 
+// (mm_pack.h: the lists the launch table of the quad kernels is generated from)
+#define MM_KQ_ITEM(k) k,
+static const int kq16[] = {MM_QUAD_KQ_16WAVES(MM_KQ_ITEM)};
+static const int kq8[] = {MM_QUAD_KQ_8WAVES(MM_KQ_ITEM)};
+#undef MM_KQ_ITEM
+
+bool quad_kq_has_instance(int KQ) {
+    for (int k : kq16)
+        if (k == KQ) return true;
+    for (int k : kq8)
+        if (k == KQ) return true;
+    return false;
+}
+
 QuadGeometry pick_quad_geometry(int64_t nquads) {
-    // KQ multiples of 4 are avoided: lane tid stores its quad sums at tid * KQ + j, and
-    // a stride that is a multiple of 4 dwords makes those stores 4-way bank conflicted.
-    // Up to 13 quads per lane fit the 128-VGPR budget of 16 waves per CU; larger graphs use
-    // 8 waves with twice the registers (measured on the 3032-state WSJ graph: 7.9 ms against
-    // 10.7 ms for 16 waves with a streamed overflow).
-    static const int kq16[] = {1, 2, 3, 5, 6, 7, 9, 10, 11, 13};
-    static const int kq8[] = {15, 17, 19, 21, 23, 25, 27, 29};
     QuadGeometry g{29, 8};
     bool found = false;
     for (int k : kq16)
@@ -268,7 +275,7 @@ QuadGraph make_quads(int64_t nrows, const std::vector<int64_t> &rowptr, const st
                      int KQ) {
     QuadGraph g;
     g.KQ = KQ;
-    const int S1p = int((nrows + 3) / 4 * 4);
+    const int S1p = padded_states(nrows);  // (the kernels' own: they write the copies of p at quad_pstride(S1p))
     g.ncopy = quad_ncopy(S1p);
     const int pstride = quad_pstride(S1p, g.ncopy);
     auto nq_of = [&](int64_t r) { return (rowptr[r + 1] - rowptr[r] + 3) / 4; };

@@ -98,14 +98,29 @@ static_assert(sizeof(RowRec) == 8, "RowRec must be 8 bytes");
 #else
 #define MM_HD
 #endif
+// S1p, the padded length of a state vector in the kernels: at least one slot beyond the last state (the row kernels' "no row"
+// position), a multiple of 4.  The engine (mm_fsm_s::S1p, what the kernels lay their LDS out by) and make_quads() (the offsets of
+// the second copy of p, quad_pstride(S1p) floats behind the first) both take it from here.
+MM_HD inline int padded_states(long long S1) { return int((S1 + 1 + 3) / 4 * 4); }
 MM_HD inline int quad_pstride(int S1p, int ncopy) { return (S1p + 31) / 32 * 32 + 32 / ncopy; }
 inline int quad_ncopy(int64_t S1p) { return 4 * (int64_t(quad_pstride(int(S1p), 2)) + S1p) <= 65535 ? 2 : 1; }
+
+// The quads per lane the quad kernels exist for: X(KQ) once per value, in ascending order.  The launch table of mm_quad_tu.hip (one
+// instance per value), pick_quad_geometry() and quad_kq_has_instance() are all generated from these two lists.
+// KQ multiples of 4 are avoided: lane tid stores its quad sums at tid * KQ + j, and a stride that is a multiple of 4 dwords makes
+// those stores 4-way bank conflicted.  Up to 13 quads per lane fit the 128-VGPR budget of 16 waves per CU; larger graphs use 8 waves
+// with twice the registers and twice the quads per lane (more gathers in flight; measured on the 3032-state WSJ graph: 7.9 ms against
+// 10.7 ms for 16 waves with a streamed overflow).
+#define MM_QUAD_KQ_16WAVES(X) X(1) X(2) X(3) X(5) X(6) X(7) X(9) X(10) X(11) X(13)
+#define MM_QUAD_KQ_8WAVES(X) X(15) X(17) X(19) X(21) X(23) X(25) X(27) X(29)
 
 struct QuadGeometry {
     int KQ;  // quads per lane held in registers
     int NW;  // wavefronts per workgroup
 };
 QuadGeometry pick_quad_geometry(int64_t nquads);
+// Is KQ on the lists above -- has the quad kernel an instance for it?
+bool quad_kq_has_instance(int KQ);
 
 struct QuadGraph {
     std::vector<int32_t> order;  // internal position -> original row

@@ -21,25 +21,12 @@ static int launch_quad_kq(const QuadLaunch *h, const RunParams &p, hipStream_t s
 template <int PASS>
 static int launch_quad_pass(const QuadLaunch *h, const RunParams &p, hipStream_t stream) {
     switch (h->kq) {
-        case 1: return launch_quad_kq<1, PASS>(h, p, stream);
-        case 2: return launch_quad_kq<2, PASS>(h, p, stream);
-        case 3: return launch_quad_kq<3, PASS>(h, p, stream);
-        case 5: return launch_quad_kq<5, PASS>(h, p, stream);
-        case 6: return launch_quad_kq<6, PASS>(h, p, stream);
-        case 7: return launch_quad_kq<7, PASS>(h, p, stream);
-        case 9: return launch_quad_kq<9, PASS>(h, p, stream);
-        case 10: return launch_quad_kq<10, PASS>(h, p, stream);
-        case 11: return launch_quad_kq<11, PASS>(h, p, stream);
-        case 13: return launch_quad_kq<13, PASS>(h, p, stream);
-        // 8-wave geometries: twice the quads per lane in twice the registers (more gathers in flight)
-        case 15: return launch_quad_kq<15, PASS>(h, p, stream);
-        case 17: return launch_quad_kq<17, PASS>(h, p, stream);
-        case 19: return launch_quad_kq<19, PASS>(h, p, stream);
-        case 21: return launch_quad_kq<21, PASS>(h, p, stream);
-        case 23: return launch_quad_kq<23, PASS>(h, p, stream);
-        case 25: return launch_quad_kq<25, PASS>(h, p, stream);
-        case 27: return launch_quad_kq<27, PASS>(h, p, stream);
-        case 29: return launch_quad_kq<29, PASS>(h, p, stream);
+        // one instance per KQ of the lists in mm_pack.h (what quad_kq_has_instance() answers by)
+#define MM_QUAD_CASE(k) \
+    case k: return launch_quad_kq<k, PASS>(h, p, stream);
+        MM_QUAD_KQ_16WAVES(MM_QUAD_CASE)
+        MM_QUAD_KQ_8WAVES(MM_QUAD_CASE)
+#undef MM_QUAD_CASE
         default: return MM_ERR_UNSUPPORTED;
     }
 }

@@ -285,6 +285,14 @@ class CompiledFSM:
         check(lib.mm_debug_quad_product(self._h, direction, KQ, x.ctypes.data, out.ctypes.data, stats.ctypes.data))
         return out, stats
 
+    def quad_layout(self, direction: int = 0, KQ: int = 5):
+        """Where the quad form puts every row (test aid).  Returns (order [S1]: internal position -> state, recs [S1, 4] uint16:
+        the row records {qe, i1, pdf, i2} the kernel reads, see mm_debug_quad_layout)."""
+        order = np.empty(self.S1, dtype=np.int32)
+        recs = np.empty((self.S1, 4), dtype=np.uint16)
+        check(lib.mm_debug_quad_layout(self._h, direction, KQ, order.ctypes.data, recs.ctypes.data))
+        return order, recs
+
 
     def row_product(self, x: np.ndarray, direction: int = 0, pair: bool = False, copies: int = 0, scrambled: bool = False, bank_opt: bool = False):
         """Host evaluation of the same product through the row-lane form of the row kernels, or its pair variant
