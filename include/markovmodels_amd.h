@@ -142,6 +142,8 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * names the state cap and says "exceed the cap" when the batch's largest FSM has more states.
  * 20 = mm_latticecost_f32 (tropical batches only): mm_latcost_fb_kernel<threads> + mm_latcost_grad_kernel<threads>; the text names
  * the bytes of LDS per state and the state cap, and says "exceed the cap" when the batch's largest FSM has more states.
+ * 21 = mm_latticebest_f32 (tropical batches only): mm_latbest_kernel<threads>; the text names the bytes of LDS per state and the
+ * state cap, and says "exceed the cap" when the batch's largest FSM has more states.
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -1002,6 +1004,61 @@ int mm_latticeposteriors_f32(mm_batch_t batch, const float *V, int64_t v_stride_
 int mm_latticecost_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
                        const int64_t *offsets, const int32_t *arc, int64_t nrec, const float *extra, const float *cost, float *risk,
                        float *diff, float *post, float *logz, float *grad, float *gamma, int64_t stride_b, int64_t stride_n, void *stream);
+
+/* Lattice best paths (MM_TROPICAL batches): the tropical twin of mm_latticeposteriors_f32 -- over the records of a lattice of
+ * mm_lattice_f32 (or a subset of one), under THIS call's emissions V and an optional extra score per record, the weight of the best
+ * path, how far below it the best path through every record lies, and the best path itself as records and as states.  It is the step
+ * behind a rescoring: the new one-best, the through-scores that re-prune the lattice to a narrower beam under the new scores, the
+ * target of a perceptron or max-margin loss.  Unlike the route over a lattice's graph it keeps parallel entries apart (it says WHICH
+ * record won) and takes a score per record.  Records, cells, offsets, arc, extra, dead records and W(path) are exactly those of
+ * mm_latticeposteriors_f32, i(r) / j(r) the source / destination of a record, f the phony final state.  In float32, in this
+ * grouping -- adds, one subtraction and a maximum, so nothing can contract:
+ *
+ *   wz_r        = (T_hat[arc[r]] + extra[r]) + e_{t+2}(j(r))     e_n(j): V[b, n-1, pdf(j)] for n <= len, 0 for j = f behind len,
+ *                                                                -inf otherwise; extra NULL: + 0
+ *   a_0(s)      = alpha_hat(s) + e_1(s)
+ *   f_r         = a_t(i(r)) + wz_r                               r in cell t
+ *   a_{t+1}(j)  = max_{r in cell t, j(r) = j} f_r
+ *   best[b]     = a_len(f)                                       (-inf: no path, len = 0 included)
+ *   b_len(f) = 0;   b_t(i) = max_{r in cell t, i(r) = i} (wz_r + b_{t+1}(j(r)))
+ *   score[r]    = (f_r + b_{t+1}(j(r))) - best[b]                -inf: no path through r, r dead, best = -inf, cell at or behind len
+ *   r_{len-1}   = the LOWEST live r of cell len-1 with j(r) = f and f_r = best
+ *   r_t         = the LOWEST live r of cell t with j(r) = i(r_{t+1}) and f_r = a_{t+1}(i(r_{t+1}))
+ *   rec[b, t]   = r_t, an index into arc;  path[b, t] = i(r_t), mm_viterbi_f32's convention (the 0-based state at frame t);
+ *                 both -1 for t >= len and for an utterance without a path
+ *
+ * The maximum and the equality are those of the floats' order with -0 below +0.  Consequences: (a) best is bit for bit the float32
+ * sum along the returned path in the recursion's order, a_0(path[b, 0]) then + wz of rec[b, 0], rec[b, 1], .., for any input: the
+ * maximum only selects among computed values.  (b) With extra NULL, the lattice's own V and exact inputs (multiples of 1/16 of
+ * moderate size) best and score are mm_lattice_f32's, bit for bit.  (c) On such inputs score[rec[b, t]] == 0 and every cell t < len
+ * of an utterance with a path has maximum 0.  (d) Where the best path is unique, path is mm_viterbi_f32's.  (e) extra[r] = -inf
+ * removes record r: rec never names it, or the utterance has no path.  (f) best <= logz of mm_latticeposteriors_f32 on the same
+ * inputs.  Nothing is NaN for inputs that are finite or -inf.  Integer maxima: a repeated call returns the same bits.
+ *
+ *   batch .. extra   as mm_latticeposteriors_f32
+ *   best         device float32[B], out.  NULL: MM_ERR_INVALID
+ *   score        device float32[nrec], out.  NULL with nrec > 0: MM_ERR_INVALID.  Between the passes it holds f_r
+ *   rec          device int64, out, or NULL (not computed): element (b, t) at rec[b*rec_stride_b + t], all N of every utterance
+ *                written.  rec_stride_b < N: MM_ERR_DIM
+ *   path         device int32, out, or NULL (not computed): element (b, t) at path[b*path_stride_b + t], likewise.
+ *                path_stride_b < N: MM_ERR_DIM
+ * Memory safety does not depend on the contents of the device arrays, by mm_latticeposteriors_f32's checks: a record whose entry is
+ * outside [0, nnz_b) or is the phony self-loop is dead, cells are clamped into [0, nrec] and made non-decreasing, lens into [0, N];
+ * records no cell covers are not written.
+ * Log and ProbSemiring batches: MM_ERR_UNSUPPORTED.  Argument errors that need no device are reported before the NULL-batch check.
+ * The state vectors live in LDS, 12 bytes per state: an FSM of more than about 13 600 states (padded) returns MM_ERR_UNSUPPORTED
+ * with the limit in the message; mm_batch_kernels(.., 21, ..) names it.
+ * Order of a call: mm_latbest_kernel alone (one workgroup per utterance, serial over its transitions, mm_latpost_fb_kernel's
+ * organisation with one pass and one barrier per step: three state vectors rotate -- read, accumulate by integer LDS maximum on the
+ * order-preserving code of the float, empty.  The forward pass parks f_r in score[r]; the backward pass overwrites it, and carries
+ * the trace: per step the 64-bit maximum of (code of f_r, 2^32 - 1 - place in the cell) over the records into the path's current
+ * state, by a wave reduction and one LDS atomic, so no back-pointer is ever stored; a doctored cell of 2^32 records or more falls
+ * back to an exact 64-bit minimum).  The work of a step is proportional to the records of its cell, not to the graph.
+ * No workspace.  Stream contract and graph capture: those of mm_latticeposteriors_f32 (a first call of any lattice entry puts the
+ * item forms and the arc table on the device); a replay after V, extra, offsets or arc were overwritten in place follows them. */
+int mm_latticebest_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                       const int64_t *offsets, const int32_t *arc, int64_t nrec, const float *extra, float *best, float *score,
+                       int64_t *rec, int64_t rec_stride_b, int32_t *path, int64_t path_stride_b, void *stream);
 
 /* totalsum(alpha, T, omega, n) / totalcumsum(alpha, T, omega, n) (src/algorithms.jl:8-29;
  * totalweightsum(fsm, n) = totalcumsum, :36), one value per FSM of the batch, in the batch's semiring

@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, set_arc_classes!, arc_class_info, arcclassposteriors, score_class_cap, scoredposteriors, cost_class_cap, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, set_path_classes!, path_class_info, classpath, lattice, latticeposteriors, latticecost, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, set_arc_classes!, arc_class_info, arcclassposteriors, score_class_cap, scoredposteriors, cost_class_cap, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, set_path_classes!, path_class_info, classpath, lattice, latticeposteriors, latticecost, latticebest, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -995,6 +995,39 @@ function latticecost(b::ROCBatch{K}, V::ROCArray{Float32,3}, offsets::AbstractVe
         pointer(cs), pointer(risk), pointer(diff), pointer(post), pointer(logz), grad === nothing ? Ptr{Float32}(C_NULL) : pointer(grad),
         gamma === nothing ? Ptr{Float32}(C_NULL) : pointer(gamma), P * N, P, AMDGPU.stream().stream))
     Array(risk), Array(diff), Array(post), Array(logz), grad === nothing ? nothing : Array(grad), gamma === nothing ? nothing : Array(gamma)
+end
+
+"""
+    latticebest(b::ROCBatch{<:TropicalSemiring}, V, offsets, arc, lens = nothing; extra = nothing, want_path = true)
+        -> (best, score, rec, path)
+
+Lattice best paths (mm_latticebest_f32 in the header), the tropical twin of `latticeposteriors`: `best` (B) the weight of the best
+path of the lattice under the emissions `V` of this call and the optional score `extra` per record, `score[r]` the best path through
+record r minus `best`, `rec` (`N × B`) the best path's record of every transition (1-based into `arc`, 0: none) and `path` (`N × B`)
+the source state of that record (1-based, 0: none); `nothing` for both without `want_path`.
+"""
+function latticebest(b::ROCBatch{K}, V::ROCArray{Float32,3}, offsets::AbstractVector{<:Integer}, arc::AbstractVector{<:Integer},
+                     lens = nothing; extra = nothing, want_path::Bool = true) where K <: TropicalSemiring
+    P, N, B = size(V)
+    length(offsets) == N * B + 1 || throw(DimensionMismatch("offsets must have N·B + 1 = $(N * B + 1) entries"))
+    n = length(arc)
+    offsets[end] <= n || throw(ArgumentError("the lattice has $(offsets[end]) records, arc holds $n"))
+    extra === nothing || length(extra) == n || throw(DimensionMismatch("extra must hold one score per record ($n)"))
+    offs = ROCArray(Int64.(collect(offsets)))
+    arcd = ROCArray(Int32.(collect(arc)) .- Int32(1))
+    ex = extra === nothing ? nothing : ROCArray(Float32.(collect(extra)))
+    best = ROCArray{Float32}(undef, B)
+    score = ROCArray{Float32}(undef, n)
+    rec = want_path ? ROCArray{Int64}(undef, N, B) : nothing
+    path = want_path ? ROCArray{Int32}(undef, N, B) : nothing
+    lp = lens === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(lens))
+    check(ccall((:mm_latticebest_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Int64}, Ptr{Int32}, Int64, Ptr{Float32}, Ptr{Float32}, Ptr{Float32},
+         Ptr{Int64}, Int64, Ptr{Int32}, Int64, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, lp, N, pointer(offs), pointer(arcd), n, ex === nothing ? Ptr{Float32}(C_NULL) : pointer(ex),
+        pointer(best), pointer(score), rec === nothing ? Ptr{Int64}(C_NULL) : pointer(rec), N,
+        path === nothing ? Ptr{Int32}(C_NULL) : pointer(path), N, AMDGPU.stream().stream))
+    Array(best), Array(score), rec === nothing ? nothing : Array(rec) .+ Int64(1), path === nothing ? nothing : Array(path) .+ Int32(1)
 end
 
 """

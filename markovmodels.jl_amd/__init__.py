@@ -2,7 +2,7 @@
 
 Host-side mirror of the reference's hot-path interface (src/MarkovModels.jl:14-45:
 FSM, nstates, rawunion, CompiledFSM, batch, compile, expand, alpha-recursion,
-beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, chunkedposteriors, windowbestpath, classbestpath, lattice, latticeposteriors, latticecost, arcposteriors, arcclassposteriors, scoredposteriors, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
+beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, chunkedposteriors, windowbestpath, classbestpath, lattice, latticeposteriors, latticecost, latticebest, arcposteriors, arcclassposteriors, scoredposteriors, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
 The directory name contains a dot, so load it with
 ``__graft_entry__.load_package()`` (importlib) rather than a plain import.
 """
@@ -12,6 +12,7 @@ from .inference import (  # noqa: F401
     BatchedFSM,
     CompiledFSM,
     Lattice,
+    LatticeBest,
     LatticeCost,
     LatticePosteriors,
     alpharecursion,
@@ -30,6 +31,7 @@ from .inference import (  # noqa: F401
     expectedcost,
     filterposteriors,
     lattice,
+    latticebest,
     latticecost,
     latticeposteriors,
     leakyposteriors,
@@ -61,8 +63,8 @@ from .longform import chunked_loglik  # noqa: F401
 from . import transitions  # noqa: F401
 from .transitions import constraint_scores, transition_loglik  # noqa: F401
 from . import decode  # noqa: F401
-from .decode import events, forced_alignment, lattice_arcs, lattice_fsm, lattice_prune, segments  # noqa: F401
+from .decode import events, forced_alignment, lattice_arcs, lattice_fsm, lattice_onebest, lattice_prune, lattice_rescore, segments  # noqa: F401
 from . import lattices  # noqa: F401
-from .lattices import lattice_loglik, lattice_risk, lattice_smbr_loss, pdf_costs, record_index  # noqa: F401
+from .lattices import lattice_best_score, lattice_loglik, lattice_risk, lattice_smbr_loss, pdf_costs, record_index  # noqa: F401
 from . import streaming  # noqa: F401
 from .streaming import FixedLagSmoother, ForwardFilter, OnlineViterbi  # noqa: F401

@@ -573,6 +573,8 @@ static int latpost_nt(mm_batch_t h) { return h->dbg.latpost_nt ? h->dbg.latpost_
 static int64_t latpost_state_cap() { return int64_t((MM_LDS_MAX - mm_latpost_lds_bytes(0)) / (mm_latpost_lds_bytes(1) - mm_latpost_lds_bytes(0))); }
 // mm_latticecost_f32: the same workgroup, five per-state LDS arrays
 static int64_t latcost_state_cap() { return int64_t((MM_LDS_MAX - mm_latcost_lds_bytes(0)) / (mm_latcost_lds_bytes(1) - mm_latcost_lds_bytes(0))); }
+// mm_latticebest_f32: the same workgroup, three per-state LDS words
+static int64_t latbest_state_cap() { return int64_t((MM_LDS_MAX - mm_latbest_lds_bytes(0)) / (mm_latbest_lds_bytes(1) - mm_latbest_lds_bytes(0))); }
 
 // item / tropical kernels: `kernel` keeps the state vectors in LDS; `big` is the same kernel with the vectors in global
 // memory, for FSMs beyond the LDS (the reference has no size limit: src/linalg.jl:170-181)
@@ -2876,6 +2878,12 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
             " bytes of LDS per state) + mm_latcost_grad_kernel<" + std::to_string(MM_LATPOST_GAMMA_NT) +
             "> (one workgroup per utterance and frame, when grad or gamma is asked for); state cap " + std::to_string(latcost_state_cap());
         if (mm_latcost_lds_bytes(h->max_S1p) > MM_LDS_MAX) s += "; " + std::to_string(h->max_S1p) + " states exceed the cap";
+    } else if (entry == 21) {  // mm_latticebest_f32
+        if (h->semiring != MM_TROPICAL) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_latticebest_f32 runs on tropical batches only");
+        s = "mm_latbest_kernel<" + std::to_string(latpost_nt(h)) + "> (one workgroup per utterance, serial over the transitions: the tropical forward-backward "
+            "over the records of each cell in one pass and one barrier per step, three rotating state vectors in LDS, integer max, the best path traced in the "
+            "backward loop, " + std::to_string(mm_latbest_lds_bytes(1) - mm_latbest_lds_bytes(0)) + " bytes of LDS per state); state cap " + std::to_string(latbest_state_cap());
+        if (mm_latbest_lds_bytes(h->max_S1p) > MM_LDS_MAX) s += "; " + std::to_string(h->max_S1p) + " states exceed the cap";
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -4914,6 +4922,46 @@ int mm_latticecost_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, c
     lc.diff = diff;
     lc.grad = grad;
     return mm_launch_latcost(h->B, nt, h->max_S1p, h->max_P1, p, lp, lc, static_cast<hipStream_t>(stream));
+}
+
+// ---- lattice best paths (mm_kernel_latbest.hip): the tropical forward-backward over the records of a lattice, and the best path
+int mm_latticebest_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, const int64_t *offsets,
+                       const int32_t *arc, int64_t nrec, const float *extra, float *best, float *score, int64_t *rec, int64_t rsb, int32_t *path,
+                       int64_t psb, void *stream) {
+    const std::string who = "mm_latticebest_f32";
+    // what the arguments alone show comes first, then the batch's refusals
+    if (!offsets || !best) return fail(MM_ERR_INVALID, who + ": offsets/best is NULL");
+    if (nrec < 0) return fail(MM_ERR_INVALID, who + ": nrec must be >= 0");
+    if (nrec > 0 && (!arc || !score)) return fail(MM_ERR_INVALID, who + ": arc/score is NULL with nrec > 0");
+    if (rec && rsb < N) return fail(MM_ERR_DIM, who + ": rec_stride_b < N");
+    if (path && psb < N) return fail(MM_ERR_DIM, who + ": path_stride_b < N");
+    if (h && h->semiring != MM_TROPICAL)
+        return fail(MM_ERR_UNSUPPORTED, who + ": tropical batches only (this batch is " + (h->semiring == MM_LOG ? "log-semiring" : "ProbSemiring") + ")");
+    int rc = check_run(h, who.c_str(), V, N, MM_TROPICAL);
+    if (rc) return rc;
+    if (mm_latbest_lds_bytes(h->max_S1p) > MM_LDS_MAX)
+        return fail(MM_ERR_UNSUPPORTED, who + ": " + std::to_string(h->max_S1p) + " states (padded) exceed the " + std::to_string(latbest_state_cap()) +
+                                            " whose vectors fit the LDS (" + std::to_string(mm_latbest_lds_bytes(1) - mm_latbest_lds_bytes(0)) + " bytes per state)");
+    const int nt = latpost_nt(h);
+    if (nt != 256 && nt != 512 && nt != 1024) return fail(MM_ERR_INVALID, who + ": MM_LATPOST_NT must be 256, 512 or 1024");
+    rc = ensure_item_forms(h, stream);
+    if (!rc) rc = ensure_lattice_arcs(h, stream);
+    if (rc) return rc;
+    const RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    LatPostParams lp{};
+    lp.arcs = static_cast<const LatticeDev *>(h->d_lat.get());
+    lp.offs = reinterpret_cast<const long long *>(offsets);
+    lp.arc = arc;
+    lp.nrec = nrec;
+    lp.extra = extra;
+    lp.post = score;
+    lp.logz = best;
+    LatBestParams lb{};
+    lb.rec = reinterpret_cast<long long *>(rec);
+    lb.rsb = rsb;
+    lb.path = path;
+    lb.psb = psb;
+    return mm_launch_latbest(h->B, nt, h->max_S1p, p, lp, lb, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -517,6 +517,17 @@ int mm_launch_latcost(int64_t B, int nt, int max_S1p, int max_P1, const RunParam
 size_t mm_latcost_lds_bytes(int S1p);      // a head + 28 bytes per state: the 16 of the posteriors, a 64-bit cost sum and a float
 size_t mm_latcost_grad_lds_bytes(int P1);  // a head + two 64-bit sums per pdf
 
+// ---- lattice best paths (mm_latbest_tu.hip: mm_latbest_kernel, the tropical forward-backward over the records of a lattice with the
+// trace of the best path, one workgroup per utterance; the workgroup is MM_LATPOST_NT's)
+struct LatBestParams {       // beside a LatPostParams, whose post is score and whose logz is best (gamma unused)
+    long long *rec;          // [b * rsb + t] the best path's records; NULL: not asked for
+    long long rsb;
+    int *path;               // [b * psb + t] their source states; NULL: not asked for
+    long long psb;
+};
+int mm_launch_latbest(int64_t B, int nt, int max_S1p, const RunParams &p, const LatPostParams &lp, const LatBestParams &lb, hipStream_t stream);
+size_t mm_latbest_lds_bytes(int S1p);  // a head + 12 bytes per state: three 32-bit words
+
 // ---- posteriors with call-time arc weights (mm_weighted_tu.hip: mm_weights_kernel, mm_log_kernel's forward half on the call's
 // descriptors, mm_weighted_bwd_kernel and mm_weighted_scatter_kernel on the item form)
 struct UttDesc;  // mm_kernels.hip

@@ -8,7 +8,9 @@ there is no path.
 
 And from the ``Lattice`` of ``BatchedFSM.lattice`` (mm_lattice_f32): one utterance's kept arcs as host arrays (``lattice_arcs``) and
 as an acyclic tropical FSM that goes back into ``compile`` / ``batch`` for rescoring (``lattice_fsm``); and the lattice of the
-records above a posterior threshold (``lattice_prune``, on the posteriors of ``BatchedFSM.latticeposteriors``).
+records above a posterior threshold (``lattice_prune``, on the posteriors of ``BatchedFSM.latticeposteriors``).  After a rescoring
+(``BatchedFSM.latticebest``, mm_latticebest_f32): the lattice re-pruned to a beam under the new scores (``lattice_rescore``) and one
+utterance's new best path as host arrays (``lattice_onebest``).
 """
 from __future__ import annotations
 
@@ -149,3 +151,48 @@ def lattice_prune(lat, post, threshold):
     counts = np.bincount(cell[keep], minlength=B * N)[: B * N].astype(_host(lat.counts).dtype).reshape(B, N)
     offs = np.concatenate([[0], np.cumsum(counts.reshape(-1), dtype=np.int64)])
     return type(lat)(counts, offs, _host(lat.arc)[keep], _host(lat.score)[keep], lat.best)
+
+
+def lattice_rescore(bf, lat, V, extra=None, lens=None, beam=None):
+    """A ``Lattice`` under new scores: ``BatchedFSM.latticebest`` on ``lat`` with the emissions ``V`` and the per-record scores
+    ``extra`` (a language model's, say), then the ``Lattice`` of the records whose NEW through-score is within ``beam`` of the new
+    best path (``score >= -beam``; ``beam`` None: every record with a finite score), with the new ``score`` and ``best``.  Counts and
+    offsets are recomputed as ``lattice_prune`` does, ``arc`` keeps its order: the result goes back into every entry that reads a
+    lattice.  On the lattice's own ``V`` with ``extra`` None and exact inputs this is the lattice ``bf.lattice`` returns at the
+    narrower beam.  Tensors stay on the device (one synchronisation, the one that sizes the result); NumPy in, NumPy out."""
+    if beam is not None and not beam >= 0:
+        raise ValueError(f"lattice_rescore: beam must be >= 0 or None, got {beam}")
+    res = bf.latticebest(lat, V, lens, extra, want_path=False)
+    n = res.score.shape[0]
+    B, N = lat.counts.shape
+    if hasattr(res.score, "cpu"):  # (tensors)
+        import torch
+
+        dev = res.score.device
+        offsets = torch.as_tensor(lat.offsets).to(dev)
+        keep = ~torch.isneginf(res.score) if beam is None else res.score >= -float(beam)
+        cell = torch.searchsorted(offsets[1:].contiguous(), torch.arange(n, device=dev, dtype=offsets.dtype), right=True)
+        keep &= cell < B * N  # (records behind the last cell belong to no transition)
+        counts = torch.bincount(cell[keep], minlength=B * N)[: B * N].to(torch.int32).reshape(B, N)
+        offs = torch.cat([torch.zeros(1, dtype=offsets.dtype, device=dev), torch.cumsum(counts.reshape(-1), 0, dtype=offsets.dtype)])
+        return type(lat)(counts, offs, torch.as_tensor(lat.arc).to(dev)[keep], res.score[keep], res.best)
+    offsets = _host(lat.offsets)
+    keep = ~np.isneginf(res.score) if beam is None else res.score >= -np.float32(beam)
+    cell = np.searchsorted(offsets[1:], np.arange(n, dtype=np.int64), side="right")
+    keep &= cell < B * N
+    counts = np.bincount(cell[keep], minlength=B * N)[: B * N].astype(np.int32).reshape(B, N)
+    offs = np.concatenate([[0], np.cumsum(counts.reshape(-1), dtype=np.int64)])
+    return type(lat)(counts, offs, _host(lat.arc)[keep], res.score[keep], res.best)
+
+
+def lattice_onebest(bf, lat, res, b):
+    """Utterance b's best path through the lattice ``lat`` as ``BatchedFSM.latticebest`` found it (``res``, asked for with its
+    path), on the host: the arrays ``(t, arc, src, dst)`` of its records, one per transition -- ``lattice_arcs``' columns without
+    the score.  Empty arrays for an utterance without a path."""
+    if res.rec is None:
+        raise ValueError("lattice_onebest: the LatticeBest holds no path (want_path=False)")
+    r = _host(res.rec)[b].astype(np.int64)
+    r = r[r >= 0]
+    k = _host(lat.arc)[r].astype(np.int64)
+    src, dst = _entry_ends(bf.cfsms[b].fsm)
+    return np.arange(r.size, dtype=np.int64), k, src[k], dst[k]

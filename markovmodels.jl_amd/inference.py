@@ -183,6 +183,18 @@ class LatticeCost(NamedTuple):
     gamma: object
 
 
+class LatticeBest(NamedTuple):
+    """What ``BatchedFSM.latticebest`` returns.  ``best[B]``: the weight of the lattice's best path (-inf: none); ``score`` float32,
+    one per record: the best path through the record minus ``best`` (<= 0 up to rounding; -inf: no path through it); ``rec[B, N]``
+    int64: the best path's record of every transition, an index into ``lat.arc``; ``path[B, N]`` int32: the source state of that
+    record, ``bestpath``'s convention (both -1 at and behind ``len`` and without a path; None when not asked for)."""
+
+    best: object
+    score: object
+    rec: object
+    path: object
+
+
 def _on_device(x, dtype, device):
     """A member of a lattice (or ``extra``) as a contiguous tensor of ``dtype`` on ``device``: a tensor, or anything NumPy reads."""
     import torch
@@ -1043,11 +1055,11 @@ class BatchedFSM:
         leakyposteriors, "entropy" = pathentropy, "filter" = filterposteriors, "window" = windowposteriors,
         "vitwindow" = viterbiwindow (tropical batches), "weighted" = weightedposteriors, "segment" = segmentposteriors,
         "classpath" = classpath (tropical batches), "lattice" = lattice (tropical batches), "latticeposteriors" = latticeposteriors
-        (tropical batches), "latticecost" = latticecost (tropical batches)."""
+        (tropical batches), "latticecost" = latticecost (tropical batches), "latticebest" = latticebest (tropical batches)."""
         import ctypes
 
         buf = ctypes.create_string_buffer(1024)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13, "arcclass": 14, "scored": 15, "classcost": 16, "classpath": 17, "lattice": 18, "latticeposteriors": 19, "latticecost": 20}[semiring], buf, 1024))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13, "arcclass": 14, "scored": 15, "classcost": 16, "classpath": 17, "lattice": 18, "latticeposteriors": 19, "latticecost": 20, "latticebest": 21}[semiring], buf, 1024))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -1161,19 +1173,12 @@ class BatchedFSM:
         offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counts.reshape(-1), 0, dtype=torch.int64)])
         return Lattice(*_results((counts, offsets, arc, score, best), as_numpy))
 
-    def latticeposteriors(self, lat, V, lens=None, extra=None, want_gamma=True):
-        """Lattice posteriors (mm_latticeposteriors_f32): the log-semiring forward-backward over the records of ``lat`` -- a
-        ``Lattice`` of ``BatchedFSM.lattice`` on this batch, or a subset of one (``decode.lattice_prune``) -- under the emissions
-        ``V`` of THIS call (a second model's, or the first one's at another scale) and an optional score ``extra`` per record.
-        Returns ``LatticePosteriors(post, logz, gamma)``: ``post`` float32 per record, the log posterior of the record among the
-        lattice's paths (-inf: no path through it); ``logz[B]`` the lattice's log-sum (-inf: no path); ``gamma[B, N, P]`` the pdf
-        occupancies = d logz / d V (``want_gamma=False``: None, and the second kernel does not run); ``exp(post)`` is
-        d logz / d extra.  ``lens`` are those of the lattice call.  ``lat``'s members may be tensors or NumPy arrays; the results are
-        NumPy arrays if ``V`` came as NumPy.  ValueError when ``lat.arc`` holds fewer records than ``lat.offsets[-1]`` (a lattice
-        cut by ``max_arcs``) -- one read-back, left out inside a stream capture.  Integer maxima and fixed-point sums: bit-identical
-        from call to call.  Tropical batches only."""
-        torch, Vt, lt, as_numpy = self._prep(V, lens)
-        B, N, P = Vt.shape
+    def _lattice_inputs(self, who, torch, lat, Vt, extra):
+        """The checks of the entries that read a lattice: ``(offsets, arc, nrec, extra)`` as contiguous tensors on V's device
+        (``extra`` None as it is).  DimensionMismatch for offsets that are not [B * N + 1], an ``arc`` that is no vector and an
+        ``extra`` of another length; ValueError when ``lat.arc`` holds fewer records than ``lat.offsets[-1]`` (one read-back, left
+        out inside a stream capture)."""
+        B, N, _ = Vt.shape
         dev = Vt.device
         offsets = _on_device(lat.offsets, torch.int64, dev)
         arc = _on_device(lat.arc, torch.int32, dev)
@@ -1190,7 +1195,47 @@ class BatchedFSM:
         if not torch.cuda.is_current_stream_capturing():
             total = int(offsets[-1].item())
             if total > nrec:
-                raise ValueError(f"latticeposteriors: the lattice has {total} records, lat.arc holds {nrec} (max_arcs cut it)")
+                raise ValueError(f"{who}: the lattice has {total} records, lat.arc holds {nrec} (max_arcs cut it)")
+        return offsets, arc, nrec, et
+
+    def latticebest(self, lat, V, lens=None, extra=None, want_path=True):
+        """Lattice best paths (mm_latticebest_f32), the tropical twin of ``latticeposteriors``: over the records of ``lat`` -- a
+        ``Lattice`` of ``BatchedFSM.lattice`` on this batch, or a subset of one -- under the emissions ``V`` of THIS call and an
+        optional score ``extra`` per record (a rescoring).  Returns ``LatticeBest(best, score, rec, path)``: ``best[B]`` the weight of
+        the best path (-inf: none), ``score`` float32 per record, the best path through the record minus ``best`` (-inf: none),
+        ``rec[B, N]`` int64 the best path's record of every transition (an index into ``lat.arc``; ties go to the lowest record) and
+        ``path[B, N]`` int32 the source state of that record, ``bestpath``'s convention; both -1 at and behind ``len`` and without a
+        path, both None with ``want_path=False``.  ``extra[r] = -inf`` removes record r.  ``decode.lattice_rescore`` re-prunes the
+        lattice by ``score``, ``decode.lattice_onebest`` reads one utterance's best path.  Inputs and results as ``latticeposteriors``
+        handles them, its ValueError for a lattice cut by ``max_arcs`` included.  Adds and integer maxima only: bit-identical from
+        call to call.  Tropical batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        dev = Vt.device
+        offsets, arc, nrec, et = self._lattice_inputs("latticebest", torch, lat, Vt, extra)
+        best = torch.empty(B, dtype=torch.float32, device=dev)
+        score = torch.empty(nrec, dtype=torch.float32, device=dev)
+        rec = torch.empty((B, N), dtype=torch.int64, device=dev) if want_path else None
+        path = torch.empty((B, N), dtype=torch.int32, device=dev) if want_path else None
+        check(lib.mm_latticebest_f32(*_head(self._h, Vt, lt, N), offsets.data_ptr(), arc.data_ptr(), nrec, _ptr(et), best.data_ptr(), score.data_ptr(),
+                                     _ptr(rec), N, _ptr(path), N, self._stream(torch)))
+        return LatticeBest(*_results((best, score, rec, path), as_numpy))
+
+    def latticeposteriors(self, lat, V, lens=None, extra=None, want_gamma=True):
+        """Lattice posteriors (mm_latticeposteriors_f32): the log-semiring forward-backward over the records of ``lat`` -- a
+        ``Lattice`` of ``BatchedFSM.lattice`` on this batch, or a subset of one (``decode.lattice_prune``) -- under the emissions
+        ``V`` of THIS call (a second model's, or the first one's at another scale) and an optional score ``extra`` per record.
+        Returns ``LatticePosteriors(post, logz, gamma)``: ``post`` float32 per record, the log posterior of the record among the
+        lattice's paths (-inf: no path through it); ``logz[B]`` the lattice's log-sum (-inf: no path); ``gamma[B, N, P]`` the pdf
+        occupancies = d logz / d V (``want_gamma=False``: None, and the second kernel does not run); ``exp(post)`` is
+        d logz / d extra.  ``lens`` are those of the lattice call.  ``lat``'s members may be tensors or NumPy arrays; the results are
+        NumPy arrays if ``V`` came as NumPy.  ValueError when ``lat.arc`` holds fewer records than ``lat.offsets[-1]`` (a lattice
+        cut by ``max_arcs``) -- one read-back, left out inside a stream capture.  Integer maxima and fixed-point sums: bit-identical
+        from call to call.  Tropical batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        dev = Vt.device
+        offsets, arc, nrec, et = self._lattice_inputs("latticeposteriors", torch, lat, Vt, extra)
         post = torch.empty(nrec, dtype=torch.float32, device=dev)
         logz = torch.empty(B, dtype=torch.float32, device=dev)
         gamma = torch.empty((B, N, P), dtype=torch.float32, device=dev) if want_gamma else None
@@ -1753,6 +1798,16 @@ def latticecost(fsm, lat, Vhats, cost, Chats=None, extra=None):
         raise TypeError("latticecost needs TropicalSemiring FSMs")
     V, lens = _need_expanded(Vhats)
     return bf.latticecost(lat, V, cost, lens, extra)
+
+
+def latticebest(fsm, lat, Vhats, Chats=None, extra=None):
+    """Lattice best paths -- see ``BatchedFSM.latticebest`` -- in ``lattice``'s call shape: the ``LatticeBest`` (NumPy members, with
+    ``rec`` and ``path``) of the lattice ``lat`` of the batch under the expanded emissions ``Vhats``.  Tropical FSMs."""
+    bf = _as_batch(fsm, Chats)
+    if bf.semiring != "tropical":
+        raise TypeError("latticebest needs TropicalSemiring FSMs")
+    V, lens = _need_expanded(Vhats)
+    return bf.latticebest(lat, V, lens, extra)
 
 
 def _total(fsm, n, cumulative):

@@ -22,6 +22,9 @@ it is MPE / MWE (Povey 2003), with minus [pdf of the record's source = the align
 
     d risk_b / d V[b, n, p] = grad[b, n, p]       d risk_b / d extra[r] = diff[r]       d risk_b / d cost[r] = exp(post[r])
 
+and the weight of its best path, ``best_b = max_{path} W(path)`` (mm_latticebest_f32; ``lattice_best_score``): the Viterbi score of
+perceptron and max-margin losses, whose gradient is the indicator of the best path's records and pdfs.
+
 A launch chain on the caller's stream.
 """
 from __future__ import annotations
@@ -113,6 +116,61 @@ def lattice_risk(bf, lat, V, cost, extra=None, lens=None):
     ``extra`` and ``exp(post[r]) * g[b(r)]`` to ``cost``.  Utterances without a path have risk 0 and zero gradients, as in
     ``lattice_loglik``.  ``bf``: a tropical ``BatchedFSM``."""
     return _risk_function().apply(V, extra, cost, bf, lat, lens)
+
+
+def _state_pdfs(bf, device):
+    """``[B, max S]`` int64 on ``device``: the pdf of every real state of every utterance's FSM (0 in the padding), made once per
+    batch and device."""
+    import torch
+
+    cache = bf.__dict__.setdefault("_state_pdf_tables", {})
+    if device not in cache:
+        rows = [np.asarray(c.C_hat.state2pdf, dtype=np.int64).ravel()[: c.S1 - 1] for c in bf.cfsms]
+        table = np.zeros((len(rows), max(r.size for r in rows)), dtype=np.int64)
+        for b, r in enumerate(rows):
+            table[b, : r.size] = r
+        cache[device] = torch.as_tensor(table).to(device)
+    return cache[device]
+
+
+def _best_function():
+    import torch
+
+    class _LatticeBestScore(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, V, extra, batch, lat, lens):
+            res = batch.latticebest(lat, V.detach(), lens, None if extra is None else extra.detach())
+            ctx.save_for_backward(res.rec, res.path, _state_pdfs(batch, V.device))
+            ctx.shape = tuple(V.shape)
+            ctx.nrec = res.score.numel()
+            ctx.has_extra = extra is not None
+            return res.best
+
+        @staticmethod
+        def backward(ctx, g):
+            rec, path, pdfs = ctx.saved_tensors
+            on = path >= 0  # (the frames of the best path; none for an utterance without one, whatever its g)
+            w = g[:, None].expand_as(path)[on]
+            gV = gE = None
+            if ctx.needs_input_grad[0]:
+                b, n = torch.nonzero(on, as_tuple=True)
+                gV = torch.zeros(ctx.shape, dtype=g.dtype, device=g.device)
+                gV.index_put_((b, n, pdfs[b, path[on].long()]), w, accumulate=True)
+            if ctx.has_extra and ctx.needs_input_grad[1]:
+                gE = torch.zeros(ctx.nrec, dtype=g.dtype, device=g.device)
+                gE.index_put_((rec[on],), w, accumulate=True)
+            return gV, gE, None, None, None
+
+    return _LatticeBestScore
+
+
+def lattice_best_score(bf, lat, V, extra=None, lens=None):
+    """``best[B]``, the weight of the best path of the lattice ``lat`` under ``V`` [B, N, P] float32 on the HIP device and the
+    optional per-record scores ``extra`` (mm_latticebest_f32), both differentiable -- the Viterbi score of perceptron and max-margin
+    losses against a lattice.  The maximum is piecewise linear: backward hands ``g[b]`` to ``extra`` at the records of the best
+    path (the indicator of ``rec``) and to ``V`` at ``(b, n, pdf(path[b, n]))``, a subgradient where best paths tie.  Utterances
+    without a path have ``best = -inf`` and zero gradients.  ``bf``: a tropical ``BatchedFSM``."""
+    return _best_function().apply(V, extra, bf, lat, lens)
 
 
 class RecordIndex(NamedTuple):
