@@ -144,6 +144,8 @@ int64_t mm_batch_total_states(mm_batch_t batch);
  * the bytes of LDS per state and the state cap, and says "exceed the cap" when the batch's largest FSM has more states.
  * 21 = mm_latticebest_f32 (tropical batches only): mm_latbest_kernel<threads>; the text names the bytes of LDS per state and the
  * state cap, and says "exceed the cap" when the batch's largest FSM has more states.
+ * 22 = mm_latticesample_f32 (tropical batches only): mm_latsample_fwd_kernel<threads> + mm_latsample_kernel<threads>; the text names
+ * the state cap and says "exceed the cap" when the batch's largest FSM has more states.
  * Informational (bench.py quotes it). */
 int mm_batch_kernels(mm_batch_t batch, int entry, char *buf, size_t n);
 /* Allocate the internal workspace for runs of up to N frames now (synchronises if it has to grow). */
@@ -1059,6 +1061,80 @@ int mm_latticecost_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int
 int mm_latticebest_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
                        const int64_t *offsets, const int32_t *arc, int64_t nrec, const float *extra, float *best, float *score,
                        int64_t *rec, int64_t rec_stride_b, int32_t *path, int64_t path_stride_b, void *stream);
+
+/* Lattice path sampling (MM_TROPICAL batches): nsamples lattice paths per utterance, drawn independently from the posterior of a
+ * lattice of mm_lattice_f32 (or a subset of one) under THIS call's emissions V and an optional extra score per record.  It is what a
+ * loss needs whose cost does NOT add up along a path -- the expected word error rate, an edit distance (Shannon, "Optimizing expected
+ * word error rate via sampling for speech recognition", Interspeech 2017; Prabhavalkar et al., "Minimum word error rate training for
+ * attention-based sequence-to-sequence models", ICASSP 2018) -- and sampled minimum-Bayes-risk decoding, and diverse pseudo-labels.
+ * Unlike mm_samplepaths_f32 it draws RECORD sequences: parallel entries between two states are separate outcomes, and every record
+ * has its own score.  Records, cells, offsets, arc, extra, dead records, lens, W(path) and logz are exactly those of
+ * mm_latticeposteriors_f32, i(r) / j(r) the source / destination of a record, f the phony final state:
+ *
+ *   P(sample k of utterance b = path) = exp(W(path) - logz[b])          path = r_0 .. r_{len-1}, one record per transition
+ *   x_r         = a_t(i(r)) + wz_r - c_t                                 r in cell t: the value mm_latticeposteriors_f32's forward pass
+ *                                                                        has for the record, wz_r = (T_hat[arc[r]] + extra[r]) + e_{t+2}(j(r))
+ *                                                                        in float32, c_t ONE constant per cell (the pass's running offset)
+ *   u_r         = unit_open(first word of Philox-4x32-10(key = seed's low and high 32 bits; counter = (b, k, t, place of r in its cell)))
+ *                 unit_open(w) = ((w >> 9) + 1/2) / 2^23, mm_samplepaths_f32's generator and its split of the seed
+ *   g_r         = -logf(-logf(u_r))                                      a Gumbel variate, float32, the accurate logarithm
+ *   key_r       = x_r + g_r                                              float32
+ *   cur_{len-1} = f;   r_t = the live record r of cell t with j(r) = cur_t and x_r > -inf whose key_r is greatest, among equal keys the
+ *                 one at the LOWEST place of the cell;   cur_{t-1} = i(r_t)
+ *   rec[b, k, t]  = r_t, an index into arc;   path[b, k, t] = i(r_t), mm_viterbi_f32's convention (the 0-based state at frame t)
+ *   logprob[b, k] = W(path) - logz[b],  W in float64: the float32 wz of r_{len-1}, r_{len-2}, .., r_0 added in that order, then the
+ *                   float32 alpha_hat(i(r_0)) + V[b, 0, pdf(i(r_0))]; the difference with logz[b] in float64, rounded once
+ *
+ * The maximum of x_r + Gumbel noise over the records into a state is a draw with probability proportional to exp(x_r) (the Gumbel-max
+ * trick); exp(x_r) over the records into cur_t is the posterior of r_t given the rest of the path behind it, and c_t, common to the
+ * cell, cancels.  Consequences: (a) a sample is a function of (lattice, V, extra, lens, seed, b, k) alone: not of nsamples, the
+ * thread count, the stream or earlier calls; the first K' samples of a call with nsamples > K' are the samples of a call with K'; a
+ * repeated call returns the same bits.  (b) The counter holds the POSITION b, not the utterance's content: two equal utterances of a
+ * batch get different samples.  (c) A record with x_r = -inf is never drawn, whatever u: a dead record, extra[r] = -inf, a record
+ * with no path into its source.  (d) A chosen record has a finite x_r, hence a finite-x record into its source one cell earlier: a
+ * chain of an utterance with a path never dies.  (e) Discretisation: u takes 2^23 values, so g takes 2^23 values in about
+ * [-2.81, 16.64]; the Gumbel mass outside that range is about 6e-8 on either side, which bounds the bias of a decision's
+ * probabilities at that order, beside the float32 rounding of x and g.  (f) Where every cell holds one live record -- a beam of 0 with
+ * a unique best path -- every sample is that path, and on inputs that are multiples of 1/16 logprob is exactly 0.  (g) The key's low
+ * word holds 2^32 - 1 - place: a record at place >= 2^32 - 1 of a doctored cell of that many records is passed over, never drawn;
+ * should that leave a sample without a candidate, its remaining entries are -1 and its logprob -inf.
+ *
+ *   batch .. extra   as mm_latticeposteriors_f32
+ *   nsamples     a host value >= 1 (MM_ERR_INVALID otherwise); more than 64 * 65535: MM_ERR_UNSUPPORTED
+ *   seed         any value; its low and high 32 bits are the generator's key
+ *   fwd          device float32[nrec], out: a per-record buffer of the caller's.  NULL with nrec > 0: MM_ERR_INVALID.  On return fwd[r]
+ *                = x_r, that is the record's forward value up to one constant per cell; -inf for a dead record, a record with no path
+ *                into its source, the records of cells at or behind len and every record of an utterance without a path
+ *   rec          device int64, out, or NULL: element (b, k, t) at rec[b*rec_stride_b + k*rec_stride_k + t].  rec_stride_k < N or
+ *                rec_stride_b < nsamples*rec_stride_k: MM_ERR_DIM
+ *   path         device int32, out, or NULL: element (b, k, t) at path[b*path_stride_b + k*path_stride_k + t]; the same rule for its
+ *                strides.  rec and path both NULL: MM_ERR_INVALID.  All N entries of every (b, k) are written: -1 for t >= len, and
+ *                everywhere for an utterance without a path
+ *   logprob      device float32, out, or NULL (not computed): element (b, k) at logprob[b*lp_stride_b + k]; -inf without a path.
+ *                lp_stride_b < nsamples: MM_ERR_DIM
+ *   logz         device float32[B], out: mm_latticeposteriors_f32's logz, bit for bit.  NULL: MM_ERR_INVALID
+ * Memory safety does not depend on the contents of the device arrays, by mm_latticeposteriors_f32's checks: a record whose entry is
+ * outside [0, nnz_b) or is the phony self-loop is dead, cells are clamped into [0, nrec] and made non-decreasing, lens into [0, N];
+ * records no cell covers are not written.
+ * Log and ProbSemiring batches: MM_ERR_UNSUPPORTED.  Argument errors that need no device are reported before the NULL-batch check.
+ * The state vectors of the forward pass live in LDS, 16 bytes per state: an FSM of more than about 10 200 states (padded) returns
+ * MM_ERR_UNSUPPORTED with the limit in the message; mm_batch_kernels(.., 22, ..) names it.
+ * Order of a call: mm_latsample_fwd_kernel (mm_latpost_fb_kernel's forward pass, the same code: it ends behind logz), then
+ * mm_latsample_kernel on a grid of (B, ceil(nsamples / 64)): a workgroup draws 64 samples of one utterance, serial over the
+ * transitions backwards.  LDS holds a 64-bit mask per state -- bit q: sample q of the chunk sits there -- and two alternating sets of
+ * 64 key slots.  Per step every thread takes records of the cell, reads the mask of the destination and, for every set bit with a
+ * finite fwd[r], maximises the 64-bit (order-preserving code of key_r, 2^32 - 1 - place) in that sample's slot by an integer LDS
+ * atomic; behind a barrier lane q of the first wave reads its winner, stores rec / path, adds wz to its float64 weight and moves
+ * its bit to the source's mask; a second barrier ends the step.  Integer maxima do not depend on the order of arrival.  The work of a
+ * step is the records of its cell plus the candidates of at most 64 states.
+ * No workspace.  Stream contract and graph capture: those of mm_latticeposteriors_f32 (a first call of any lattice entry puts the
+ * item forms and the arc table on the device); a replay after V, extra, offsets or arc were overwritten in place follows them. */
+int mm_latticesample_f32(mm_batch_t batch, const float *V, int64_t v_stride_b, int64_t v_stride_n, const int32_t *lens, int64_t N,
+                         const int64_t *offsets, const int32_t *arc, int64_t nrec, const float *extra,
+                         int64_t nsamples, int64_t seed, float *fwd,
+                         int64_t *rec, int64_t rec_stride_b, int64_t rec_stride_k,
+                         int32_t *path, int64_t path_stride_b, int64_t path_stride_k,
+                         float *logprob, int64_t lp_stride_b, float *logz, void *stream);
 
 /* totalsum(alpha, T, omega, n) / totalcumsum(alpha, T, omega, n) (src/algorithms.jl:8-29;
  * totalweightsum(fsm, n) = totalcumsum, :36), one value per FSM of the batch, in the batch's semiring

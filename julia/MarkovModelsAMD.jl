@@ -31,7 +31,7 @@ using LinearAlgebra
 import MarkovModels: compile, batch, pdfposteriors, αrecursion, βrecursion, totalsum, totalcumsum
 
 # what this module adds to the package's API
-export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, set_arc_classes!, arc_class_info, arcclassposteriors, score_class_cap, scoredposteriors, cost_class_cap, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, set_path_classes!, path_class_info, classpath, lattice, latticeposteriors, latticecost, latticebest, pdfposteriors_generic, last_redo_count,
+export ROCCompiledFSM, ROCBatch, to_device, compile_many, bestpath, maxstateposteriors, arcposteriors, set_arc_classes!, arc_class_info, arcclassposteriors, score_class_cap, scoredposteriors, cost_class_cap, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, leakyposteriors, filterposteriors, windowposteriors, segmentposteriors, viterbiwindow, set_path_classes!, path_class_info, classpath, lattice, latticeposteriors, latticecost, latticebest, latticesample, pdfposteriors_generic, last_redo_count,
        last_fallback_count, last_exact_first, team_xcd_stats, reserve_ex!, set_deterministic!, set_posterior_floor!, set_exact_policy!,
        set_mark_policy!, set_gamma_mode!, set_rccl, allreduce_logz, allgather_ttl, ROCSparseCSR, ROCSparseVec, elmul!, eldiv!,
        compiled_cache_clear!, compiled_cache_limits!
@@ -1028,6 +1028,45 @@ function latticebest(b::ROCBatch{K}, V::ROCArray{Float32,3}, offsets::AbstractVe
         pointer(best), pointer(score), rec === nothing ? Ptr{Int64}(C_NULL) : pointer(rec), N,
         path === nothing ? Ptr{Int32}(C_NULL) : pointer(path), N, AMDGPU.stream().stream))
     Array(best), Array(score), rec === nothing ? nothing : Array(rec) .+ Int64(1), path === nothing ? nothing : Array(path) .+ Int32(1)
+end
+
+"""
+    latticesample(b::ROCBatch{<:TropicalSemiring}, V, offsets, arc, nsamples, lens = nothing; seed = 0, extra = nothing,
+                  want_path = true, want_logprob = true) -> (rec, path, logprob, logz)
+
+Lattice path sampling (mm_latticesample_f32 in the header): `nsamples` independent draws per utterance from the posterior over the
+record sequences of the lattice under the emissions `V` of this call and the optional score `extra` per record.  `rec`
+(`N × nsamples × B`) the samples' records (1-based into `arc`, 0: none), `path` (`N × nsamples × B`) their source states (1-based,
+0: none; `nothing` without `want_path`), `logprob` (`nsamples × B`) the log posterior of every sample (`nothing` without
+`want_logprob`), `logz` (B) as `latticeposteriors` returns it.  A sample depends on the inputs, `seed`, its utterance's position and
+its own index alone.
+"""
+function latticesample(b::ROCBatch{K}, V::ROCArray{Float32,3}, offsets::AbstractVector{<:Integer}, arc::AbstractVector{<:Integer},
+                       nsamples::Integer, lens = nothing; seed::Integer = 0, extra = nothing, want_path::Bool = true,
+                       want_logprob::Bool = true) where K <: TropicalSemiring
+    P, N, B = size(V)
+    nsamples >= 1 || throw(ArgumentError("nsamples must be >= 1"))
+    length(offsets) == N * B + 1 || throw(DimensionMismatch("offsets must have N·B + 1 = $(N * B + 1) entries"))
+    n = length(arc)
+    offsets[end] <= n || throw(ArgumentError("the lattice has $(offsets[end]) records, arc holds $n"))
+    extra === nothing || length(extra) == n || throw(DimensionMismatch("extra must hold one score per record ($n)"))
+    offs = ROCArray(Int64.(collect(offsets)))
+    arcd = ROCArray(Int32.(collect(arc)) .- Int32(1))
+    ex = extra === nothing ? nothing : ROCArray(Float32.(collect(extra)))
+    fwd = ROCArray{Float32}(undef, n)
+    rec = ROCArray{Int64}(undef, N, nsamples, B)
+    path = want_path ? ROCArray{Int32}(undef, N, nsamples, B) : nothing
+    logprob = want_logprob ? ROCArray{Float32}(undef, nsamples, B) : nothing
+    logz = ROCArray{Float32}(undef, B)
+    lp = lens === nothing ? Ptr{Int32}(C_NULL) : Ptr{Int32}(pointer(lens))
+    check(ccall((:mm_latticesample_f32, LIB), Cint,
+        (Ptr{Cvoid}, Ptr{Float32}, Int64, Int64, Ptr{Int32}, Int64, Ptr{Int64}, Ptr{Int32}, Int64, Ptr{Float32}, Int64, Int64, Ptr{Float32},
+         Ptr{Int64}, Int64, Int64, Ptr{Int32}, Int64, Int64, Ptr{Float32}, Int64, Ptr{Float32}, Ptr{Cvoid}),
+        b.handle, pointer(V), P * N, P, lp, N, pointer(offs), pointer(arcd), n, ex === nothing ? Ptr{Float32}(C_NULL) : pointer(ex),
+        nsamples, seed % Int64, pointer(fwd), pointer(rec), N * nsamples, N,
+        path === nothing ? Ptr{Int32}(C_NULL) : pointer(path), N * nsamples, N,
+        logprob === nothing ? Ptr{Float32}(C_NULL) : pointer(logprob), nsamples, pointer(logz), AMDGPU.stream().stream))
+    Array(rec) .+ Int64(1), path === nothing ? nothing : Array(path) .+ Int32(1), logprob === nothing ? nothing : Array(logprob), Array(logz)
 end
 
 """

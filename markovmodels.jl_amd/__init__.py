@@ -2,7 +2,7 @@
 
 Host-side mirror of the reference's hot-path interface (src/MarkovModels.jl:14-45:
 FSM, nstates, rawunion, CompiledFSM, batch, compile, expand, alpha-recursion,
-beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, chunkedposteriors, windowbestpath, classbestpath, lattice, latticeposteriors, latticecost, latticebest, arcposteriors, arcclassposteriors, scoredposteriors, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
+beta-recursion, pdfposteriors, leakyposteriors, filterposteriors, windowposteriors, chunkedposteriors, windowbestpath, classbestpath, lattice, latticeposteriors, latticecost, latticebest, latticesample, arcposteriors, arcclassposteriors, scoredposteriors, classcost, weightedposteriors, samplepaths, expectedcost, pathentropy, totalsum, totalcumsum, totalweightsum) over the C ABI in include/markovmodels_amd.h.
 The directory name contains a dot, so load it with
 ``__graft_entry__.load_package()`` (importlib) rather than a plain import.
 """
@@ -15,6 +15,7 @@ from .inference import (  # noqa: F401
     LatticeBest,
     LatticeCost,
     LatticePosteriors,
+    LatticeSamples,
     alpharecursion,
     arcclassposteriors,
     arcposteriors,
@@ -34,6 +35,7 @@ from .inference import (  # noqa: F401
     latticebest,
     latticecost,
     latticeposteriors,
+    latticesample,
     leakyposteriors,
     maxstateposteriors,
     pathentropy,
@@ -65,6 +67,6 @@ from .transitions import constraint_scores, transition_loglik  # noqa: F401
 from . import decode  # noqa: F401
 from .decode import events, forced_alignment, lattice_arcs, lattice_fsm, lattice_onebest, lattice_prune, lattice_rescore, segments  # noqa: F401
 from . import lattices  # noqa: F401
-from .lattices import lattice_best_score, lattice_loglik, lattice_risk, lattice_smbr_loss, pdf_costs, record_index  # noqa: F401
+from .lattices import lattice_best_score, lattice_loglik, lattice_risk, lattice_sampled_risk, lattice_smbr_loss, pdf_costs, record_index  # noqa: F401
 from . import streaming  # noqa: F401
 from .streaming import FixedLagSmoother, ForwardFilter, OnlineViterbi  # noqa: F401

@@ -79,6 +79,7 @@ SYMBOLS = [
     "mm_latticeposteriors_f32",
     "mm_latticecost_f32",
     "mm_latticebest_f32",
+    "mm_latticesample_f32",
     "mm_totalsum_f32",
     "mm_set_rccl",
     "mm_allreduce_logz",
@@ -232,6 +233,8 @@ def _load():
     lib.mm_latticecost_f32.argtypes = [vp, fp, i64, i64, vp, i64, vp, vp, i64, fp, fp, fp, fp, fp, fp, fp, fp, i64, i64, vp]
     lib.mm_latticebest_f32.restype = C.c_int
     lib.mm_latticebest_f32.argtypes = [vp, fp, i64, i64, vp, i64, vp, vp, i64, fp, fp, fp, vp, i64, vp, i64, vp]
+    lib.mm_latticesample_f32.restype = C.c_int
+    lib.mm_latticesample_f32.argtypes = [vp, fp, i64, i64, vp, i64, vp, vp, i64, fp, i64, i64, fp, vp, i64, i64, vp, i64, i64, fp, i64, fp, vp]
     lib.mm_viterbiwindow_f32.restype = C.c_int
     lib.mm_viterbiwindow_f32.argtypes = [vp, fp, i64, i64, vp, i64, fp, vp, vp, C.c_int, fp, fp, vp, vp, i64, fp, vp, vp]
     lib.mm_totalsum_f32.restype = C.c_int

@@ -575,6 +575,8 @@ static int64_t latpost_state_cap() { return int64_t((MM_LDS_MAX - mm_latpost_lds
 static int64_t latcost_state_cap() { return int64_t((MM_LDS_MAX - mm_latcost_lds_bytes(0)) / (mm_latcost_lds_bytes(1) - mm_latcost_lds_bytes(0))); }
 // mm_latticebest_f32: the same workgroup, three per-state LDS words
 static int64_t latbest_state_cap() { return int64_t((MM_LDS_MAX - mm_latbest_lds_bytes(0)) / (mm_latbest_lds_bytes(1) - mm_latbest_lds_bytes(0))); }
+// mm_latticesample_f32: its forward pass is mm_latticeposteriors_f32's, and the draw needs less
+static int64_t latsample_state_cap() { return latpost_state_cap(); }
 
 // item / tropical kernels: `kernel` keeps the state vectors in LDS; `big` is the same kernel with the vectors in global
 // memory, for FSMs beyond the LDS (the reference has no size limit: src/linalg.jl:170-181)
@@ -2884,6 +2886,13 @@ int mm_batch_kernels(mm_batch_t h, int entry, char *buf, size_t n) {
             "over the records of each cell in one pass and one barrier per step, three rotating state vectors in LDS, integer max, the best path traced in the "
             "backward loop, " + std::to_string(mm_latbest_lds_bytes(1) - mm_latbest_lds_bytes(0)) + " bytes of LDS per state); state cap " + std::to_string(latbest_state_cap());
         if (mm_latbest_lds_bytes(h->max_S1p) > MM_LDS_MAX) s += "; " + std::to_string(h->max_S1p) + " states exceed the cap";
+    } else if (entry == 22) {  // mm_latticesample_f32
+        if (h->semiring != MM_TROPICAL) return fail(MM_ERR_UNSUPPORTED, "mm_batch_kernels: mm_latticesample_f32 runs on tropical batches only");
+        s = "mm_latsample_fwd_kernel<" + std::to_string(latpost_nt(h)) + "> (mm_latpost_fb_kernel's forward pass alone: every record's forward value) + "
+            "mm_latsample_kernel<" + std::to_string(latpost_nt(h)) + "> (one workgroup per utterance and " + std::to_string(MM_LS_CHUNK) +
+            " samples, serial over the transitions backwards: a Gumbel-max draw among the records into each sample's state, a 64-bit occupancy mask per state "
+            "and 64-bit integer max in LDS); state cap " + std::to_string(latsample_state_cap());
+        if (mm_latsample_lds_bytes(h->max_S1p) > MM_LDS_MAX) s += "; " + std::to_string(h->max_S1p) + " states exceed the cap";
     } else if (entry == 2) {  // mm_pdfposteriors_ex: what its last call on this batch launched
         s = h->gen.last_kernels.empty() ? std::string("mm_generic_kernel (not called yet)") : h->gen.last_kernels;
     } else {
@@ -4962,6 +4971,59 @@ int mm_latticebest_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, c
     lb.path = path;
     lb.psb = psb;
     return mm_launch_latbest(h->B, nt, h->max_S1p, p, lp, lb, static_cast<hipStream_t>(stream));
+}
+
+// ---- lattice path sampling (mm_kernel_latsample.hip): the forward pass of the lattice posteriors, then record sequences drawn
+// backwards from the lattice's posterior
+int mm_latticesample_f32(mm_batch_t h, const float *V, int64_t vsb, int64_t vsn, const int32_t *lens, int64_t N, const int64_t *offsets,
+                         const int32_t *arc, int64_t nrec, const float *extra, int64_t nsamples, int64_t seed, float *fwd, int64_t *rec, int64_t rsb,
+                         int64_t rsk, int32_t *path, int64_t psb, int64_t psk, float *logprob, int64_t lsb, float *logz, void *stream) {
+    const std::string who = "mm_latticesample_f32";
+    // what the arguments alone show comes first, then the batch's refusals
+    if (!offsets || !logz) return fail(MM_ERR_INVALID, who + ": offsets/logz is NULL");
+    if (nrec < 0) return fail(MM_ERR_INVALID, who + ": nrec must be >= 0");
+    if (nrec > 0 && (!arc || !fwd)) return fail(MM_ERR_INVALID, who + ": arc/fwd is NULL with nrec > 0");
+    if (nsamples < 1) return fail(MM_ERR_INVALID, who + ": nsamples must be >= 1");
+    if (!rec && !path) return fail(MM_ERR_INVALID, who + ": rec and path are both NULL");
+    if (rec && (rsk < N || rsb < nsamples * rsk)) return fail(MM_ERR_DIM, who + ": rec_stride_k < N or rec_stride_b < nsamples * rec_stride_k");
+    if (path && (psk < N || psb < nsamples * psk)) return fail(MM_ERR_DIM, who + ": path_stride_k < N or path_stride_b < nsamples * path_stride_k");
+    if (logprob && lsb < nsamples) return fail(MM_ERR_DIM, who + ": lp_stride_b < nsamples");
+    if (nsamples > int64_t(MM_LS_CHUNK) * MM_LS_MAX_CHUNKS)
+        return fail(MM_ERR_UNSUPPORTED, who + ": more than " + std::to_string(int64_t(MM_LS_CHUNK) * MM_LS_MAX_CHUNKS) + " samples in one call");
+    if (h && h->semiring != MM_TROPICAL)
+        return fail(MM_ERR_UNSUPPORTED, who + ": tropical batches only (this batch is " + (h->semiring == MM_LOG ? "log-semiring" : "ProbSemiring") + ")");
+    int rc = check_run(h, who.c_str(), V, N, MM_TROPICAL);
+    if (rc) return rc;
+    if (mm_latsample_lds_bytes(h->max_S1p) > MM_LDS_MAX)
+        return fail(MM_ERR_UNSUPPORTED, who + ": " + std::to_string(h->max_S1p) + " states (padded) exceed the " + std::to_string(latsample_state_cap()) +
+                                            " whose vectors fit the LDS (16 bytes per state)");
+    const int nt = latpost_nt(h);
+    if (nt != 256 && nt != 512 && nt != 1024) return fail(MM_ERR_INVALID, who + ": MM_LATPOST_NT must be 256, 512 or 1024");
+    rc = ensure_item_forms(h, stream);
+    if (!rc) rc = ensure_lattice_arcs(h, stream);
+    if (rc) return rc;
+    const RunParams p = run_params(h, V, vsb, vsn, lens, N);
+    LatPostParams lp{};
+    lp.arcs = static_cast<const LatticeDev *>(h->d_lat.get());
+    lp.offs = reinterpret_cast<const long long *>(offsets);
+    lp.arc = arc;
+    lp.nrec = nrec;
+    lp.extra = extra;
+    lp.post = fwd;
+    lp.logz = logz;
+    LatSampleParams ls{};
+    ls.nsamples = nsamples;
+    ls.key0 = unsigned(uint64_t(seed));
+    ls.key1 = unsigned(uint64_t(seed) >> 32);
+    ls.rec = reinterpret_cast<long long *>(rec);
+    ls.rsb = rsb;
+    ls.rsk = rsk;
+    ls.path = path;
+    ls.psb = psb;
+    ls.psk = psk;
+    ls.logprob = logprob;
+    ls.lsb = lsb;
+    return mm_launch_latsample(h->B, nt, h->max_S1p, p, lp, ls, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -528,6 +528,24 @@ struct LatBestParams {       // beside a LatPostParams, whose post is score and 
 int mm_launch_latbest(int64_t B, int nt, int max_S1p, const RunParams &p, const LatPostParams &lp, const LatBestParams &lb, hipStream_t stream);
 size_t mm_latbest_lds_bytes(int S1p);  // a head + 12 bytes per state: three 32-bit words
 
+// ---- lattice path sampling (mm_latsample_tu.hip: mm_latsample_fwd_kernel, the forward half of mm_latpost_fb_kernel, and
+// mm_latsample_kernel, one workgroup per utterance and chunk of MM_LS_CHUNK samples; the workgroup is MM_LATPOST_NT's)
+#define MM_LS_CHUNK 64       // samples of a workgroup: one bit each in a state's occupancy mask
+#define MM_LS_MAX_CHUNKS 65535  // the grid's y extent
+struct LatSampleParams {     // beside a LatPostParams, whose post is fwd (gamma unused)
+    long long nsamples;
+    unsigned key0, key1;     // the seed's two halves, as SampleParams splits it
+    long long *rec;          // [b * rsb + k * rsk + t] the samples' records; NULL: not asked for
+    long long rsb, rsk;
+    int *path;               // [b * psb + k * psk + t] their source states; NULL: not asked for
+    long long psb, psk;
+    float *logprob;          // [b * lsb + k]; NULL: not asked for
+    long long lsb;
+};
+// the forward pass in its instance of `nt` threads, then the samples
+int mm_launch_latsample(int64_t B, int nt, int max_S1p, const RunParams &p, const LatPostParams &lp, const LatSampleParams &ls, hipStream_t stream);
+size_t mm_latsample_lds_bytes(int S1p);  // the larger of the forward pass's (16 bytes per state) and the sampler's (a head + 8 per state)
+
 // ---- posteriors with call-time arc weights (mm_weighted_tu.hip: mm_weights_kernel, mm_log_kernel's forward half on the call's
 // descriptors, mm_weighted_bwd_kernel and mm_weighted_scatter_kernel on the item form)
 struct UttDesc;  // mm_kernels.hip

@@ -1,6 +1,6 @@
 // mm_kernel_latbest.hip -- lattice best paths (mm_latticebest_f32: the tropical forward-backward over the records of a lattice of
 // mm_lattice_f32, under the call's V and an optional score per record: the best path's weight, every record's through-score below it,
-// and the best path itself as records and states).  Included by mm_latbest_tu.hip only.
+// and the best path itself as records and states).  Included by mm_latbest_tu.hip, and by mm_kernel_latsample.hip for lb_key.
 //
 // mm_latbest_kernel<NT>   mm_latpost_fb_kernel's organisation -- one workgroup of NT threads per utterance, serial over its transitions,
 //                         the work of a step the records of its cell, state vectors in LDS as order-preserving codes of floats, an

@@ -24,7 +24,8 @@
 //                              for no global load of its own.
 // mm_latpost_gamma_kernel<NT>  one workgroup per (b, n): exp(post[r]) of the cell summed by the pdf of the source in 64-bit fixed
 //                              point in LDS, the row written with its zeros.
-// lp_fb<NT, COST>              the body of both forward-backward kernels.  COST (mm_latcost_fb_kernel<NT>, mm_latticecost_f32) carries
+// lp_fb<NT, COST, FWD_ONLY>    the body of both forward-backward kernels (FWD_ONLY: of mm_kernel_latsample.hip's forward pass, which ends
+//                              behind logz and the -inf fill: post keeps every record's forward value x_r).  COST (mm_latcost_fb_kernel<NT>, mm_latticecost_f32) carries
 //                              the expected cost of the paths beside the vectors: a float C per state (ca_t forward, cb_{t+1} backward,
 //                              relative to the maximum Cm of the step that finished it -- forward, Cm accumulates in a double, which
 //                              ends as the risk) and a signed 64-bit sum.  Pass A also takes the block's maximum vmax of |v_r|,
@@ -206,7 +207,7 @@ __device__ __forceinline__ void lp_ahead_all(const LatPostParams &lp, const floa
     lp_ahead3(u, a);
 }
 
-template <int NT, bool COST>
+template <int NT, bool COST, bool FWD_ONLY = false>
 __device__ __forceinline__ void lp_fb(char *lp_smem, const RunParams &p, const LatPostParams &lp, const LatCostParams &lc) {
     unsigned *const slot_m = reinterpret_cast<unsigned *>(lp_smem);       // [2] the step's maximum
     unsigned *const slot_y = slot_m + 2;                                   // [2] the cell's maximum (backward)
@@ -397,7 +398,7 @@ __device__ __forceinline__ void lp_fb(char *lp_smem, const RunParams &p, const L
             if constexpr (COST) lc.diff[r] = 0.f;
         }
     }
-    if (!alive) return;
+    if (FWD_ONLY || !alive) return;
 
     // ---- backward: b_len = one at f
     for (int s = tid; s < S1; s += NT) {

@@ -195,6 +195,19 @@ class LatticeBest(NamedTuple):
     path: object
 
 
+class LatticeSamples(NamedTuple):
+    """What ``BatchedFSM.latticesample`` returns.  ``rec[B, K, N]`` int64: sample k's record of every transition, an index into
+    ``lat.arc``; ``path[B, K, N]`` int32: the source state of that record, ``bestpath``'s convention (both -1 at and behind ``len``
+    and without a path; ``path`` None when not asked for); ``logprob[B, K]``: the log posterior of the sampled record sequence
+    among the lattice's paths (-inf without a path; None when not asked for); ``logz[B]``: the lattice's log-sum,
+    ``latticeposteriors``' (-inf: no path)."""
+
+    rec: object
+    path: object
+    logprob: object
+    logz: object
+
+
 def _on_device(x, dtype, device):
     """A member of a lattice (or ``extra``) as a contiguous tensor of ``dtype`` on ``device``: a tensor, or anything NumPy reads."""
     import torch
@@ -1055,11 +1068,12 @@ class BatchedFSM:
         leakyposteriors, "entropy" = pathentropy, "filter" = filterposteriors, "window" = windowposteriors,
         "vitwindow" = viterbiwindow (tropical batches), "weighted" = weightedposteriors, "segment" = segmentposteriors,
         "classpath" = classpath (tropical batches), "lattice" = lattice (tropical batches), "latticeposteriors" = latticeposteriors
-        (tropical batches), "latticecost" = latticecost (tropical batches), "latticebest" = latticebest (tropical batches)."""
+        (tropical batches), "latticecost" = latticecost (tropical batches), "latticebest" = latticebest (tropical batches), "latticesample" =
+        latticesample (tropical batches)."""
         import ctypes
 
         buf = ctypes.create_string_buffer(1024)
-        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13, "arcclass": 14, "scored": 15, "classcost": 16, "classpath": 17, "lattice": 18, "latticeposteriors": 19, "latticecost": 20, "latticebest": 21}[semiring], buf, 1024))
+        check(lib.mm_batch_kernels(self._h, {"log": 0, "tropical": 1, "export": 3, "arcs": 4, "sample": 5, "cost": 6, "leaky": 7, "entropy": 8, "filter": 9, "window": 10, "vitwindow": 11, "weighted": 12, "segment": 13, "arcclass": 14, "scored": 15, "classcost": 16, "classpath": 17, "lattice": 18, "latticeposteriors": 19, "latticecost": 20, "latticebest": 21, "latticesample": 22}[semiring], buf, 1024))
         return buf.value.decode()
 
     def kernels_generic(self) -> str:
@@ -1220,6 +1234,34 @@ class BatchedFSM:
         check(lib.mm_latticebest_f32(*_head(self._h, Vt, lt, N), offsets.data_ptr(), arc.data_ptr(), nrec, _ptr(et), best.data_ptr(), score.data_ptr(),
                                      _ptr(rec), N, _ptr(path), N, self._stream(torch)))
         return LatticeBest(*_results((best, score, rec, path), as_numpy))
+
+    def latticesample(self, lat, V, nsamples, seed=0, lens=None, extra=None, want_path=True, want_logprob=True):
+        """Lattice path sampling (mm_latticesample_f32): ``nsamples`` independent draws per utterance from the posterior over the
+        RECORD sequences of ``lat`` -- a ``Lattice`` of ``BatchedFSM.lattice`` on this batch, or a subset of one -- under the
+        emissions ``V`` of THIS call and an optional score ``extra`` per record; parallel entries between two states are separate
+        outcomes.  Returns ``LatticeSamples(rec, path, logprob, logz)``: ``rec[B, K, N]`` int64 the records (indices into
+        ``lat.arc``), ``path[B, K, N]`` int32 their source states (None with ``want_path=False``), both -1 at and behind ``len`` and
+        without a path; ``logprob[B, K]`` the log posterior of each sample (None with ``want_logprob=False``; -inf without a path);
+        ``logz[B]`` as ``latticeposteriors`` returns it.  A sample is a function of the lattice, ``V``, ``extra``, ``lens``,
+        ``seed``, its utterance's POSITION b and its index k alone: the first samples of a larger call are those of a smaller one,
+        a repeated call returns the same bits, and equal utterances at different positions get different samples.  A record with
+        ``extra = -inf`` is never drawn.  The costs of the samples (an edit distance, say) go into
+        ``lattices.lattice_sampled_risk``.  Inputs and results as ``latticeposteriors`` handles them, its ValueError for a lattice
+        cut by ``max_arcs`` included.  Tropical batches only."""
+        torch, Vt, lt, as_numpy = self._prep(V, lens)
+        B, N, P = Vt.shape
+        dev = Vt.device
+        offsets, arc, nrec, et = self._lattice_inputs("latticesample", torch, lat, Vt, extra)
+        K = int(nsamples)
+        Ka = max(K, 0)
+        fwd = torch.empty(nrec, dtype=torch.float32, device=dev)
+        rec = torch.empty((B, Ka, N), dtype=torch.int64, device=dev)
+        path = torch.empty((B, Ka, N), dtype=torch.int32, device=dev) if want_path else None
+        logprob = torch.empty((B, Ka), dtype=torch.float32, device=dev) if want_logprob else None
+        logz = torch.empty(B, dtype=torch.float32, device=dev)
+        check(lib.mm_latticesample_f32(*_head(self._h, Vt, lt, N), offsets.data_ptr(), arc.data_ptr(), nrec, _ptr(et), K, int(seed), fwd.data_ptr(),
+                                       rec.data_ptr(), Ka * N, N, _ptr(path), Ka * N, N, _ptr(logprob), Ka, logz.data_ptr(), self._stream(torch)))
+        return LatticeSamples(*_results((rec, path, logprob, logz), as_numpy))
 
     def latticeposteriors(self, lat, V, lens=None, extra=None, want_gamma=True):
         """Lattice posteriors (mm_latticeposteriors_f32): the log-semiring forward-backward over the records of ``lat`` -- a
@@ -1808,6 +1850,17 @@ def latticebest(fsm, lat, Vhats, Chats=None, extra=None):
         raise TypeError("latticebest needs TropicalSemiring FSMs")
     V, lens = _need_expanded(Vhats)
     return bf.latticebest(lat, V, lens, extra)
+
+
+def latticesample(fsm, lat, Vhats, nsamples, seed=0, Chats=None, extra=None):
+    """Lattice path sampling -- see ``BatchedFSM.latticesample`` -- in ``lattice``'s call shape: the ``LatticeSamples`` (NumPy members,
+    with ``path`` and ``logprob``) of ``nsamples`` draws per utterance from the posterior of the lattice ``lat`` of the batch under the
+    expanded emissions ``Vhats``.  Tropical FSMs."""
+    bf = _as_batch(fsm, Chats)
+    if bf.semiring != "tropical":
+        raise TypeError("latticesample needs TropicalSemiring FSMs")
+    V, lens = _need_expanded(Vhats)
+    return bf.latticesample(lat, V, nsamples, seed, lens, extra)
 
 
 def _total(fsm, n, cumulative):

@@ -25,6 +25,9 @@ it is MPE / MWE (Povey 2003), with minus [pdf of the record's source = the align
 and the weight of its best path, ``best_b = max_{path} W(path)`` (mm_latticebest_f32; ``lattice_best_score``): the Viterbi score of
 perceptron and max-margin losses, whose gradient is the indicator of the best path's records and pdfs.
 
+and, for a cost that does NOT add up along a path (a word error rate, an edit distance), the sampled risk: the mean cost of paths
+drawn from the lattice's posterior (mm_latticesample_f32; ``lattice_sampled_risk``) with the score-function gradient.
+
 A launch chain on the caller's stream.
 """
 from __future__ import annotations
@@ -171,6 +174,70 @@ def lattice_best_score(bf, lat, V, extra=None, lens=None):
     path (the indicator of ``rec``) and to ``V`` at ``(b, n, pdf(path[b, n]))``, a subgradient where best paths tie.  Utterances
     without a path have ``best = -inf`` and zero gradients.  ``bf``: a tropical ``BatchedFSM``."""
     return _best_function().apply(V, extra, bf, lat, lens)
+
+
+def _sampled_risk_function():
+    import torch
+
+    class _LatticeSampledRisk(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, V, extra, costs, rec, path, logz, pdfs):
+            K = costs.shape[1]
+            c = costs.detach().to(torch.float32)
+            # the leave-one-out weights: (c_k - mean of the others) / K; they sum to 0 over k
+            w = (c - (c.sum(1, keepdim=True) - c) / (K - 1)) / K
+            ctx.save_for_backward(w, rec, path, pdfs)
+            ctx.shape = tuple(V.shape)
+            ctx.nrec = None if extra is None else extra.numel()
+            return torch.where(torch.isneginf(logz), torch.zeros_like(logz), c.mean(1))
+
+        @staticmethod
+        def backward(ctx, g):
+            w, rec, path, pdfs = ctx.saved_tensors
+            on = path >= 0  # (the frames of the samples; none for an utterance without a path, whatever its g)
+            v = (g[:, None] * w)[:, :, None].expand_as(path)[on]
+            gV = gE = None
+            if ctx.needs_input_grad[0]:
+                b, _, n = torch.nonzero(on, as_tuple=True)
+                gV = torch.zeros(ctx.shape, dtype=g.dtype, device=g.device)
+                gV.index_put_((b, n, pdfs[b, path[on].long()]), v, accumulate=True)
+            if ctx.nrec is not None and ctx.needs_input_grad[1]:
+                gE = torch.zeros(ctx.nrec, dtype=g.dtype, device=g.device)
+                gE.index_put_((rec[on],), v, accumulate=True)
+            return gV, gE, None, None, None, None, None
+
+    return _LatticeSampledRisk
+
+
+def lattice_sampled_risk(bf, lat, V, samples, costs, extra=None):
+    """``risk[B]``, the sampled risk of the lattice ``lat`` for costs that do NOT add up along a path: ``risk[b] = mean_k costs[b, k]``
+    with ``costs`` [B, K] whatever the caller computed from ``samples`` -- the ``LatticeSamples`` of ``bf.latticesample(lat, V, K, ..)``
+    with its ``path``, on the same ``V`` and ``extra`` -- such as the edit distance of each sampled word sequence to the transcript
+    (Shannon, "Optimizing expected word error rate via sampling for speech recognition", Interspeech 2017; Prabhavalkar et al.,
+    "Minimum word error rate training for attention-based sequence-to-sequence models", ICASSP 2018).  K >= 2.  ``costs`` takes no
+    gradient.  Differentiable in ``V`` [B, N, P] float32 on the HIP device and in the per-record scores ``extra`` by the
+    score-function estimator with the leave-one-out baseline:
+
+        w_k = (c_k - mean_{k' != k} c_k') / K
+        d risk[b] / d V[b, n, p] ~ sum_k w_k [pdf(path[b, k, n]) = p]        d risk[b] / d extra[r] ~ sum_k w_k [rec[b, k, n] = r]
+
+    The gradient of a path's log posterior is its indicator minus the posteriors gamma; the weights of an utterance sum to 0, so
+    the gamma term drops out and no posterior call is needed.  The estimate is unbiased for the gradient of the expected cost (it is
+    K / (K - 1) times the sample covariance of the cost and the indicator).  Utterances without a path have risk 0 and zero
+    gradients.  ``lat`` is read for nothing but its place in the call (the samples name its records).  ``bf``: a tropical
+    ``BatchedFSM``."""
+    import torch
+
+    if samples.path is None:
+        raise ValueError("lattice_sampled_risk: the samples need their path (latticesample(.., want_path=True))")
+    dev = V.device
+    rec, path, logz = (torch.as_tensor(x).to(dev) for x in (samples.rec, samples.path, samples.logz))
+    costs = torch.as_tensor(costs).to(dev)
+    if costs.dim() != 2 or tuple(costs.shape) != tuple(path.shape[:2]):
+        raise ValueError(f"lattice_sampled_risk: costs must be [B, K] = {tuple(path.shape[:2])}, got {tuple(costs.shape)}")
+    if costs.shape[1] < 2:
+        raise ValueError("lattice_sampled_risk: the leave-one-out baseline needs K >= 2 samples")
+    return _sampled_risk_function().apply(V, extra, costs, rec, path, logz, _state_pdfs(bf, dev))
 
 
 class RecordIndex(NamedTuple):
