@@ -801,16 +801,25 @@ __device__ __forceinline__ void pair_one(const mm_f32x2 (&wr)[KA / 2], const uns
         x[s0 + 1] = ldsr2(ar[2 * (K2 + D) + 1] + rdoff);
     }
 }
-// Two pairs whose products are all in straight-line code: pair K2 goes to the running sums, pair K2 + 1 to sums of
-// its own (accN), which the caller adds to the running sums unless a segment ends between the two.
+// the same into a register pair of its own: dst = w * x + add (add stays what it was)
+__device__ __forceinline__ void pk_fma_wlo_to(mm_f32x2 &dst, const mm_f32x2 &w2, const mm_f32x2 &x, const mm_f32x2 &add) {
+    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(dst) : "v"(w2), "v"(x), "v"(add));
+}
+// Two pairs (a "quad") whose products are all in straight-line code, ONE chain of four packed FMAs: pair K2 goes to the
+// running sums (cur), pair K2 + 1 continues them in the OTHER register pair (nxt = cur + its products) -- speculating that
+// no segment ends between the two.  cur then still holds the sums as they stood after pair K2: if a segment does end there,
+// the caller finishes from cur and computes nxt again from zero (pair_two_again).  The two register pairs swap their roles
+// from quad to quad (statically: MM_PAIR_CUR / MM_PAIR_NXT), so the common path of a quad is the four FMAs and nothing
+// else.  The operand slots of pair K2 + 1 are reloaded by the caller, behind the test (pair_two_reload): the rare path
+// reads them again.
 template <int K2, int KA, int D>
-__device__ __forceinline__ void pair_two(const mm_f32x2 (&wr)[KA / 2], const unsigned (&ar)[KA], mm_f32x2 (&x)[2 * D], mm_f32x2 &accA,
-                                         mm_f32x2 &accN, unsigned rdoff) {
+__device__ __forceinline__ void pair_two(const mm_f32x2 (&wr)[KA / 2], const unsigned (&ar)[KA], mm_f32x2 (&x)[2 * D], mm_f32x2 &cur,
+                                         mm_f32x2 &nxt, unsigned rdoff) {
     constexpr int s0 = (2 * K2) % (2 * D), s1 = (2 * K2 + 2) % (2 * D);
-    pk_fma_wlo(accA, wr[K2], x[s0]);
-    pk_mul_wlo(accN, wr[K2 + 1], x[s1]);
-    pk_fma_whi(accA, wr[K2], x[s0 + 1]);
-    pk_fma_whi(accN, wr[K2 + 1], x[s1 + 1]);
+    pk_fma_wlo(cur, wr[K2], x[s0]);
+    pk_fma_whi(cur, wr[K2], x[s0 + 1]);
+    pk_fma_wlo_to(nxt, wr[K2 + 1], x[s1], cur);
+    pk_fma_whi(nxt, wr[K2 + 1], x[s1 + 1]);
 #ifdef MM_PAIR_DUMMY
     {   // timing experiment (never shipped): the instruction mix of a two-utterance float64 form -- per arc one more 64-bit FMA and
         // a move next to the (here: packed) FMA that exists; results go nowhere
@@ -827,33 +836,51 @@ __device__ __forceinline__ void pair_two(const mm_f32x2 (&wr)[KA / 2], const uns
         x[s0] = ldsr2(ar[2 * (K2 + D)] + rdoff);
         x[s0 + 1] = ldsr2(ar[2 * (K2 + D) + 1] + rdoff);
     }
+}
+// (rare path) a segment ended after pair K2: the sums of pair K2 + 1 from zero
+template <int K2, int KA, int D>
+__device__ __forceinline__ void pair_two_again(const mm_f32x2 (&wr)[KA / 2], const mm_f32x2 (&x)[2 * D], mm_f32x2 &nxt) {
+    constexpr int s1 = (2 * K2 + 2) % (2 * D);
+    pk_mul_wlo(nxt, wr[K2 + 1], x[s1]);
+    pk_fma_whi(nxt, wr[K2 + 1], x[s1 + 1]);
+}
+template <int K2, int KA, int D>
+__device__ __forceinline__ void pair_two_reload(const unsigned (&ar)[KA], mm_f32x2 (&x)[2 * D], unsigned rdoff) {
+    constexpr int s1 = (2 * K2 + 2) % (2 * D);
     if constexpr (2 * (K2 + 1 + D) < KA) {
         x[s1] = ldsr2(ar[2 * (K2 + 1 + D)] + rdoff);
         x[s1 + 1] = ldsr2(ar[2 * (K2 + 1 + D) + 1] + rdoff);
     }
 }
-#define MM_PAIR_FMA(k) pair_one<(2 * (k) < KA ? (k) : 0), KA, D, PHASE == 0>(rg.w2, rg.a, x, accA, accB, rdoff);
+// the running sums of the quad that starts at pair k (k even) live in accA or accB by the parity of the quad
+#define MM_PAIR_CUR(k) (((k) & 2) ? accB : accA)
+#define MM_PAIR_NXT(k) (((k) & 2) ? accA : accB)
+#define MM_PAIR_FMA(k, acc) pair_one<(2 * (k) < KA ? (k) : 0), KA, D, PHASE == 0>(rg.w2, rg.a, x, acc, acc, rdoff);
 #define MM_PAIR_END(k) ((((k) < 32 ? em_lo : em_hi) >> ((k) & 31)) & 1u)
-#define MM_PAIR_ONE(k)                   \
-    if constexpr (2 * (k) < KA) {        \
-        MM_PAIR_FMA(k)                   \
-        if (MM_PAIR_END(k)) finish();    \
+#define MM_PAIR_ONE(k, acc)               \
+    if constexpr (2 * (k) < KA) {         \
+        MM_PAIR_FMA(k, acc)               \
+        if (MM_PAIR_END(k)) finish(acc);  \
     }
 // Two pairs per wave-uniform test of the end mask (a taken branch costs a wave about 30 cycles with its bit test, as
 // much as the pair's gathers): the bits are looked at one by one only when one of the two pairs ends a segment.
+// Common path: the four FMAs of pair_two.  Rare path: a segment that ends after pair k is finished from the sums as they
+// stood there (cur), and pair k + 1 starts again from zero; one that ends after pair k + 1 is finished from nxt, which
+// finish() zeroes.  Either way the running sums leave the quad in nxt, the next quad's cur.
 #define MM_PAIR_TWO(k)                                                                                       \
-    if constexpr (2 * (k) + 2 < KA && MM_PAIR_DOUBLE) {                                                      \
-        pair_two<(2 * (k) + 2 < KA ? (k) : 0), KA, D>(rg.w2, rg.a, x, accA, accN, rdoff);                    \
+    if constexpr (2 * (k) + 2 < KA) {                                                                        \
+        pair_two<(2 * (k) + 2 < KA ? (k) : 0), KA, D>(rg.w2, rg.a, x, MM_PAIR_CUR(k), MM_PAIR_NXT(k), rdoff); \
         if (__builtin_expect(((((k) < 32 ? em_lo : em_hi) >> ((k) & 31)) & 3u) != 0u, 0)) {                  \
-            if (MM_PAIR_END(k)) finish();                                                                    \
-            accA += accN;                                                                                    \
-            accN = mm_f32x2{0.f, 0.f};                                                                       \
-            if (MM_PAIR_END((k) + 1)) finish();                                                              \
+            if (MM_PAIR_END(k)) {                                                                            \
+                finish(MM_PAIR_CUR(k));                                                                      \
+                pair_two_again<(2 * (k) + 2 < KA ? (k) : 0), KA, D>(rg.w2, x, MM_PAIR_NXT(k));               \
+            }                                                                                                \
+            if (MM_PAIR_END((k) + 1)) finish(MM_PAIR_NXT(k));                                                \
         }                                                                                                    \
-        accA += accN;                                                                                        \
-    } else {                                                                                                 \
-        MM_PAIR_ONE(k)                                                                                       \
-        MM_PAIR_ONE((k) + 1)                                                                                 \
+        pair_two_reload<(2 * (k) + 2 < KA ? (k) : 0), KA, D>(rg.a, x, rdoff);                                \
+    } else { /* the window's tail where KA is no multiple of 4: one pair at a time, on into the last quad's sums */ \
+        MM_PAIR_ONE(k, MM_PAIR_CUR(k))                                                                       \
+        MM_PAIR_ONE((k) + 1, MM_PAIR_CUR(k))                                                                 \
     }
 // A wave lowers its issue priority as it advances through the step (MM_PAIR_PRIO): the arbiter serves the highest
 // priority, then the OLDEST wave, so with equal priorities the four waves of a SIMD finish one after the other and the
@@ -920,7 +947,6 @@ __device__ __forceinline__ void pair_agent(const RunParams &p, int pair, int hse
 #ifndef MM_PAIR_EXITS_B
 #define MM_PAIR_EXITS_B 1  // phase B leaves the arc window after the wave's last segment like phase A (until the finishes went linear: 8 spilled registers)
 #endif
-    constexpr bool MM_PAIR_DOUBLE = true;
     // LINF: the finishes stay in the linear domain (round 5): the service wave stages the step's emissions as factors 2^(v - E - S),
     // a finish is p = s * factor (and, in phase B, q = s * partner), BOTH directions store p -- the vector with the frame's emission --
     // and combine with their own s (the vector without it): alpha_n beta_n = (T' alpha_{n-1}) (beta_n (*) lhs_n) either way.
@@ -1597,13 +1623,14 @@ __device__ __forceinline__ void pair_agent(const RunParams &p, int pair, int hse
                 // even / odd arcs (phase B has no registers to spare: one chain there)
                 float worst = 0.f;
                 unsigned smin = 0xffffffffu;
-                mm_f32x2 accA = {0.f, 0.f}, accN = {0.f, 0.f};
-                mm_f32x2 &accB = accA;
+                // the running sums: one chain, in accA and accB by turns (MM_PAIR_TWO)
+                mm_f32x2 accA, accB = {0.f, 0.f};
+                asm("v_mov_b64 %0, 0" : "=v"(accA));
                 unsigned long long lgw = lgw0;
-                auto finish = [&]() {
+                auto finish = [&](mm_f32x2 &acc) {
                     const int lg = (int)(lgw & 15ull);
                     lgw >>= 4;
-                    float s0 = accA.x, s1 = accA.y;
+                    float s0 = acc.x, s1 = acc.y;
                     if (lg) grp_sum_last2(s0, s1, lg);
                     const unsigned pos8 = info & 0xffffu;
                     if constexpr (LINF) {
@@ -1654,7 +1681,9 @@ __device__ __forceinline__ void pair_agent(const RunParams &p, int pair, int hse
                         ldsw2((info2 >> 16) + L::Q(WR), fast_exp2(st0 + al.x), fast_exp2(st1 + al.y));  // A .* B   (:154)
                     }
                     }
-                    accA = mm_f32x2{0.f, 0.f};
+                    // the sums start again: ONE 64-bit move (a plain assignment became a copy of a zeroed register pair that the
+                    // compiler first had to put together: three moves).  Dead, and dropped, where what follows starts from a product.
+                    asm("v_mov_b64 %0, 0" : "=v"(acc));
                     sa += 512u;
                     // (a plain copy is coalesced away and paid for with register moves on the no-finish path of EVERY pair)
                     asm volatile("v_mov_b32 %0, %1" : "=v"(info) : "v"(infoN));
